@@ -26,7 +26,12 @@ through libmsiren's C ABI (include/msiren.h, "multi-GPU"): no torch.distributed,
 the process; "nccl" -- the same over torch.distributed (RCCL); "gloo" -- torch.distributed on the CPU,
 which lets several ranks share one card to rehearse the N > 1 path on a 1-GPU box.
 
-Prints ONE JSON line on rank 0 (README / DESIGN.md §5 describe the fields).
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the roofline of the timed
+region.  --full adds everything measured or checked beyond that (the single-stream roofline phase, the sustained-MFMA probe, the
+host->host and slice->slice rates, the other BASELINE configurations in child runs, the CPU baseline, the cross-rank weight check
+at N = 1, the strong region of an N > 1 run).  --dump-outputs DIR writes what the last timed step computed as .npy files.
+
+Prints ONE JSON line on rank 0 (README / DESIGN.md §6 describe the fields).
 """
 
 from __future__ import annotations
@@ -47,6 +52,7 @@ FP32_MFMA_PEAK_TFLOPS = 157.3  # MI355X_MICROARCH.md: dense f32-input MFMA peak 
 F16_MFMA_PEAK_TFLOPS = 2500.0  # dense fp16/bf16 MFMA peak (no sparsity)
 MIN_WARMUP_S = 0.4             # untimed: the card needs a few hundred ms under load before its clock settles
 MIN_ROOFLINE_LAUNCHES = 200
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files of all ranks together
 
 
 def parse(argv=None):
@@ -74,6 +80,12 @@ def parse(argv=None):
     ap.add_argument("--brain-mask", action="store_true",
                     help="elliptical brain-like mask on the synthetic slices (43 %% of the tiles become black; only "
                          "--pipeline reconstruct skips them, as the reference's black-patch filter does)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (see the module docstring); "
+                         "--no-cpu-baseline / --no-extras / --no-strong leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32; a fixed seeded "
+                         f"sample of rows if the outputs exceed {DUMP_LIMIT_BYTES >> 20} MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the host->host and slice->slice rates after the timed region")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="wall budget of the CPU baseline sample")
@@ -93,6 +105,8 @@ def parse(argv=None):
                          "RANK / WORLD_SIZE=1 / MASTER_* set, what a scaling sweep's N = 1 point goes through) -- and fail "
                          "unless the two values agree within 3 %%")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.streams is None:
         args.streams = 3 if args.model == "deep_residual" else 2
     return args
@@ -134,6 +148,17 @@ def traffic_bytes(kernel):
             if e.get("kernel") == kernel:
                 return {"bytes_per_launch": e["bytes_per_launch"], "source": e.get("source", f"profiles/{rnd}/traffic.json")}
     return None
+
+
+def dump_outputs(directory, name, out, limit_bytes):
+    """--dump-outputs: `out` as directory/<name>.npy, float32.  Above `limit_bytes` a fixed sample of its rows along the leading
+    axis (default_rng(0), kept in order) stands for the whole, so that two builds run with the same arguments compare row for row."""
+    out = np.ascontiguousarray(out, dtype=np.float32)
+    if out.nbytes > limit_bytes:
+        keep = max(1, limit_bytes // out[0].nbytes)
+        out = out[np.sort(np.random.default_rng(0).choice(out.shape[0], size=keep, replace=False))]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), out)
 
 
 def cpu_baseline(sd, tiles, activation, budget_s):
@@ -338,13 +363,16 @@ def main():
         raise SystemExit(f"[rank {rank}] the communicator reports rank {comm_rank} of {comm_ranks}, the launcher {rank} of {world}")
     # Every rank evaluates the SAME 16 tiles with the weights it ended up with; the bit patterns of the outputs are
     # summed and MAX / MIN-reduced: equal <=> every rank holds the weights rank 0 loaded (a wrong blob on a receiving
-    # rank would otherwise be silent -- nothing else in the benchmark compares ranks).
-    probe_tiles = np.random.default_rng(4242).random((16, 32, 32), dtype=np.float32)
-    probe_sum = float(np.ascontiguousarray(model(probe_tiles)).view(np.uint32).astype(np.float64).sum())
-    sum_max, sum_min = group.max(probe_sum), group.min(probe_sum)
-    if sum_max != sum_min:
-        raise SystemExit(f"[rank {rank}] ranks disagree on the probe output (checksum {probe_sum:.0f}, max {sum_max:.0f}, "
-                         f"min {sum_min:.0f}): the weight broadcast did not replicate rank 0's state_dict")
+    # rank would otherwise be silent -- nothing else in the benchmark compares ranks).  One rank has nothing to compare: --full only.
+    probe_sum = identical = None
+    if world > 1 or args.full:
+        probe_tiles = np.random.default_rng(4242).random((16, 32, 32), dtype=np.float32)
+        probe_sum = float(np.ascontiguousarray(model(probe_tiles)).view(np.uint32).astype(np.float64).sum())
+        sum_max, sum_min = group.max(probe_sum), group.min(probe_sum)
+        if sum_max != sum_min:
+            raise SystemExit(f"[rank {rank}] ranks disagree on the probe output (checksum {probe_sum:.0f}, max {sum_max:.0f}, "
+                             f"min {sum_min:.0f}): the weight broadcast did not replicate rank 0's state_dict")
+        identical = True
 
     # Who sits where: every rank fills its own row of a (world x 9) table -- device index, PCI bus id (domain, bus, device,
     # function), CUs, clock, HBM, what its communicator says its rank is -- and one MAX-reduce hands rank 0 all of it
@@ -444,30 +472,38 @@ def main():
     timed_kernels = model.profile_kernels()   # what the timed region launched, as the library names it
     _lib.check(lib.msiren_profile_enable(h, 0))
     elapsed_local = t1 - t0
+    if args.dump_outputs and B > 0:
+        # the last timed step's buffer, read before anything behind the timed region launches again
+        if args.pipeline == "reconstruct":
+            name, out = "reconstructed_slices", d_recons[(nstep[0] - 1) % len(d_recons)].numpy()[:n_sl]
+        else:
+            name, out = "forward_tiles", d_outs[(nstep[0] - 1) % len(d_outs)].numpy()[:B]
+        dump_outputs(args.dump_outputs, name if world == 1 else f"{name}_rank{rank}", out, DUMP_LIMIT_BYTES // world)
     group.barrier()
     elapsed = group.max(elapsed_local)
 
+    alone_kernels = timed_kernels
     if args.streams > 1 and B > 0:
         # With two streams the launches of consecutive steps overlap, so a launch's own duration says
         # little about the kernel.  The roofline figure is therefore taken from a single-stream phase of
-        # the same process (kernel alone on the device), after the timed region.
-        _lib.check(lib.msiren_set_streams(h, 1))
-        for _ in range(8):
-            step()
-        model.sync()
-        _lib.check(lib.msiren_profile_enable(h, 1))
-        for _ in range(max(MIN_ROOFLINE_LAUNCHES, args.steps // 4) if n_sl <= 8 else max(20, args.steps // 4)):
-            step()
-        _lib.check(lib.msiren_profile_read(h, C.byref(launches), C.byref(trunk_ms)))
-        alone_kernels = model.profile_kernels()
-        _lib.check(lib.msiren_profile_enable(h, 0))
-        _lib.check(lib.msiren_set_streams(h, args.streams))
-    else:
-        alone_kernels = timed_kernels
+        # the same process (kernel alone on the device), after the timed region (--full).
+        alone_kernels = []
+        if args.full:
+            _lib.check(lib.msiren_set_streams(h, 1))
+            for _ in range(8):
+                step()
+            model.sync()
+            _lib.check(lib.msiren_profile_enable(h, 1))
+            for _ in range(max(MIN_ROOFLINE_LAUNCHES, args.steps // 4) if n_sl <= 8 else max(20, args.steps // 4)):
+                step()
+            _lib.check(lib.msiren_profile_read(h, C.byref(launches), C.byref(trunk_ms)))
+            alone_kernels = model.profile_kernels()
+            _lib.check(lib.msiren_profile_enable(h, 0))
+            _lib.check(lib.msiren_set_streams(h, args.streams))
 
     # behind the timed region and the roofline phase (the card is warm): the power-limited MFMA ceiling of this card
     sustained_tflops = sustained_mhz = None
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         t_, m_ = C.c_double(), C.c_double()
         _lib.check(lib.msiren_mfma_sustained_probe(h, C.byref(t_), C.byref(m_)))
         sustained_tflops, sustained_mhz = t_.value, m_.value
@@ -477,7 +513,7 @@ def main():
     # ">= 0.9 linear" is about -- is measured behind it, by all ranks, in the same process group.
     strong = None
     default_sizing = not args.total_slices and args.slices == 1
-    if world > 1 and default_sizing and not args.no_strong and not deep and args.pipeline == "forward" and not args.brain_mask:
+    if args.full and world > 1 and default_sizing and not args.no_strong and not deep and args.pipeline == "forward" and not args.brain_mask:
         strong = strong_config3(model, group, lib, h, _lib, syn, shard_range, rank, world, args, device_sync, fence, backend)
 
     px_per_step = n_total * 320 * 320
@@ -590,7 +626,7 @@ def main():
             "rccl_ranks": comm_ranks if backend in ("rccl", "nccl") else None,
             "comm_ranks": comm_ranks,
             "rccl_lib": (os.environ.get("MSIREN_RCCL_LIB") or "system librccl") if backend == "rccl" and world > 1 else None,
-            "ranks_hold_identical_weights": bool(sum_max == sum_min), "probe_checksum": probe_sum,
+            "ranks_hold_identical_weights": identical, "probe_checksum": probe_sum,
             "ranks": ranks_info,
             "warmup_steps_run": warm_steps,
             # which HIP runtime libmsiren's calls ran on in this process (msiren_runtime_info): the system one in a torch-free process,
@@ -639,8 +675,9 @@ def main():
             ref = orc.siren_forward(sd, mods, num_layers=L, activation=args.activation, residual=deep,
                                     dtype=np.float64).reshape(-1, 24, 24)
             result["check_nerr_vs_fp64_oracle"] = float(np.abs(got - ref).max() / np.abs(ref).max())
-        tiles400 = d_tiles.numpy()[:400] if (world == 1 and not args.no_cpu_baseline and not deep) else None
-        if world == 1 and not args.no_extras and not deep and n_sl >= 1:
+        want_cpu = args.full and world == 1 and not args.no_cpu_baseline and not deep
+        tiles400 = d_tiles.numpy()[:400] if want_cpu else None
+        if args.full and world == 1 and not args.no_extras and not deep and n_sl >= 1:
             result["extra"] = extras(model, lib, h, _lib, d_img, d_tiles, d_recons, args.streams)
             # SURVEY.md section 8(d)'s PRIMARY timed region -- the drop-in call, tiles on the host -> (B,24,24) on the host, PCIe included
             # (error.py:233-258) -- where the driver's record keeps it: a top-level key, and inside `config` (kept whole).  Never `value`.
@@ -672,7 +709,7 @@ def main():
                 if "value" in c3:
                     result["config"].setdefault("also_measured", {})["config3_64_slices_n1"] = {"value": c3["value"], "ms_per_step": c3["ms_per_step"]}
                     result["config"]["config3_64_slices_n1_mpixel_s"] = c3["value"]
-        if world == 1 and not args.no_cpu_baseline and not deep:
+        if want_cpu:
             result["cpu_baseline"] = cpu_baseline(sd, tiles400, args.activation, args.cpu_seconds)
         else:
             result["cpu_baseline"] = None
@@ -872,7 +909,9 @@ def other_configs(launch_timeout=90.0, wall_budget=240.0, torch_first=False):
     out = {}
     t_start = time.perf_counter()
     for name, (flags, what) in runs.items():
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-extras"] + flags + (["--torch-first"] if torch_first else [])
+        # (--full for the one-stream roofline phase the summary reads; no CPU baseline, no extras)
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--no-extras"] + flags + \
+            (["--torch-first"] if torch_first else [])
         # a side measurement must not delay the headline line without bound: a child gets at most `launch_timeout` seconds, all of them
         # together `wall_budget` (each takes 10-20 s, mostly `import torch` on a fresh box); what does not fit is reported as skipped
         left = wall_budget - (time.perf_counter() - t_start)

@@ -13,7 +13,7 @@ import pytest
 from conftest import load_golden
 from mri_inr_amd import _lib, synthetic as syn
 from oracle import siren_oracle as orc
-from test_gpu_parity import check, make_model, make_with_env
+from test_gpu_parity import _fresh_pages, check, make_model, make_with_env
 
 pytestmark = pytest.mark.gpu
 
@@ -226,7 +226,8 @@ def test_host_slice_call_in_place_same_bits_as_staged_copies():
     assert np.array_equal(m.reconstruct(odd), ref_odd)
     # the caller page-locks the first slice of a stack and calls on slices 0..1 and 1..2: the first range is page-locked in part
     hip = ctypes.CDLL("libamdhip64.so")
-    stack = imgs.copy()
+    stack = _fresh_pages(imgs.shape)
+    stack[...] = imgs
     assert hip.hipHostRegister(ctypes.c_void_p(stack.ctypes.data), ctypes.c_size_t(320 * 320 * 4), ctypes.c_uint(0)) == 0
     try:
         assert np.array_equal(m.reconstruct(stack[:2]), ref[:2])

@@ -275,7 +275,7 @@ def test_bench_two_ranks_rehearsal_reports_what_the_communicator_saw(tmp_path):
     """bench.py --gpus 2 on the one card through the stub: the line carries the communicator's own rank count, no
     fallback, and the cross-rank check of the replicated weights."""
     stub = _build_rccl_stub(tmp_path)
-    d = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline"],
+    d = _bench(["--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline"],
                {"MSIREN_BENCH_ALLOW_SHARED": "1", "MSIREN_RCCL_LIB": stub, "RCCL_STUB_DIR": str(tmp_path)}, timeout=400)
     assert d["n_gpus"] == 2 and d["collective_fallback"] is False
     assert d["config"]["rccl_ranks"] == 2 and d["config"]["rccl_lib"] == stub
@@ -296,8 +296,8 @@ def test_bench_two_ranks_rehearsal_reports_what_the_communicator_saw(tmp_path):
 
 
 def test_bench_under_torchrun_as_the_driver_starts_it(tmp_path):
-    """The scaling sweep's command line, verbatim: `python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1
-    --master-port P bench.py --gpus 2 --steps K --warmup W` -- two ranks on the one card through the stub RCCL.  Under torchrun the
+    """The scaling sweep's command line with --full: `python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1
+    --master-port P bench.py --gpus 2 --steps K --warmup W --full` -- two ranks on the one card through the stub RCCL.  Under torchrun the
     unique id travels through the agent's TCP store (TORCHELASTIC_USE_AGENT_STORE; mri_inr_amd/launch.py), i.e. torch is imported in the
     rank AFTER libmsiren has brought the system HIP runtime up: the line must say so (torch-free runtime, rccl backend, no fallback) and
     carry both regions."""
@@ -307,7 +307,7 @@ def test_bench_under_torchrun_as_the_driver_starts_it(tmp_path):
     e = {k: v for k, v in os.environ.items() if k not in launch.ENV_KEYS}
     e.update({"MSIREN_BENCH_ALLOW_SHARED": "1", "MSIREN_RCCL_LIB": stub, "RCCL_STUB_DIR": str(tmp_path)})
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2"]
+           "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -332,7 +332,7 @@ def _bench(args, env=None, timeout=900):
 
 
 def test_bench_single_gpu_line_carries_roofline_cpu_baseline_and_extras():
-    d = _bench(["--steps", "20", "--warmup", "5", "--cpu-seconds", "2"])
+    d = _bench(["--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "2"])
     assert d["n_gpus"] == 1 and d["steps"] == 20 and d["warmup"] == 5 and d["scaling"] == "weak"
     assert d["metric"] == "Mpixels/sec reconstructed (320x320 slice, hidden=256, 5 layers)"
     assert "configs[1]" in d["config"]["workload"] and d["config"]["warmup_steps_run"] >= 5
@@ -382,7 +382,7 @@ def test_bench_gpus2_starts_its_own_ranks_gloo_rehearsal_on_one_card():
     """`python bench.py --gpus 2` with no launcher: two ranks, n_gpus 2 in the line (weak: one slice per rank;
     strong: a fixed batch of 6 slices split 3 + 3)."""
     env = {"MSIREN_BENCH_BACKEND": "gloo"}
-    d = _bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--no-cpu-baseline"], env)
+    d = _bench(["--gpus", "2", "--steps", "10", "--warmup", "3", "--full", "--no-cpu-baseline"], env)
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["config"]["slices_per_step_total"] == 2
     assert abs(d["value"] - 2 * 320 * 320 / d["ms_per_step"] / 1e3) < 1e-6 * d["value"]
     assert d["extra"]["configs"]["config3_64_slices_strong"]["slices_per_rank"] == [32, 32]      # the strong region rides along
@@ -422,3 +422,26 @@ def test_bench_strong_scaling_config3_single_gpu():
     d = _bench(["--total-slices", "64", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-extras"])
     assert d["scaling"] == "strong" and d["n_gpus"] == 1 and d["config"]["patches_per_step_rank0"] == 25600
     assert "configs[2]" in d["config"]["workload"]
+
+
+def test_bench_plain_line_is_lean_and_dumps_what_the_last_timed_step_computed(tmp_path):
+    """Without --full the line carries the timed region only (none of the measurements behind it), --steps is the number of timed
+    launches, and --dump-outputs writes the last timed step's (400,24,24) outputs: the same bits on every run with the same arguments,
+    and the fp64 oracle's values on the seeded slice the benchmark tiles."""
+    from mri_inr_amd import synthetic as syn
+    from oracle import siren_oracle as orc
+
+    d = _bench(["--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path / "a")])
+    assert d["steps"] == 7 and abs(d["value"] - 320 * 320 / d["ms_per_step"] / 1e3) < 1e-6 * d["value"]
+    assert d["roofline"]["launches"] == 7 and d["roofline"]["sustained_fp16_mfma_tflops_measured"] is None
+    for k in ("extra", "host_to_host", "fp32", "roofline_kernel_alone"):
+        assert k not in d, k
+    assert d["cpu_baseline"] is None and d["config"]["probe_checksum"] is None
+    out = np.load(tmp_path / "a" / "forward_tiles.npy")
+    assert out.shape == (400, 24, 24) and out.dtype == np.float32 and np.isfinite(out).all()
+    _bench(["--steps", "3", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")])
+    assert np.array_equal(np.load(tmp_path / "b" / "forward_tiles.npy"), out)
+    tiles, _ = orc.image_to_patches(syn.make_slice(0), 32, 16)
+    sd = syn.make_state_dict(seed=7, trained_like=True)
+    ref = orc.modulated_siren_forward(sd, tiles[:64], num_layers=5, dtype=np.float64)
+    assert np.abs(out[:64] - ref).max() / np.abs(ref).max() < 1e-4

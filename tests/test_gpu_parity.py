@@ -886,6 +886,16 @@ def test_two_threads_share_one_pageable_input_array():
     assert _range_kind(models[0], shared) == 0          # still ordinary pageable memory: nothing of the caller's was page-locked
 
 
+def _fresh_pages(shape):
+    """A float32 array for a caller-side hipHostRegister, on pages of a private anonymous mapping of its own: never heap pages that an
+    earlier array (and the HIP runtime's pins for its pageable copies of it) held -- registering such reused heap pages is what the GPU
+    memory faults of round 5 were consistent with (profiles/r6/01_*).  The mapping lives as long as the array."""
+    import mmap
+
+    buf = mmap.mmap(-1, int(np.prod(shape)) * 4, flags=mmap.MAP_PRIVATE)
+    return np.frombuffer(buf, dtype=np.float32).reshape(shape)
+
+
 def _range_kind(m, a):
     """msiren_host_range_kind of a numpy array's bytes: 0 pageable, 1 inside one page-locked allocation, 2 page-locked in part."""
     import ctypes
@@ -957,9 +967,10 @@ def test_buffers_page_locked_in_part_go_through_a_bounce_buffer():
     hip = ctypes.CDLL("libamdhip64.so")
     sd = syn.make_state_dict(seed=7, trained_like=True)
     m = make_model(sd, precision="f16x3")
-    x = np.random.default_rng(79).random((700, 32, 32), dtype=np.float32)
+    x = _fresh_pages((700, 32, 32))
+    x[...] = np.random.default_rng(79).random((700, 32, 32), dtype=np.float32)
     ref = m(x.copy())
-    out = np.zeros((700, 24, 24), np.float32)
+    out = _fresh_pages((700, 24, 24))
     assert hip.hipHostRegister(ctypes.c_void_p(x.ctypes.data), ctypes.c_size_t(300 * 32 * 32 * 4), ctypes.c_uint(0)) == 0
     assert hip.hipHostRegister(ctypes.c_void_p(out.ctypes.data), ctypes.c_size_t(300 * 24 * 24 * 4), ctypes.c_uint(0)) == 0
     try:
@@ -993,6 +1004,10 @@ def test_buffers_page_locked_in_part_go_through_a_bounce_buffer():
     _forward_into(m, x[200:600], out[200:600])
     assert np.array_equal(out[200:600], ref[200:600])
     # two registrations with pageable rows between them: rows [0, 100) and [200, 300) page-locked, the call on rows [50, 250)
+    # (of a fresh copy: x's pages have just been copied from as pageable memory)
+    fresh = _fresh_pages(x.shape)
+    fresh[...] = x
+    x = fresh
     row = 32 * 32 * 4
     for lo in (0, 200):
         assert hip.hipHostRegister(ctypes.c_void_p(x.ctypes.data + lo * row), ctypes.c_size_t(100 * row), ctypes.c_uint(0)) == 0

@@ -219,6 +219,22 @@ def test_committed_bench_line_follows_the_contract():
         assert abs(s["value"] - 64 * 320 * 320 / (s["ms_per_step"] * 1e-3) / 1e6) < 1e-6 * s["value"]
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_fixed_rows_above_the_limit(tmp_path):
+    """bench.py --dump-outputs: the whole array as float32 while it fits, else the same seeded rows on every call (in order)."""
+    import bench
+
+    x = np.arange(100 * 4 * 4, dtype=np.float64).reshape(100, 4, 4)
+    bench.dump_outputs(str(tmp_path / "all"), "x", x, 1 << 20)
+    got = np.load(tmp_path / "all" / "x.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), "x", x, 30 * 64 + 63)
+    a, b = np.load(tmp_path / "s1" / "x.npy"), np.load(tmp_path / "s2" / "x.npy")
+    assert a.shape == (30, 4, 4) and a.nbytes <= 30 * 64 + 63 and np.array_equal(a, b)
+    rows = (a[:, 0, 0] // 16).astype(int)
+    assert (np.diff(rows) > 0).all() and np.array_equal(a, x[rows])
+
+
 def test_metric_plots_have_the_references_names_and_the_density_is_seaborns_default_kde(tmp_path):
     """test_mod_siren.py:248-256 of the reference: one box plot and one density plot per metric, named ``{key}_metrics_boxplot.png`` /
     ``{key}_density_plot.png`` (src/util/visualization.py:145, :164).  The density restates seaborn's ``kdeplot`` defaults (seaborn is
