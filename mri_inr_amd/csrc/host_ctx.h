@@ -5,6 +5,7 @@
 //     host_buffers.hip     what a caller's host range is (pageable / page-locked / page-locked in part), bounce buffers
 //     comm_rccl.hip        RCCL through dlopen: communicator, the one weight broadcast, barrier / MAX
 //     diagnostics.hip      stamped timeline builds, the sustained-MFMA probe
+//     scores.hip           PSNR / SSIM / NRMSE of image pairs (the evaluation harness's metrics; kernels: scores.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +51,7 @@ struct msiren_ctx {
     struct StreamCtx {
         hipStream_t s = nullptr;
         mh::DevBuf mods, modpad, latent, patches, keep, rec, queue, feat, plan;
+        mh::DevBuf score;     // partials of msiren_score_images(_dev) (scores.hip.h)
         mh::DevBuf cscratch;  // split-fp16 Modulator: the latent part of layers 1.., lane-private (encoder_modulator_f16x3.hip.h)
         hipEvent_t ev_join = nullptr;  // a host call that pipelines itself: this stream's chunk has been enqueued
         msiren::PassQueue pq;  // host view of the never-reset pass counter (pass_queue.h)
