@@ -11,6 +11,12 @@
 #include "trunk_instances.h"
 #include "launch_dispatch.h"
 
+namespace msiren {  // (compiled in k_f32.hip, k_f16x3n.hip, k_f16x3w.hip)
+MSIREN_F32_INSTANCES(MSIREN_EXTERN_TRUNK)
+MSIREN_F16X3N_INSTANCES(MSIREN_EXTERN_TRUNK)
+MSIREN_F16X3W_INSTANCES(MSIREN_EXTERN_TRUNK)
+}  // namespace msiren
+
 using namespace mh;
 
 extern "C" {
@@ -26,7 +32,7 @@ int msiren_trunk_timeline(msiren_handle h, const float* mods_dev, int64_t B, flo
     DevBuf st;
     if ((rc = ensure(h, st, (size_t)grid * 32 * sizeof(uint64_t)))) return rc;
     HIPCHK(hipMemsetAsync(st.p, 0, (size_t)grid * 32 * sizeof(uint64_t), h->sc[h->cur].s));
-    msiren::TrunkParams p = make_trunk_params(h, mods_dev, h->H, B, out_dev);
+    msiren::TrunkParams p = make_trunk_params(h, nullptr, mods_dev, h->H, B, out_dev);
     p.stamps = (unsigned long long*)st.p;
     hipLaunchKernelGGL((msiren::siren_trunk_f32_kernel<256, 0, 0, 1>), dim3(grid), dim3(256), 256 * 256 + 256 * 16, h->sc[h->cur].s, p);
     HIPCHK(hipGetLastError());

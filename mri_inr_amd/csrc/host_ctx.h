@@ -1,6 +1,8 @@
 // Shared by the host translation units of libmsiren.so (round 6: the former 3 000-line msiren.hip, cut by responsibility):
 //     msiren.hip           C ABI: lifecycle, weights, the forward / slice entry points on host pointers, memory, timing, info
-//     launch_dispatch.hip  which kernel runs for which shape, and its launch: trunks, prologue, tiling / fold, the *_dev slice pipeline
+//     dispatch.h           which kernel runs for which model and call: pure functions, no HIP (tests/test_dispatch.py)
+//     launch_dispatch.hip  the launches of what dispatch.h picks: trunks, prologue, tiling / fold, the *_dev slice pipeline
+//     trunk_instances.h    the one list of kernel instances: k_*.hip instantiate it, the host units declare it extern
 //     weights_pack.hip     state_dict -> the kernels' weight layouts (host arithmetic + uploads)
 //     host_buffers.hip     what a caller's host range is (pageable / page-locked / page-locked in part), bounce buffers
 //     comm_rccl.hip        RCCL through dlopen: communicator, the one weight broadcast, barrier / MAX
@@ -16,6 +18,7 @@
 #include <vector>
 
 #include "../../include/msiren.h"
+#include "dispatch.h"
 #include "encoder_params.h"
 #include "pass_queue.h"
 
@@ -56,17 +59,10 @@ struct msiren_ctx {
         hipEvent_t ev_join = nullptr;  // a host call that pipelines itself: this stream's chunk has been enqueued
         msiren::PassQueue pq;  // host view of the never-reset pass counter (pass_queue.h)
     } sc[3];
-    int cur = 0, nstreams = 1;
-    bool solo = false;     // a synchronous host-pointer call is running on ONE stream: nothing of this handle is to run beside its trunk
-    // which split-fp16 trunk a launch takes: 0 = launch_trunk_f16x3's own rule; 1 = register-resident with room beside it
-    // (ring of 3); 2 = weight-stationary.  Set per chunk by a host call that pipelines itself (host_plan.h).
-    int trunk_force = 0;
-    hipEvent_t trunk_after = nullptr;  // the next trunk launch waits for this event first (a pipelined host call: the weight-stationary
-                                       // trunk of the last chunk behind the other stream's conditional launch, which cannot run beside it)
-    bool em_beside = false;  // the prologue being launched runs beside a trunk of this call (a pipelined host call's chunks): shallow weight ring
-    static constexpr int lin_tile_min = 1024;  // rows from which the exact-fp32 Linear layers use the 32 x 32-tile kernel (a quarter of it for >= 512 outputs)
-    char last_trunk[96] = "";  // name of the trunk instance launched last (msiren_last_trunk_kernel)
-    const int* plan = nullptr;  // device-side list of non-black patches in effect (slice pipeline only)
+    int cur = 0, nstreams = 1;  // cur: the stream the next asynchronous (*_dev) call takes (next_stream rotates it)
+    msiren::DispatchHandle dh;  // what dispatch.h reads of this handle: the knobs from msiren_create, the rest from msiren_commit_weights
+    const char* last_trunk = "";  // name of the trunk instance launched last (msiren_last_trunk_kernel; msiren::kInstances)
+    struct { const void* k = nullptr; int bytes = 0; } lds_set[8];  // the dynamic-LDS limit raised per kernel (launch_dispatch.hip: launch)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::map<std::string, std::vector<float>> tensors;  // state_dict, host copies
     std::map<std::string, size_t> expected;             // key -> element count
@@ -77,39 +73,25 @@ struct msiren_ctx {
     float bout = 0.f, cg0 = 0.f, cg = 0.f;
     // split-fp16 trunk (MSIREN_PREC_F16X3)
     void* d_wp16n = nullptr;  // weight stream of the 16x16x32 kernel (default)
-    int lds_attr_f16n[2][4] = {};
-    int lds_attr_f16h[2][2] = {};  // half-unit instances (num_layers = 5 only)
-    int lds_attr_f16w[2] = {};     // weight-stationary instances ([activation])
-    int lds_attr_f32[4] = {}, lds_attr_x1 = 0;  // exact-fp32 trunk ([activation][residual]) / single-product 16-bit trunk
     // f16x3 domain guard: a word in host memory the trunk kernels set when a scaled modulation does not fit fp16
     volatile int* status_host = nullptr;
     int* status_dev = nullptr;
     unsigned range_epoch = 0;      // number of the split-fp16 trunk launch in flight (what it writes to its stream's flag word)
-    // Synchronous one-chunk msiren_forward_tiles calls (round 5): the host is going to wait for the stream anyway, so the trunk raises its flag in
-    // HOST memory (status_host[8]) and the call looks at it after the wait -- no conditional launch (4.4 us of kernel + a launch gap per call);
-    // a flagged call enqueues the exact-fp32 trunk then and waits once more (profiles/r5/12_*).  Asynchronous calls keep the conditional launch.
-    bool host_check_now = false;   // set by the call for the launch_trunk it reaches
-    struct { const float* mods = nullptr; int64_t B = 0; float* out = nullptr; unsigned epoch = 0; bool armed = false; } hc;
     int64_t range_events = 0;      // synchronisations that found the conditional exact-fp32 trunk had run, since create
     float* d_dump = nullptr;       // 256 floats: where lanes of the weight-stationary trunk that have nothing to store write
     int trace_host = 0;            // MSIREN_TRACE_HOST=1: msiren_forward_tiles prints the host-side timeline of the call (stderr)
-    int f16_ws = 1;                // the weight-stationary trunk runs single-stream launches (MSIREN_F16_WS=0: never; tests, A/B)
     float *d_bias16 = nullptr, *d_wout16 = nullptr, *d_s0t = nullptr;
     float mscale16[16] = {0};  // 16x16 kernel: factor of each layer's modulation row (the NEXT layer's weight scale, inverted)
     bool f16x3_ready = false;
     // single-product 16-bit trunk (MSIREN_PREC_BF16 / MSIREN_PREC_F16), H = 512
     void *d_woutx1 = nullptr, *d_wpx1n = nullptr;  // last_layer.weight (fp16); weight stream of siren_trunk_x1n.hip.h
     void* d_wpx1w = nullptr;       // weight stream of siren_trunk_x1w.hip.h (weight-stationary: 64 KB per layer, N-pass and wave)
-    int lds_attr_x1w = 0;
-
     float* d_bias32x1 = nullptr;   // bias rows: fp32, in revolutions x the layer's weight scale
     float* d_s0t512 = nullptr;
     float winvx1[64] = {0};
     bool x1_ready = false;
     int num_cus = 256;
-    // environment knobs (the whole list): read ONCE, at msiren_create -- not on the launch path
-    int half_allowed = 1;      // MSIREN_F16_HALF=0: never use the half-unit instance (tests: instance selection)
-    int host_pipe_min = 2400;  // MSIREN_HOST_PIPE_MIN: tiles from which a host call cuts itself into chunks (below: one chunk, buffers in place; profiles/r5/04_*)
+    // environment knobs (the whole list): read ONCE, at msiren_create -- not on the launch path (dispatch's: dh)
     static constexpr int host_first = 112, host_piece = 400;  // tiles in the first / the further chunks of a pipelined host call (host_plan.h)
     unsigned queue_start = 0;  // MSIREN_QUEUE_START: initial value of the never-reset pass counters (tests: wrap-around)
     // modulator: transposed weights so that consecutive threads read consecutive outputs
@@ -124,7 +106,6 @@ struct msiren_ctx {
     float em_winv_c3 = 1.f, em_winv_fc = 1.f, em_winv_z[64] = {0}, em_winv_h[64] = {0};
     int em_wave_stride = 0, em_zp_start = 0;
     bool em_enc = false, em_mod = false;  // which halves of the stream are packed (the checkpoint's key set decides)
-    int em_depth = 0;              // MSIREN_EM_DEPTH=2|4|8: force the weight-ring depth of the split-fp16 prologue (tests: same bits at every depth)
     int em_enabled = 1;            // MSIREN_PROLOGUE_F16X3=0: the exact-fp32 launches per layer on a split-fp16 handle (tests, A/B)
     float* d_foldw = nullptr;  // (S,S) overlap-add weights
     // workspaces
@@ -146,6 +127,26 @@ struct msiren_ctx {
 
 namespace mh {
 
+// One call's launch state, passed by reference from the entry point down through the launchers: nothing of it lives on the handle.
+// Synchronous one-chunk msiren_forward_tiles calls (round 5): the host is going to wait for the stream anyway, so the trunk raises its
+// flag in HOST memory (status_host[8]) and the call looks at it after the wait -- no conditional launch (4.4 us of kernel + a launch
+// gap per call); a flagged call enqueues the exact-fp32 trunk then and waits once more (profiles/r5/12_*).
+struct HostCheck { const float* mods = nullptr; int64_t B = 0; float* out = nullptr; unsigned epoch = 0; bool armed = false; };
+struct Call {
+    int stream = 0;                    // h->sc[stream]
+    msiren::CallMode mode;             // what dispatch.h reads of the call
+    const int* plan = nullptr;         // device-side list of kept patches (slice pipeline; mode.plan)
+    hipEvent_t trunk_wait = nullptr;  // the trunk waits for this event first (a pipelined host call's weight-stationary last chunk)
+    HostCheck* hc = nullptr;           // mode.host_check: where the trunk launch leaves what the host check needs
+};
+inline Call make_call(const msiren_ctx* h, bool sync) {
+    Call c;
+    c.stream = h->cur;
+    c.mode.nstreams = h->nstreams;
+    c.mode.sync = sync;
+    return c;
+}
+
 // msiren.hip
 int use_device(msiren_ctx* h);
 int ensure(msiren_ctx* h, DevBuf& b, size_t bytes);                 // grow-only device workspace
@@ -154,6 +155,7 @@ int check(msiren_ctx* h, bool need_commit = true);
 int sync_all(msiren_ctx* h);
 bool take_range_flag(msiren_ctx* h);
 void next_stream(msiren_ctx* h);   // asynchronous forward entry points rotate over the configured streams
+Call dev_call(msiren_ctx* h);      // next_stream, then the call of an asynchronous entry point
 
 // weights_pack.hip: state_dict -> kernel layouts.  pack_modulator / pack_encoder return 1 when their keys are absent.
 void declare_expected(msiren_ctx* h);
@@ -165,17 +167,15 @@ int pack_encoder(msiren_ctx* h);
 int pack_prologue_f16x3(msiren_ctx* h);
 int pack_fold_weights(msiren_ctx* h);
 
-// launch_dispatch.hip: everything below enqueues on h->sc[h->cur].s
-bool use_f16x3(msiren_ctx* h);
-bool ws_capable(msiren_ctx* h, int64_t B);
-int ensure_queue(msiren_ctx* h);
-int launch_trunk(msiren_ctx* h, const float* mods_dev, int64_t B, float* out_dev);
-int launch_trunk_f32_cond(msiren_ctx* h, const float* mods_dev, int64_t B, float* out_dev, const int* flag_word = nullptr, unsigned flag_val = 0);
-int launch_modulator(msiren_ctx* h, const float* z_dev, int64_t B, float* mods_dev);
-int launch_encoder(msiren_ctx* h, const float* tiles_dev, int64_t B, float* z_dev);
-int forward_latent_dev(msiren_ctx* h, const float* z_dev, int64_t B, float* out_dev, float* mods_out_dev);
-int forward_tiles_dev(msiren_ctx* h, const float* tiles_dev, int64_t B, float* out_dev);
-int reconstruct_on_current_stream(msiren_ctx* h, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev);
+// launch_dispatch.hip: everything below enqueues on h->sc[c.stream].s
+void describe_for_dispatch(msiren_ctx* h);  // h->dh from the committed weights (msiren_commit_weights)
+int launch_trunk(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev);
+int launch_trunk_f32_cond(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev, const int* flag_word = nullptr, unsigned flag_val = 0);
+int launch_modulator(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* mods_dev);
+int launch_encoder(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev);
+int forward_latent_dev(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* out_dev, float* mods_out_dev);
+int forward_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* out_dev);
+int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev);
 
 // comm_rccl.hip
 int comm_destroy(msiren_ctx* h);

@@ -1,13 +1,6 @@
-// Device code of the siren_trunk_f16x3n.hip.h instances libmsiren launches (declared extern in trunk_instances.h).
+// Device code of the siren_trunk_f16x3n.hip.h instances libmsiren launches (the list: trunk_instances.h).
 #include "siren_trunk_f16x3n.hip.h"
+#include "trunk_instances.h"
 namespace msiren {
-template __global__ void siren_trunk_f16x3n_kernel<0, 3, 5>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<0, 3, 0>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<0, 4, 5>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<0, 4, 0>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<1, 3, 5>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<1, 3, 0>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<1, 4, 5>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<1, 4, 0>(TrunkF16Params);
-template __global__ void siren_trunk_f16x3n_kernel<0, 4, 5, 1>(TrunkF16Params);
+MSIREN_F16X3N_INSTANCES(MSIREN_DEFINE_TRUNK)
 }  // namespace msiren

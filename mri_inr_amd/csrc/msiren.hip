@@ -71,9 +71,8 @@ int sync_all(msiren_ctx* h) {
     return 0;
 }
 
-template <typename F>
-int with_range_fallback(msiren_ctx* h, F&& run) {
-    const int rc = run();
+// behind a synchronous host call: the domain flag in host memory is informational (the outputs are the exact-fp32 trunk's already)
+static int take_range_flag_after(msiren_ctx* h, int rc) {
     (void)take_range_flag(h);
     return rc;
 }
@@ -81,6 +80,11 @@ int with_range_fallback(msiren_ctx* h, F&& run) {
 // asynchronous forward entry points rotate over the configured streams
 void next_stream(msiren_ctx* h) {
     if (h->nstreams > 1) h->cur = (h->cur + 1) % h->nstreams;
+}
+
+Call dev_call(msiren_ctx* h) {
+    next_stream(h);
+    return make_call(h, false);
 }
 
 // event pairs recorded since the last collection -> totals (the streams have been synchronised by the caller)
@@ -161,13 +165,13 @@ int msiren_create(const msiren_config* cfg, msiren_handle* out) {
     h->O = cfg->outer_patch_size;
     h->I = cfg->inner_patch_size;
     h->num_cus = prop.multiProcessorCount;
-    if (const char* e = std::getenv("MSIREN_F16_HALF")) h->half_allowed = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MSIREN_HOST_PIPE_MIN")) h->host_pipe_min = std::max(128, std::atoi(e));
+    if (const char* e = std::getenv("MSIREN_F16_HALF")) h->dh.half_allowed = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MSIREN_HOST_PIPE_MIN")) h->dh.host_pipe_min = std::max(128, std::atoi(e));
     if (const char* e = std::getenv("MSIREN_QUEUE_START")) h->queue_start = (unsigned)std::strtoul(e, nullptr, 0);
-    if (const char* e = std::getenv("MSIREN_F16_WS")) h->f16_ws = std::atoi(e) != 0;
+    if (const char* e = std::getenv("MSIREN_F16_WS")) h->dh.f16_ws = std::atoi(e) != 0;
     if (const char* e = std::getenv("MSIREN_TRACE_HOST")) h->trace_host = std::atoi(e);
     if (const char* e = std::getenv("MSIREN_PROLOGUE_F16X3")) h->em_enabled = std::atoi(e) != 0;
-    if (const char* e = std::getenv("MSIREN_EM_DEPTH")) h->em_depth = std::atoi(e);
+    if (const char* e = std::getenv("MSIREN_EM_DEPTH")) h->dh.em_depth = std::atoi(e);
     declare_expected(h);
     hipError_t e = hipSetDevice(cfg->device);
     for (auto& c : h->sc)
@@ -260,6 +264,7 @@ int msiren_commit_weights(msiren_handle h) {
     if (rc < 0) return rc;
     h->have_encoder = (rc == 0);
     if ((rc = pack_prologue_f16x3(h))) return rc;
+    describe_for_dispatch(h);
     h->committed = true;
     return 0;
 }
@@ -267,36 +272,29 @@ int msiren_commit_weights(msiren_handle h) {
 int msiren_forward_mods_dev(msiren_handle h, const float* mods_dev, int64_t B, float* out_dev) {
     int rc = check(h);
     if (rc) return rc;
-    next_stream(h);
+    const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!mods_dev || !out_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    return launch_trunk(h, mods_dev, B, out_dev);
+    return launch_trunk(h, c, mods_dev, B, out_dev);
 }
-
-namespace {
-struct SoloCall {  // marks a synchronous single-stream host call for its duration (trunk choice: use_f16x3w, ring depth)
-    msiren_ctx* h;
-    explicit SoloCall(msiren_ctx* hh, bool on = true) : h(hh) { if (h) h->solo = on; }
-    ~SoloCall() { if (h) h->solo = false; }
-};
-}  // namespace
 
 static int msiren_forward_mods_impl(msiren_handle h, const float* mods_host, int64_t B, float* out_host) {
     int rc = check(h);
     if (rc) return rc;
-    SoloCall solo(h);
     if (B < 0 || (B > 0 && (!mods_host || !out_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
     if (B == 0) return 0;
+    const Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
     const size_t nm = (size_t)h->L * B * h->H * sizeof(float), no = (size_t)B * h->P * sizeof(float);
-    if ((rc = ensure(h, h->sc[h->cur].mods, nm)) || (rc = ensure(h, h->ws_out, no))) return rc;
+    if ((rc = ensure(h, sc.mods, nm)) || (rc = ensure(h, h->ws_out, no))) return rc;
     const HostSrc src(mods_host, nm);
     const HostDst dst(out_host, no);
     HOSTBUF_OK(src);
     HOSTBUF_OK(dst);
     DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(h->sc[h->cur].mods.p, src.as<float>(), nm, hipMemcpyHostToDevice, h->sc[h->cur].s));
-    if ((rc = launch_trunk(h, (const float*)h->sc[h->cur].mods.p, B, (float*)h->ws_out.p))) return rc;
-    HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, h->sc[h->cur].s));
-    HIPCHK(hipStreamSynchronize(h->sc[h->cur].s));
+    HIPCHK(hipMemcpyAsync(sc.mods.p, src.as<float>(), nm, hipMemcpyHostToDevice, sc.s));
+    if ((rc = launch_trunk(h, c, (const float*)sc.mods.p, B, (float*)h->ws_out.p))) return rc;
+    HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
+    HIPCHK(hipStreamSynchronize(sc.s));
     drain.disarm();
     dst.finish();
     return 0;
@@ -304,37 +302,38 @@ static int msiren_forward_mods_impl(msiren_handle h, const float* mods_host, int
 
 int msiren_forward_mods(msiren_handle h, const float* mods_host, int64_t B, float* out_host) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");
-    return with_range_fallback(h, [&] { return msiren_forward_mods_impl(h, mods_host, B, out_host); });
+    return take_range_flag_after(h, msiren_forward_mods_impl(h, mods_host, B, out_host));
 }
 
 int msiren_forward_latent_dev(msiren_handle h, const float* z_dev, int64_t B, float* out_dev, float* mods_out_dev) {
     int rc = check(h);
     if (rc) return rc;
-    next_stream(h);
+    const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!z_dev || !out_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    return forward_latent_dev(h, z_dev, B, out_dev, mods_out_dev);
+    return forward_latent_dev(h, c, z_dev, B, out_dev, mods_out_dev);
 }
 
 static int msiren_forward_latent_impl(msiren_handle h, const float* z_host, int64_t B, float* out_host, float* mods_out_host) {
     int rc = check(h);
     if (rc) return rc;
-    SoloCall solo(h);
     if (B < 0 || (B > 0 && (!z_host || !out_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
     if (B == 0) return 0;
+    const Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
     const size_t nz = (size_t)B * h->Z * sizeof(float), no = (size_t)B * h->P * sizeof(float);
     const size_t nm = (size_t)h->L * B * h->H * sizeof(float);
-    if ((rc = ensure(h, h->sc[h->cur].latent, nz)) || (rc = ensure(h, h->ws_out, no)) || (rc = ensure(h, h->sc[h->cur].mods, nm))) return rc;
+    if ((rc = ensure(h, sc.latent, nz)) || (rc = ensure(h, h->ws_out, no)) || (rc = ensure(h, sc.mods, nm))) return rc;
     const HostSrc src(z_host, nz);
     const HostDst dst(out_host, no), dst_mods(mods_out_host, nm);
     HOSTBUF_OK(src);
     HOSTBUF_OK(dst);
     HOSTBUF_OK(dst_mods);
     DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(h->sc[h->cur].latent.p, src.as<float>(), nz, hipMemcpyHostToDevice, h->sc[h->cur].s));
-    if ((rc = forward_latent_dev(h, (const float*)h->sc[h->cur].latent.p, B, (float*)h->ws_out.p, (float*)h->sc[h->cur].mods.p))) return rc;
-    HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, h->sc[h->cur].s));
-    if (mods_out_host) HIPCHK(hipMemcpyAsync(dst_mods.as<float>(), h->sc[h->cur].mods.p, nm, hipMemcpyDeviceToHost, h->sc[h->cur].s));
-    HIPCHK(hipStreamSynchronize(h->sc[h->cur].s));
+    HIPCHK(hipMemcpyAsync(sc.latent.p, src.as<float>(), nz, hipMemcpyHostToDevice, sc.s));
+    if ((rc = forward_latent_dev(h, c, (const float*)sc.latent.p, B, (float*)h->ws_out.p, (float*)sc.mods.p))) return rc;
+    HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
+    if (mods_out_host) HIPCHK(hipMemcpyAsync(dst_mods.as<float>(), sc.mods.p, nm, hipMemcpyDeviceToHost, sc.s));
+    HIPCHK(hipStreamSynchronize(sc.s));
     drain.disarm();
     dst.finish();
     dst_mods.finish();
@@ -343,25 +342,25 @@ static int msiren_forward_latent_impl(msiren_handle h, const float* z_host, int6
 
 int msiren_forward_latent(msiren_handle h, const float* z_host, int64_t B, float* out_host, float* mods_out_host) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");
-    return with_range_fallback(h, [&] { return msiren_forward_latent_impl(h, z_host, B, out_host, mods_out_host); });
+    return take_range_flag_after(h, msiren_forward_latent_impl(h, z_host, B, out_host, mods_out_host));
 }
 
 // ---- the two producers alone: model.encoder(tiles) and model.modulator(z) of the reference (modulated_siren.py:420, 416) ----
 int msiren_encode_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, float* z_dev) {
     int rc = check(h);
     if (rc) return rc;
-    next_stream(h);
+    const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!tiles_dev || !z_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
     if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
-    return launch_encoder(h, tiles_dev, B, z_dev);
+    return launch_encoder(h, c, tiles_dev, B, z_dev);
 }
 
 int msiren_modulate_dev(msiren_handle h, const float* z_dev, int64_t B, float* mods_dev) {
     int rc = check(h);
     if (rc) return rc;
-    next_stream(h);
+    const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!z_dev || !mods_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    return launch_modulator(h, z_dev, B, mods_dev);
+    return launch_modulator(h, c, z_dev, B, mods_dev);
 }
 
 int msiren_encode_tiles(msiren_handle h, const float* tiles_host, int64_t B, float* z_host) {
@@ -371,7 +370,8 @@ int msiren_encode_tiles(msiren_handle h, const float* tiles_host, int64_t B, flo
     if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
     if (B == 0) return 0;
     const size_t nt = (size_t)B * h->O * h->O * sizeof(float), nz = (size_t)B * h->Z * sizeof(float);
-    auto& c = h->sc[h->cur];
+    const Call call = make_call(h, false);  // (the prologue's MODE 1 / 2 instances have one ring depth, no prefetch: nothing to tell)
+    auto& c = h->sc[call.stream];
     if ((rc = ensure(h, h->ws_tiles, nt)) || (rc = ensure(h, c.latent, nz))) return rc;
     const HostSrc src(tiles_host, nt);
     const HostDst dst(z_host, nz);
@@ -379,7 +379,7 @@ int msiren_encode_tiles(msiren_handle h, const float* tiles_host, int64_t B, flo
     HOSTBUF_OK(dst);
     DrainOnExit drain(h);
     HIPCHK(hipMemcpyAsync(h->ws_tiles.p, src.as<float>(), nt, hipMemcpyHostToDevice, c.s));
-    if ((rc = launch_encoder(h, (const float*)h->ws_tiles.p, B, (float*)c.latent.p))) return rc;
+    if ((rc = launch_encoder(h, call, (const float*)h->ws_tiles.p, B, (float*)c.latent.p))) return rc;
     HIPCHK(hipMemcpyAsync(dst.as<float>(), c.latent.p, nz, hipMemcpyDeviceToHost, c.s));
     HIPCHK(hipStreamSynchronize(c.s));
     drain.disarm();
@@ -393,7 +393,8 @@ int msiren_modulate(msiren_handle h, const float* z_host, int64_t B, float* mods
     if (B < 0 || (B > 0 && (!z_host || !mods_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
     if (B == 0) return 0;
     const size_t nz = (size_t)B * h->Z * sizeof(float), nm = (size_t)h->L * B * h->H * sizeof(float);
-    auto& c = h->sc[h->cur];
+    const Call call = make_call(h, false);  // (as msiren_encode_tiles)
+    auto& c = h->sc[call.stream];
     if ((rc = ensure(h, c.latent, nz)) || (rc = ensure(h, c.mods, nm))) return rc;
     const HostSrc src(z_host, nz);
     const HostDst dst(mods_host, nm);
@@ -401,7 +402,7 @@ int msiren_modulate(msiren_handle h, const float* z_host, int64_t B, float* mods
     HOSTBUF_OK(dst);
     DrainOnExit drain(h);
     HIPCHK(hipMemcpyAsync(c.latent.p, src.as<float>(), nz, hipMemcpyHostToDevice, c.s));
-    if ((rc = launch_modulator(h, (const float*)c.latent.p, B, (float*)c.mods.p))) return rc;
+    if ((rc = launch_modulator(h, call, (const float*)c.latent.p, B, (float*)c.mods.p))) return rc;
     HIPCHK(hipMemcpyAsync(dst.as<float>(), c.mods.p, nm, hipMemcpyDeviceToHost, c.s));
     HIPCHK(hipStreamSynchronize(c.s));
     drain.disarm();
@@ -412,10 +413,10 @@ int msiren_modulate(msiren_handle h, const float* z_host, int64_t B, float* mods
 int msiren_forward_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, float* out_dev) {
     int rc = check(h);
     if (rc) return rc;
-    next_stream(h);
+    const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!tiles_dev || !out_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
     if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
-    return forward_tiles_dev(h, tiles_dev, B, out_dev);
+    return forward_tiles_dev(h, c, tiles_dev, B, out_dev);
 }
 
 static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, int64_t B, float* out_host) {
@@ -441,7 +442,7 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
     using Chunk = msiren::HostChunk;
     std::vector<Chunk> plan;
     const int cur0 = h->cur;
-    const bool pipelined = B >= h->host_pipe_min && use_f16x3(h) && !h->x1_ready && h->L == 5 && h->em_enc && h->em_mod && ws_capable(h, B);
+    const bool pipelined = msiren::host_call_pipelines(h->dh, B);
     if (pipelined) plan = msiren::pipelined_host_plan(B, h->host_first, h->host_piece, cur0);  // (host_plan.h: unit-tested on the CPU)
     else plan.push_back({0, B, cur0, 0, false});
     const int nchunks = (int)plan.size();
@@ -468,13 +469,10 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
     const auto t0 = clk::now();
     auto us = [&]() { return std::chrono::duration<double, std::micro>(clk::now() - t0).count(); };
     std::vector<double> tr_h2d(nchunks, 0.0), tr_launch(nchunks, 0.0), tr_d2h(nchunks, 0.0);
-    SoloCall solo(h);
-    struct Restore {  // the launchers address the stream through h->cur, the trunk through h->trunk_force, the prologue's ring through h->em_beside
-        msiren_ctx* h;
-        int cur;
-        ~Restore() { h->cur = cur; h->trunk_force = 0; h->em_beside = false; h->trunk_after = nullptr; h->host_check_now = false; h->hc.armed = false; }
-    } restore{h, cur0};
-    h->host_check_now = nchunks == 1;
+    HostCheck hc;
+    Call call = make_call(h, true);
+    call.mode.host_check = nchunks == 1;
+    call.hc = &hc;
     auto download = [&](int k) {
         const Chunk& c = plan[k];
         tr_d2h[k] = us();
@@ -486,9 +484,9 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
     };
     for (int k = 0; k < nchunks && !rc; ++k) {
         const Chunk& c = plan[k];
-        h->cur = c.stream;
-        h->trunk_force = c.trunk;
-        h->em_beside = c.beside;
+        call.stream = c.stream;
+        call.mode.trunk = c.trunk;
+        call.mode.beside = c.beside;
         const float* d_t = in_zc ? in_zc + (size_t)c.lo * tile_elems : (const float*)h->ws_tiles.p + (size_t)c.lo * tile_elems;
         if (!in_zc) {
             hipError_t e = hipMemcpyAsync((void*)d_t, tiles_host + (size_t)c.lo * tile_elems, (size_t)c.n * tile_elems * sizeof(float), hipMemcpyHostToDevice, h->sc[c.stream].s);
@@ -497,8 +495,8 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
         tr_h2d[k] = us();
         // (the weight-stationary trunk owns its CUs: queued beside the previous chunk's conditional exact-fp32 launch it would start first,
         //  and that launch -- and the download behind it -- would wait for it to end)
-        if (pipelined && c.trunk == 2 && k >= 1 && !rc) h->trunk_after = h->sc[plan[k - 1].stream].ev_join;
-        if (!rc) rc = forward_tiles_dev(h, d_t, c.n, out_base + (size_t)c.lo * h->P);
+        call.trunk_wait = pipelined && c.trunk == 2 && k >= 1 ? h->sc[plan[k - 1].stream].ev_join : nullptr;
+        if (!rc) rc = forward_tiles_dev(h, call, d_t, c.n, out_base + (size_t)c.lo * h->P);
         if (pipelined && !rc) {
             auto& sc = h->sc[c.stream];
             if (!sc.ev_join) { hipError_t e2 = hipEventCreateWithFlags(&sc.ev_join, hipEventDisableTiming); if (e2 != hipSuccess) rc = fail(MSIREN_E_HIP, "hipEventCreate: %s", hipGetErrorString(e2)); }
@@ -510,16 +508,14 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
         if (pipelined && k >= 1 && !rc) download(k - 1);
     }
     for (int k = pipelined ? nchunks - 1 : 0; k < nchunks && !rc; ++k) download(k);
-    h->cur = cur0;
     int rs = sync_all(h);
-    if (!rc && !rs && h->hc.armed && (unsigned)h->status_host[8] == h->hc.epoch) {
+    if (!rc && !rs && hc.armed && (unsigned)h->status_host[8] == hc.epoch) {
         // the trunk met a modulation outside the fp16 domain: the batch once more on the exact-fp32 trunk (the conditional kernel, its
         // condition pointed at the word that has just been read), the download once more if there is one
-        h->hc.armed = false;
-        h->cur = plan[0].stream;
-        rc = launch_trunk_f32_cond(h, h->hc.mods, h->hc.B, h->hc.out, h->status_dev + 8, h->hc.epoch);
+        Call fix = make_call(h, true);
+        fix.stream = plan[0].stream;
+        rc = launch_trunk_f32_cond(h, fix, hc.mods, hc.B, hc.out, h->status_dev + 8, hc.epoch);
         if (!rc) download(0);
-        h->cur = cur0;
         rs = sync_all(h);
     }
     if (!rs) drain.disarm();
@@ -534,13 +530,12 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
 
 int msiren_forward_tiles(msiren_handle h, const float* tiles_host, int64_t B, float* out_host) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");
-    return with_range_fallback(h, [&] { return msiren_forward_tiles_impl(h, tiles_host, B, out_host); });
+    return take_range_flag_after(h, msiren_forward_tiles_impl(h, tiles_host, B, out_host));
 }
 
 static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, float* recon_host) {
     int rc = check(h);
     if (rc) return rc;
-    SoloCall solo(h);
     if (n < 0 || (n > 0 && (!images_host || !recon_host))) return fail(MSIREN_E_INVALID, "bad arguments");
     if (n == 0) return 0;
     int32_t nV, nH;
@@ -551,7 +546,8 @@ static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_h
     // As in msiren_forward_tiles: where the caller's reconstruction array is page-locked memory (the Python mirror's outputs are, by default)
     // the fold stores straight into it; the image always arrives by a copy (DMA from page-locked memory, through the runtime from pageable
     // memory): read in place every pixel would cross the link four times (32 x 32 tiles at a stride of 16; profiles/r5/09_*).
-    auto& sc = h->sc[h->cur];
+    const Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
     const HostSrc src(images_host, ni);
     const HostDst dst(recon_host, nr);
     HOSTBUF_OK(src);
@@ -559,7 +555,7 @@ static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_h
     DrainOnExit drain(h);
     float* const d_rec = dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_img.p;
     HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-    if ((rc = reconstruct_on_current_stream(h, (const float*)h->ws_in.p, n, height, width, d_rec))) return rc;
+    if ((rc = reconstruct_slices(h, c, (const float*)h->ws_in.p, n, height, width, d_rec))) return rc;
     if (d_rec == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_img.p, nr, hipMemcpyDeviceToHost, sc.s));
     HIPCHK(hipStreamSynchronize(sc.s));
     drain.disarm();
@@ -569,7 +565,7 @@ static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_h
 
 int msiren_reconstruct_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, float* recon_host) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");
-    return with_range_fallback(h, [&] { return msiren_reconstruct_slices_impl(h, images_host, n, height, width, recon_host); });
+    return take_range_flag_after(h, msiren_reconstruct_slices_impl(h, images_host, n, height, width, recon_host));
 }
 
 int msiren_set_streams(msiren_handle h, int32_t n) {

@@ -1,75 +1,51 @@
-// Kernel instantiations of the trunk translation units (k_*.hip), declared `extern` for the host units: a host file parses the
-// kernel headers for their parameter structs, LDS layouts and schedules, but the device code of every trunk instance is
-// generated once, in its own translation unit (make -j: six compilers side by side instead of one 4-minute run).
-// GENERATED together with k_*.hip by the list in this file's history; keep the two in step (the link fails otherwise).
+// Every kernel instance libmsiren launches, one list per kernel translation unit (k_*.hip: make -j compiles them side by side).
+// Plain preprocessor, no HIP: each k_*.hip expands its list into explicit instantiations (MSIREN_DEFINE_*), the host units into
+// `extern template` declarations (MSIREN_EXTERN_*) and the table of kernel pointers (launch_dispatch.hip), dispatch.h into the table
+// of instance names.  X(family, template arguments): the arguments are written without spaces, since they are part of the name
+// (siren_trunk_<family>_kernel<arguments>: msiren_last_trunk_kernel, bench.py's roofline.kernel).
 #pragma once
-#include "encoder_modulator_f16x3.hip.h"
-#include "siren_trunk_f16x3h.hip.h"
-#include "siren_trunk_f16x3n.hip.h"
-#include "siren_trunk_f16x3w.hip.h"
-#include "siren_trunk_f32.hip.h"
-#include "siren_trunk_x1n.hip.h"
-#include "siren_trunk_x1w.hip.h"
-namespace msiren {
-extern template __global__ void siren_trunk_f32_kernel<128, 0, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<128, 0, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<128, 1, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<128, 1, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<256, 0, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<256, 0, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<256, 1, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<256, 1, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<384, 0, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<384, 0, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<384, 1, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<384, 1, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<512, 0, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<512, 0, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<512, 1, 0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<512, 1, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_kernel<256, 0, 0, 1>(TrunkParams);
-extern template __global__ void siren_trunk_f32_cond_kernel<0>(TrunkParams);
-extern template __global__ void siren_trunk_f32_cond_kernel<1>(TrunkParams);
-extern template __global__ void siren_trunk_f16x3n_kernel<0, 3, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<0, 3, 0>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<0, 4, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<0, 4, 0>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<1, 3, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<1, 3, 0>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<1, 4, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<1, 4, 0>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3n_kernel<0, 4, 5, 1>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3h_kernel<0, 3, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3h_kernel<0, 4, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3h_kernel<1, 3, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3h_kernel<1, 4, 5>(TrunkF16Params);
-extern template __global__ void siren_trunk_f16x3w_kernel<0, 4>(TrunkWsParams);
-extern template __global__ void siren_trunk_f16x3w_kernel<1, 4>(TrunkWsParams);
-extern template __global__ void siren_trunk_f16x3w_kernel<0, 4, 1>(TrunkWsParams);
-extern template __global__ void siren_trunk_x1w_kernel<0, 0, 0>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<0, 0, 0, 3>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1w_kernel<0, 0, 1>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<0, 0, 1, 3>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1w_kernel<0, 1, 0>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<0, 1, 0, 3>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1w_kernel<0, 1, 1>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<0, 1, 1, 3>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1w_kernel<1, 0, 0>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<1, 0, 0, 3>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1w_kernel<1, 0, 1>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<1, 0, 1, 3>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1w_kernel<1, 1, 0>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<1, 1, 0, 3>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1w_kernel<1, 1, 1>(TrunkX1Params);
-extern template __global__ void siren_trunk_x1n_kernel<1, 1, 1, 3>(TrunkX1Params);
-extern template __global__ void latent_mods_f16x3_kernel<2, 2, 2, 3>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<2, 2, 4, 3>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<2, 2, 8, 3>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<2, 2, 4, 1>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<2, 2, 4, 2>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<4, 1, 4, 3>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<4, 1, 8, 3>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<4, 1, 4, 1>(EmTailParams);
-extern template __global__ void latent_mods_f16x3_kernel<4, 1, 4, 2>(EmTailParams);
-extern template __global__ void encoder_conv_f16x3_kernel<1>(EncoderParams, const float*, em_u4*, float*);
-}  // namespace msiren
+
+#define MSIREN_F32_INSTANCES(X)                                                   \
+    X(f32, 128,0,0) X(f32, 128,0,1) X(f32, 128,1,0) X(f32, 128,1,1)               \
+    X(f32, 256,0,0) X(f32, 256,0,1) X(f32, 256,1,0) X(f32, 256,1,1)               \
+    X(f32, 384,0,0) X(f32, 384,0,1) X(f32, 384,1,0) X(f32, 384,1,1)               \
+    X(f32, 512,0,0) X(f32, 512,0,1) X(f32, 512,1,0) X(f32, 512,1,1)               \
+    X(f32, 256,0,0,1) /* stamped build: msiren_trunk_timeline */                  \
+    X(f32_cond, 0) X(f32_cond, 1)
+#define MSIREN_F16X3N_INSTANCES(X)                                                \
+    X(f16x3n, 0,3,5) X(f16x3n, 0,3,0) X(f16x3n, 0,4,5) X(f16x3n, 0,4,0)           \
+    X(f16x3n, 1,3,5) X(f16x3n, 1,3,0) X(f16x3n, 1,4,5) X(f16x3n, 1,4,0)           \
+    X(f16x3n, 0,4,5,1) /* stamped build: msiren_f16x3_timeline */
+#define MSIREN_F16X3H_INSTANCES(X) X(f16x3h, 0,3,5) X(f16x3h, 0,4,5) X(f16x3h, 1,3,5) X(f16x3h, 1,4,5)
+#define MSIREN_F16X3W_INSTANCES(X) X(f16x3w, 0,4) X(f16x3w, 1,4) X(f16x3w, 0,4,1) /* stamped build: msiren_f16x3w_timeline */
+#define MSIREN_X1N_INSTANCES(X)                                                   \
+    X(x1n, 0,0,0,3) X(x1n, 0,0,1,3) X(x1n, 0,1,0,3) X(x1n, 0,1,1,3)               \
+    X(x1n, 1,0,0,3) X(x1n, 1,0,1,3) X(x1n, 1,1,0,3) X(x1n, 1,1,1,3)
+#define MSIREN_X1W_INSTANCES(X)                                                   \
+    X(x1w, 0,0,0) X(x1w, 0,0,1) X(x1w, 0,1,0) X(x1w, 0,1,1)                       \
+    X(x1w, 1,0,0) X(x1w, 1,0,1) X(x1w, 1,1,0) X(x1w, 1,1,1)
+#define MSIREN_TRUNK_INSTANCES(X)                                                                                          \
+    MSIREN_F32_INSTANCES(X) MSIREN_F16X3N_INSTANCES(X) MSIREN_F16X3H_INSTANCES(X) MSIREN_F16X3W_INSTANCES(X) \
+    MSIREN_X1N_INSTANCES(X) MSIREN_X1W_INSTANCES(X)
+
+// the one-launch prologue (<family>_f16x3_kernel: encoder_modulator_f16x3.hip.h); latent_mods<NPH,NPZ,DEPTH,MODE>
+#define MSIREN_PROLOGUE_INSTANCES(X)                                                              \
+    X(latent_mods, 2,2,2,3) X(latent_mods, 2,2,4,3) X(latent_mods, 2,2,8,3)                       \
+    X(latent_mods, 2,2,4,1) X(latent_mods, 2,2,4,2)                                               \
+    X(latent_mods, 4,1,4,3) X(latent_mods, 4,1,8,3) X(latent_mods, 4,1,4,1) X(latent_mods, 4,1,4,2) \
+    X(encoder_conv, 1)
+
+// HIP units only (inside namespace msiren, behind the kernel headers): the parameter list of each family
+#define MSIREN_PARAMS_f32 (TrunkParams)
+#define MSIREN_PARAMS_f32_cond (TrunkParams)
+#define MSIREN_PARAMS_f16x3n (TrunkF16Params)
+#define MSIREN_PARAMS_f16x3h (TrunkF16Params)
+#define MSIREN_PARAMS_f16x3w (TrunkWsParams)
+#define MSIREN_PARAMS_x1n (TrunkX1Params)
+#define MSIREN_PARAMS_x1w (TrunkX1Params)
+#define MSIREN_PARAMS_latent_mods (EmTailParams)
+#define MSIREN_PARAMS_encoder_conv (EncoderParams, const float*, em_u4*, float*)
+#define MSIREN_DEFINE_TRUNK(fam, ...) template __global__ void siren_trunk_##fam##_kernel<__VA_ARGS__> MSIREN_PARAMS_##fam;
+#define MSIREN_DEFINE_PROLOGUE(fam, ...) template __global__ void fam##_f16x3_kernel<__VA_ARGS__> MSIREN_PARAMS_##fam;
+#define MSIREN_EXTERN_TRUNK(fam, ...) extern MSIREN_DEFINE_TRUNK(fam, __VA_ARGS__)
+#define MSIREN_EXTERN_PROLOGUE(fam, ...) extern MSIREN_DEFINE_PROLOGUE(fam, __VA_ARGS__)

@@ -11,7 +11,6 @@
 #include "siren_trunk_f16x3n.hip.h"        // F16Lds
 #include "siren_trunk_x1n.hip.h"           // X1nLds
 #include "siren_trunk_x1w.hip.h"           // X1wLds
-#include "trunk_instances.h"
 
 namespace mh {
 
