@@ -33,11 +33,12 @@
 extern "C" {
 #endif
 
-/* 3 (round 6): msiren_runtime_info, msiren_host_range_kind added; the large-call split (MSIREN_SPLIT_MIN) and the per-call page-locking of
+/* 4: msiren_sample_* (the trunk at caller-chosen coordinates), msiren_upsampled_geometry / _lattice and the *_scaled slice pipeline
+ * (another output stride) added.  3 (round 6): msiren_runtime_info, msiren_host_range_kind added; the large-call split (MSIREN_SPLIT_MIN) and the per-call page-locking of
  * caller buffers (MSIREN_HOST_REGISTER) left the library.  2 (round 5): msiren_chain_* gone, msiren_profile_read_kernel /
  * msiren_last_trunk_kernel / msiren_device_pci added; sync no longer returns MSIREN_E_RANGE.  A library of another number refuses
  * msiren_create. */
-#define MSIREN_ABI_VERSION 3
+#define MSIREN_ABI_VERSION 4
 
 #if defined(__GNUC__)
 #define MSIREN_API __attribute__((visibility("default")))
@@ -213,6 +214,43 @@ MSIREN_API int msiren_gather_rows_dev(msiren_handle h, const float* src_dev, con
 MSIREN_API int msiren_scatter_rows_dev(msiren_handle h, const float* src_dev, const int32_t* idx_dev, int64_t n_idx, int64_t n_rows, int64_t row_elems,
                                        float* dst_dev);
 
+/* ---- the representation off its own grid ------------------------------------------------------ */
+
+/* SirenNet.forward(coords, mods) at coordinates the CALLER chooses (modulated_siren.py:215-233 takes any (..., 2) coordinates):
+ * one set coords (Q, 2) float32 shared by all patches of the call -- column 0 the row coordinate, column 1 the column coordinate, as in
+ * the "grid" buffer -- and out[b, q] = SirenNet(coords[q], mods[:, b]), out (B, Q).  1 <= Q <= 65 536 (MSIREN_E_INVALID beyond: the
+ * layer-0 table of the call is 4 H bytes per coordinate); Q need not be a square; coordinates may lie outside [-1, 1]; a non-finite
+ * coordinate gives non-finite outputs at that q only.  The 16-bit trunks read layer 0 from a table that is built on the device, on
+ * the call's stream, in front of the trunk (sample_grid.hip.h); the fp32 trunk reads the coordinates themselves.  The _tiles forms
+ * run encoder and Modulator first, as ModulatedSiren.forward does (modulated_siren.py:435-457).  The _dev forms enqueue on the stream
+ * rotation like the forward calls; coords_dev is read on the stream, so the caller keeps it unchanged until msiren_sync.  The
+ * host-pointer forms are synchronous one-chunk calls.  B = 0 does nothing. */
+MSIREN_API int msiren_sample_mods(msiren_handle h, const float* coords_host, int64_t Q, const float* mods_host, int64_t B, float* out_host);
+MSIREN_API int msiren_sample_mods_dev(msiren_handle h, const float* coords_dev, int64_t Q, const float* mods_dev, int64_t B, float* out_dev);
+MSIREN_API int msiren_sample_tiles(msiren_handle h, const float* coords_host, int64_t Q, const float* tiles_host, int64_t B, float* out_host);
+MSIREN_API int msiren_sample_tiles_dev(msiren_handle h, const float* coords_dev, int64_t Q, const float* tiles_dev, int64_t B, float* out_dev);
+
+/* Build-defined (the reference has no such mode): the slice pipeline at another OUTPUT stride I' ("out_stride").
+ * Tiling stays O / I -- the encoder sees the same tiles -- and every tile is evaluated on the S' x S' pixel centres of the same physical
+ * tile, S' = S I'/I, then folded with kernel S', stride I', padding pad' = (S' - I')/2 and the reference's weight formula at size S'
+ * (tiling.py:67-88).  S' and pad' must be integers and S' >= 2, MSIREN_E_INVALID otherwise.  With d = 2/(S-1), r = I'/I (fp64):
+ *     lin'[j] = (-1 - d/2) + (d/r) (j + 1/2),  j = 0 .. S'-1,  rounded once to fp32;  coords[a S' + b] = (lin'[a], lin'[b]).
+ * msiren_upsampled_geometry / _lattice need neither a handle nor a device. */
+MSIREN_API int msiren_upsampled_geometry(int32_t S, int32_t I, int32_t out_stride, int32_t* out_tile, int32_t* pad);
+MSIREN_API int msiren_upsampled_lattice(int32_t S, int32_t I, int32_t out_stride, float* lin_out /* out_tile floats */);
+/* Build-defined: msiren_reconstruct_slices(_dev) / msiren_reconstruct_tiles_dev / msiren_weighted_fold_dev at output stride
+ * out_stride: recon (n, nV*out_stride, nH*out_stride).  out_stride = inner_patch_size IS the existing entry point (the model's own
+ * grid and committed table: the same bits).  The lattice's table and fold weights are built once per stream and stride and kept until
+ * the next msiren_commit_weights.  n = 0 does nothing. */
+MSIREN_API int msiren_reconstruct_slices_scaled(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                                int32_t out_stride, float* recon_host);
+MSIREN_API int msiren_reconstruct_slices_scaled_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                                    int32_t out_stride, float* recon_dev);
+MSIREN_API int msiren_reconstruct_tiles_scaled_dev(msiren_handle h, const float* tiles_dev, int64_t n_slices, int32_t n_vertical,
+                                                   int32_t n_horizontal, int32_t out_stride, float* recon_dev);
+MSIREN_API int msiren_weighted_fold_scaled_dev(msiren_handle h, const float* tiles_dev /* (n*nV*nH, S', S') */, int64_t n_slices,
+                                               int32_t n_vertical, int32_t n_horizontal, int32_t out_stride, float* recon_dev);
+
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.
  * data range = max - min over both images (subtracted in float32); PSNR = 10 log10(range^2 / mean((o-p)^2));
@@ -301,7 +339,8 @@ MSIREN_API int msiren_profile_read(msiren_handle h, int64_t* launches, double* t
 /* The same, per trunk instance: entry `index` (0-based, in order of first launch since msiren_profile_enable(h, 1)) ->
  * its name as launched (e.g. "siren_trunk_f16x3w_kernel<0,4>"), launch count, summed milliseconds and the coordinates
  * (patches x siren_patch_size^2) its launches evaluated -- a host call of several slices runs two trunk instances, so a roofline figure is per instance: msiren_flops_per_coord x coords_total / ms_total.  MSIREN_E_INVALID past
- * the last entry.  msiren_last_trunk_kernel: the instance the most recent trunk launch of the handle used. */
+ * the last entry.  A msiren_sample_* call on a 16-bit handle adds an entry "layer0_table_kernel" (its coordinates: those of the call's set; not
+ * part of msiren_profile_read's trunk totals).  msiren_last_trunk_kernel: the instance the most recent trunk launch of the handle used. */
 MSIREN_API int msiren_profile_read_kernel(msiren_handle h, int32_t index, char* name128, int64_t* launches, double* ms_total,
                                           int64_t* coords_total);
 MSIREN_API int msiren_last_trunk_kernel(msiren_handle h, char* name128);

@@ -32,7 +32,7 @@ int msiren_trunk_timeline(msiren_handle h, const float* mods_dev, int64_t B, flo
     DevBuf st;
     if ((rc = ensure(h, st, (size_t)grid * 32 * sizeof(uint64_t)))) return rc;
     HIPCHK(hipMemsetAsync(st.p, 0, (size_t)grid * 32 * sizeof(uint64_t), h->sc[h->cur].s));
-    msiren::TrunkParams p = make_trunk_params(h, nullptr, mods_dev, h->H, B, out_dev);
+    msiren::TrunkParams p = make_trunk_params(h, Call{}, mods_dev, h->H, B, out_dev);
     p.stamps = (unsigned long long*)st.p;
     hipLaunchKernelGGL((msiren::siren_trunk_f32_kernel<256, 0, 0, 1>), dim3(grid), dim3(256), 256 * 256 + 256 * 16, h->sc[h->cur].s, p);
     HIPCHK(hipGetLastError());

@@ -58,6 +58,7 @@ struct CallMode {
     bool beside = false;      // the prologue runs beside a trunk of the same call (HostChunk::beside)
     bool plan = false;        // a device-side list of kept patches is in effect: the batch size is not known on the host
     bool host_check = false;  // the trunk's domain guard is read on the host behind the call's wait (synchronous one-chunk call)
+    int coords = 0;           // coordinates per patch of a call that brings its own set (msiren_sample_*, *_scaled); 0 = the handle's P
     bool alone() const { return nstreams == 1 || sync; }  // no other call of the handle runs beside this one
 };
 
@@ -108,7 +109,7 @@ inline TrunkPick pick_trunk(const DispatchHandle& d, const CallMode& m, int64_t 
     // Half-unit instance (16 coordinates per wave, twice the waves) for small batches: everything fits in one round even as
     // half-units, so the extra waves are free and the latency drops (a single tile: 76 -> 66 us).  Needs the unit count on the host
     // (no plan) and the depth-5 instance.
-    const int64_t units = B * ((d.P + 31) / 32);
+    const int64_t units = B * (((m.coords ? m.coords : d.P) + 31) / 32);
     t.half = !m.plan && d.L == 5 && d.half_allowed && units <= 2 * (int64_t)d.num_cus;
     if (m.trunk == 2 || (m.trunk == 0 && ws_capable(d, B) && m.alone() && !t.half)) {
         t.half = false;

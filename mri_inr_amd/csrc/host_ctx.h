@@ -8,6 +8,8 @@
 //     comm_rccl.hip        RCCL through dlopen: communicator, the one weight broadcast, barrier / MAX
 //     diagnostics.hip      stamped timeline builds, the sustained-MFMA probe
 //     scores.hip           PSNR / SSIM / NRMSE of image pairs (the evaluation harness's metrics; kernels: scores.hip.h)
+//     sample_grid.hip      the trunk at caller-chosen coordinates and the slice pipeline at another output stride: the per-call layer-0
+//                          table (kernel: sample_grid.hip.h), msiren_sample_*, msiren_upsampled_*, the *_scaled entry points
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -56,6 +58,13 @@ struct msiren_ctx {
         mh::DevBuf mods, modpad, latent, patches, keep, rec, queue, feat, plan;
         mh::DevBuf score;     // partials of msiren_score_images(_dev) (scores.hip.h)
         mh::DevBuf cscratch;  // split-fp16 Modulator: the latent part of layers 1.., lane-private (encoder_modulator_f16x3.hip.h)
+        mh::DevBuf coords, l0tab;  // msiren_sample_*: the call's coordinates (host-pointer form) and its layer-0 table (sample_grid.hip)
+        struct Lattice {           // an output stride's lattice, kept per stream until the next msiren_commit_weights (sample_grid.hip)
+            int out_stride = 0, tile = 0, pad = 0;  // I', S', pad'
+            float *coords = nullptr, *table = nullptr, *foldw = nullptr;  // (S'S', 2); (H/4, S'S', 4) or null (fp32 trunk); (S', S')
+            std::vector<float> host;  // what coords and foldw were uploaded from (alive while the copies may be in flight)
+        };
+        std::vector<Lattice> lattices;
         hipEvent_t ev_join = nullptr;  // a host call that pipelines itself: this stream's chunk has been enqueued
         msiren::PassQueue pq;  // host view of the never-reset pass counter (pass_queue.h)
     } sc[3];
@@ -70,6 +79,7 @@ struct msiren_ctx {
     bool committed = false, have_modulator = false, have_encoder = false;
     // trunk
     float *d_grid = nullptr, *d_l0 = nullptr, *d_wp = nullptr, *d_bias = nullptr, *d_wout = nullptr;
+    float *d_w0raw = nullptr, *d_b0raw = nullptr;  // net.layers.0.weight (H, 2) / .bias (H; zeros without bias) as stored: layer0_table_kernel
     float bout = 0.f, cg0 = 0.f, cg = 0.f;
     // split-fp16 trunk (MSIREN_PREC_F16X3)
     void* d_wp16n = nullptr;  // weight stream of the 16x16x32 kernel (default)
@@ -115,7 +125,7 @@ struct msiren_ctx {
     int64_t prof_launches = 0;
     double prof_ms = 0.0;
     struct ProfRec { hipEvent_t a, b; int kernel; int64_t coords; };
-    struct ProfKernel { std::string name; int64_t launches = 0, coords = 0; double ms = 0.0; };
+    struct ProfKernel { std::string name; int64_t launches = 0, coords = 0; double ms = 0.0; bool trunk = true; };  // trunk: counts in msiren_profile_read's totals
     std::vector<ProfRec> prof_events;
     std::vector<ProfKernel> prof_kernels;  // totals per trunk instance since msiren_profile_enable(h, 1), in order of first launch
     size_t prof_used = 0;
@@ -132,13 +142,26 @@ namespace mh {
 // flag in HOST memory (status_host[8]) and the call looks at it after the wait -- no conditional launch (4.4 us of kernel + a launch
 // gap per call); a flagged call enqueues the exact-fp32 trunk then and waits once more (profiles/r5/12_*).
 struct HostCheck { const float* mods = nullptr; int64_t B = 0; float* out = nullptr; unsigned epoch = 0; bool armed = false; };
+// The coordinate set a call evaluates: null / 0 = the model's own grid and the table committed with the weights.
+struct CoordSet {
+    const float* coords = nullptr;  // device, (Q, 2): what the fp32 trunks read (the conditional ones of the domain guard included)
+    const float* table = nullptr;   // device, (H/4, Q, 4): layer 0 of the 16-bit trunks (layer0_table_kernel); null on an fp32 handle
+    int Q = 0;
+};
 struct Call {
     int stream = 0;                    // h->sc[stream]
     msiren::CallMode mode;             // what dispatch.h reads of the call
     const int* plan = nullptr;         // device-side list of kept patches (slice pipeline; mode.plan)
     hipEvent_t trunk_wait = nullptr;  // the trunk waits for this event first (a pipelined host call's weight-stationary last chunk)
     HostCheck* hc = nullptr;           // mode.host_check: where the trunk launch leaves what the host check needs
+    CoordSet cs;                       // msiren_sample_* / the *_scaled pipeline (with_coords sets it and mode.coords together)
+    int P(const msiren_ctx* h) const { return cs.Q ? cs.Q : h->P; }  // coordinates per patch of this call
 };
+inline Call with_coords(Call c, const CoordSet& cs) {
+    c.cs = cs;
+    c.mode.coords = cs.Q;
+    return c;
+}
 inline Call make_call(const msiren_ctx* h, bool sync) {
     Call c;
     c.stream = h->cur;
@@ -146,6 +169,10 @@ inline Call make_call(const msiren_ctx* h, bool sync) {
     c.mode.sync = sync;
     return c;
 }
+
+// the output side of the slice pipeline where it is not the model's own (the call carries the lattice: Call::cs): tile S', stride I',
+// padding pad', fold weights (S', S')
+struct OutGeom { int tile = 0, stride = 0, pad = 0; const float* foldw = nullptr; };
 
 // msiren.hip
 int use_device(msiren_ctx* h);
@@ -166,16 +193,27 @@ int pack_modulator(msiren_ctx* h);
 int pack_encoder(msiren_ctx* h);
 int pack_prologue_f16x3(msiren_ctx* h);
 int pack_fold_weights(msiren_ctx* h);
+std::vector<float> fold_weight_matrix(int S);  // generate_weight_matrix(S) of the reference (tiling.py:67-88), (S, S)
 
 // launch_dispatch.hip: everything below enqueues on h->sc[c.stream].s
 void describe_for_dispatch(msiren_ctx* h);  // h->dh from the committed weights (msiren_commit_weights)
+// msiren_profile_enable: an event pair around a launch on stream s; `name` null = the trunk launched last
+int profile_begin(msiren_ctx* h, int s, hipEvent_t* end_event);
+int profile_end(msiren_ctx* h, int s, hipEvent_t end_event, int64_t coords, const char* name = nullptr);
 int launch_trunk(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev);
 int launch_trunk_f32_cond(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev, const int* flag_word = nullptr, unsigned flag_val = 0);
 int launch_modulator(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* mods_dev);
 int launch_encoder(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev);
 int forward_latent_dev(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* out_dev, float* mods_out_dev);
 int forward_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* out_dev);
-int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev);
+int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og = nullptr);
+
+int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
+int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
+
+// sample_grid.hip
+int scaled_call(msiren_ctx* h, Call& c, int32_t out_stride, OutGeom* og);  // the call evaluates and folds the lattice of out_stride (built on first use)
+void drop_lattices(msiren_ctx* h);  // msiren_commit_weights (the streams are idle), msiren_destroy
 
 // comm_rccl.hip
 int comm_destroy(msiren_ctx* h);

@@ -3,5 +3,5 @@
 #include "host_ctx.h"
 
 namespace mh {
-msiren::TrunkParams make_trunk_params(msiren_ctx* h, const int* plan, const float* mods, int stride, int64_t B, float* out_dev);
+msiren::TrunkParams make_trunk_params(msiren_ctx* h, const Call& c, const float* mods, int stride, int64_t B, float* out_dev);
 }

@@ -69,9 +69,9 @@ int launch(msiren_ctx* h, int s, int inst, int64_t grid, int lds, P p, bool name
     return 0;
 }
 
-msiren::TrunkParams make_trunk_params(msiren_ctx* h, const int* plan, const float* mods, int stride, int64_t B, float* out_dev) {
+msiren::TrunkParams make_trunk_params(msiren_ctx* h, const Call& c, const float* mods, int stride, int64_t B, float* out_dev) {
     msiren::TrunkParams p{};
-    p.grid = h->d_grid;
+    p.grid = c.cs.Q ? c.cs.coords : h->d_grid;
     p.l0 = h->d_l0;
     p.wp = h->d_wp;
     p.bias = h->d_bias;
@@ -82,12 +82,12 @@ msiren::TrunkParams make_trunk_params(msiren_ctx* h, const int* plan, const floa
     p.cg0 = h->cg0;
     p.cg = h->cg;
     p.B = (int)B;
-    p.P = h->P;
+    p.P = c.P(h);
     p.L = h->L;
     p.mod_stride = stride;
-    p.chunks = (h->P + 63) / 64;
+    p.chunks = (p.P + 63) / 64;
     p.stamps = nullptr;
-    p.plan = plan;
+    p.plan = c.plan;
     return p;
 }
 
@@ -132,7 +132,7 @@ static int queue_reset_after_plan_launch(msiren_ctx* h, int s, bool by_the_next_
 }
 
 // msiren_profile_enable: a HIP event pair around every trunk launch, on the stream it is launched on
-static int profile_begin(msiren_ctx* h, int s, hipEvent_t* end_event) {
+int profile_begin(msiren_ctx* h, int s, hipEvent_t* end_event) {
     *end_event = nullptr;
     if (!h->profile) return 0;
     if (h->prof_used == h->prof_events.size()) {
@@ -147,17 +147,20 @@ static int profile_begin(msiren_ctx* h, int s, hipEvent_t* end_event) {
     return 0;
 }
 
-// closes the pair profile_begin opened: the launch in between was h->last_trunk over `coords` coordinates
-static int profile_end(msiren_ctx* h, int s, hipEvent_t end_event, int64_t coords) {
+// closes the pair profile_begin opened: the launch in between was h->last_trunk (or `name`: not a trunk) over `coords` coordinates
+int profile_end(msiren_ctx* h, int s, hipEvent_t end_event, int64_t coords, const char* name) {
     if (!end_event) return 0;
     HIPCHK(hipEventRecord(end_event, h->sc[s].s));
+    const bool trunk = !name;
+    if (trunk) name = h->last_trunk;
     auto& r = h->prof_events[h->prof_used - 1];
     int k = 0;
     for (; k < (int)h->prof_kernels.size(); ++k)
-        if (h->prof_kernels[k].name == h->last_trunk) break;
+        if (h->prof_kernels[k].name == name) break;
     if (k == (int)h->prof_kernels.size()) {
         h->prof_kernels.emplace_back();
-        h->prof_kernels.back().name = h->last_trunk;
+        h->prof_kernels.back().name = name;
+        h->prof_kernels.back().trunk = trunk;
     }
     r.kernel = k;
     r.coords = coords;
@@ -174,7 +177,7 @@ static int launch_trunk_f16x3w(msiren_ctx* h, const Call& c, const msiren::Trunk
     msiren::TrunkWsParams p{};
     if (!h->d_dump) HIPCHK(hipMalloc((void**)&h->d_dump, 256 * sizeof(float)));
     p.dump = h->d_dump;
-    p.s0t = h->d_s0t;
+    p.s0t = c.cs.Q ? c.cs.table : h->d_s0t;
     p.wp = (const _Float16*)h->d_wp16n;
     p.bias = h->d_bias16;
     p.wout = h->d_wout16;
@@ -185,10 +188,10 @@ static int launch_trunk_f16x3w(msiren_ctx* h, const Call& c, const msiren::Trunk
     p.cg0 = h->cg0;
     p.cg = h->cg;
     p.B = (int)B;
-    p.P = h->P;
+    p.P = c.P(h);
     p.L = h->L;
     p.plan = c.plan;
-    const int upp = (h->P + 31) / 32;
+    const int upp = (p.P + 31) / 32;
     const int64_t units = B * upp;
     if (units > 0x3fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
     p.units_per_patch = upp;
@@ -218,9 +221,9 @@ static int launch_trunk_f16x3w(msiren_ctx* h, const Call& c, const msiren::Trunk
 // prologue and layer 0 do not shrink), and the cross-stream dependency costs more than the tail it removes.
 static int launch_trunk_f16x3n(msiren_ctx* h, const Call& c, const msiren::TrunkPick& t, const float* mods_dev, int64_t B, float* out_dev) {
     msiren::TrunkF16Params p{};
-    p.grid = h->d_grid;
+    p.grid = c.cs.Q ? c.cs.coords : h->d_grid;
     p.l0 = h->d_l0;
-    p.s0t = h->d_s0t;
+    p.s0t = c.cs.Q ? c.cs.table : h->d_s0t;
     p.wp = (const _Float16*)h->d_wp16n;
     p.bias = h->d_bias16;
     p.wout = h->d_wout16;
@@ -231,11 +234,11 @@ static int launch_trunk_f16x3n(msiren_ctx* h, const Call& c, const msiren::Trunk
     p.cg0 = h->cg0;
     p.cg = h->cg;
     p.B = (int)B;
-    p.P = h->P;
+    p.P = c.P(h);
     p.L = h->L;
     p.plan = c.plan;
-    if (B * ((h->P + 31) / 32) > 0x3fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
-    p.units_per_patch = t.half ? (h->P + 15) / 16 : (h->P + 31) / 32;
+    if (B * ((p.P + 31) / 32) > 0x3fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
+    p.units_per_patch = t.half ? (p.P + 15) / 16 : (p.P + 31) / 32;
     p.unit_base = 0;
     p.total_units = (int)(B * p.units_per_patch);
     // the pass queue: workgroup g starts with pass g of 4 units, further passes come from the counter
@@ -254,7 +257,7 @@ static int launch_trunk_f16x3n(msiren_ctx* h, const Call& c, const msiren::Trunk
 static int launch_trunk_x1(msiren_ctx* h, const Call& c, const msiren::TrunkPick& t, const float* mods_dev, int64_t B, float* out_dev) {
     const bool ws = msiren::kInstances[t.inst].family == Kernel::x1w;
     msiren::TrunkX1Params p{};
-    p.s0t = h->d_s0t512;
+    p.s0t = c.cs.Q ? c.cs.table : h->d_s0t512;
     p.wp = (const unsigned short*)(ws ? h->d_wpx1w : h->d_wpx1n);
     p.bias32 = h->d_bias32x1;
     p.wout = (const _Float16*)h->d_woutx1;
@@ -265,9 +268,9 @@ static int launch_trunk_x1(msiren_ctx* h, const Call& c, const msiren::TrunkPick
     p.cg0 = h->cg0;
     p.cg = h->cg;
     p.B = (int)B;
-    p.P = h->P;
+    p.P = c.P(h);
     p.L = h->L;
-    p.units_per_patch = (h->P + 31) / 32;
+    p.units_per_patch = (p.P + 31) / 32;
     const int64_t units = B * p.units_per_patch;
     if (units > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
     p.total_units = (int)units;
@@ -288,7 +291,7 @@ static int launch_trunk_x1(msiren_ctx* h, const Call& c, const msiren::TrunkPick
 
 // exact-fp32 trunk: one workgroup per 64 coordinates of a patch
 static int launch_trunk_f32(msiren_ctx* h, const Call& c, int inst, const float* mods_dev, int64_t B, float* out_dev) {
-    const int chunks = (h->P + 63) / 64;
+    const int chunks = (c.P(h) + 63) / 64;
     if (B * (int64_t)chunks > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
     auto& sc = h->sc[c.stream];
     const float* mods = mods_dev;
@@ -303,12 +306,12 @@ static int launch_trunk_f32(msiren_ctx* h, const Call& c, int inst, const float*
         mods = (const float*)sc.modpad.p;
         stride = h->HP;
     }
-    const msiren::TrunkParams p = make_trunk_params(h, c.plan, mods, stride, B, out_dev);
+    const msiren::TrunkParams p = make_trunk_params(h, c, mods, stride, B, out_dev);
     const int lds = h->HP * 256 + h->HP * 16;  // X image + layer-0 rows
     hipEvent_t e1 = nullptr;
     int rc;
     if ((rc = profile_begin(h, c.stream, &e1)) || (rc = launch(h, c.stream, inst, B * chunks, lds, p, true))) return rc;
-    return profile_end(h, c.stream, e1, B * h->P);
+    return profile_end(h, c.stream, e1, B * c.P(h));
 }
 
 // Behind every split-fp16 trunk launch, on the same stream: the exact-fp32 trunk over the same batch as a conditional launch
@@ -318,9 +321,9 @@ static int launch_trunk_f32(msiren_ctx* h, const Call& c, int inst, const float*
 // reference's fp32 arithmetic computes (modulated_siren.py:215-233), on the asynchronous API as well; the flag in host memory is
 // informational (msiren_range_events).
 int launch_trunk_f32_cond(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev, const int* flag_word, unsigned flag_val) {
-    const int cpp = (h->P + 31) / 32;
+    const int cpp = (c.P(h) + 31) / 32;
     if (B * (int64_t)cpp > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
-    msiren::TrunkParams p = make_trunk_params(h, c.plan, mods_dev, h->H, B, out_dev);  // (f16x3 needs H = 256 = HP: no padding of the rows)
+    msiren::TrunkParams p = make_trunk_params(h, c, mods_dev, h->H, B, out_dev);  // (f16x3 needs H = 256 = HP: no padding of the rows)
     p.cond = flag_word ? flag_word : (const int*)h->sc[c.stream].queue.p + 16;
     p.cond_val = (int)(flag_word ? flag_val : h->range_epoch);
     p.items = (int)(B * cpp);
@@ -343,15 +346,15 @@ int launch_trunk(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B,
     if (family == Kernel::f16x3w) rc = launch_trunk_f16x3w(h, c, t, mods_dev, B, out_dev);
     else if (family == Kernel::x1w || family == Kernel::x1n) rc = launch_trunk_x1(h, c, t, mods_dev, B, out_dev);
     else rc = launch_trunk_f16x3n(h, c, t, mods_dev, B, out_dev);
-    if (rc || (rc = profile_end(h, c.stream, e1, B * h->P))) return rc;
+    if (rc || (rc = profile_end(h, c.stream, e1, B * c.P(h)))) return rc;
     if (t.guard == Guard::host) {  // (the caller looks at the flag in host memory behind its wait for the stream)
         *c.hc = {mods_dev, B, out_dev, h->range_epoch, true};
         return 0;
     }
     if (t.guard == Guard::f32_512) {  // H = 512: the 64-coordinate exact-fp32 trunk as the conditional launch (its workgroups read the flag word and leave)
-        const int chunks = (h->P + 63) / 64;
+        const int chunks = (c.P(h) + 63) / 64;
         if (B * (int64_t)chunks > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
-        msiren::TrunkParams p = make_trunk_params(h, c.plan, mods_dev, h->H, B, out_dev);
+        msiren::TrunkParams p = make_trunk_params(h, c, mods_dev, h->H, B, out_dev);
         p.cond = (const int*)h->sc[c.stream].queue.p + 16;
         p.cond_val = (int)h->range_epoch;
         p.host_flag = h->status_dev;
@@ -657,14 +660,18 @@ namespace mh {
 
 // filter -> model -> reintegrate -> weighted fold on tiles that are already on the device (the call's stream)
 // `images_dev` given: `patches` is scratch that image_to_patches fills; null: `patches` are the caller's tiles
+// `og` (with c.cs): the output side at another stride (msiren_*_scaled); null: the model's own S, I and fold weights
 static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw,
-                             const float* patches_ro, int64_t n, int32_t nV, int32_t nH, float* recon_dev) {
+                             const float* patches_ro, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og) {
     int rc;
     auto& sc = h->sc[c.stream];
     const int64_t NP = n * nV * nH;
+    const int P = c.P(h), upp = (P + 31) / 32;
+    const int oS = og ? og->tile : h->S, oI = og ? og->stride : h->I, opad = og ? og->pad : (h->S - h->I) / 2;
+    const float* foldw = og ? og->foldw : h->d_foldw;
     if (NP > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "too many patches for one call: %lld", (long long)NP);
     if ((rc = ensure(h, sc.keep, (size_t)(NP + 64) * sizeof(int)))) return rc;
-    if ((rc = ensure(h, sc.rec, (size_t)NP * h->P * sizeof(float)))) return rc;
+    if ((rc = ensure(h, sc.rec, (size_t)NP * P * sizeof(float)))) return rc;
     if ((rc = ensure(h, sc.latent, (size_t)NP * h->Z * sizeof(float)))) return rc;
     if ((rc = ensure(h, sc.mods, (size_t)h->L * NP * h->H * sizeof(float)))) return rc;
     int* black = (int*)sc.keep.p;
@@ -682,14 +689,14 @@ static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images
     const bool fused = msiren::fused_slice_tiling(c.mode, images_dev != nullptr);
     if (fused) {
         if ((rc = ensure_queue(h, c.stream))) return rc;
-        msiren::TilingPlanParams tp{images_dev, patches_rw, black, plan, (unsigned*)sc.queue.p + 32, (int)n, height, width, nV, nH, h->O, h->I, pad, (int)NP, (h->P + 31) / 32};
+        msiren::TilingPlanParams tp{images_dev, patches_rw, black, plan, (unsigned*)sc.queue.p + 32, (int)n, height, width, nV, nH, h->O, h->I, pad, (int)NP, upp};
         hipLaunchKernelGGL(msiren::patches_flags_plan_kernel, dim3((unsigned)NP), dim3(256), 0, st, tp);
         HIPCHK(hipGetLastError());
     } else {
         if (images_dev && (rc = launch_image_to_patches(h, c.stream, images_dev, n, height, width, patches_rw))) return rc;
         hipLaunchKernelGGL(msiren::black_flags_kernel, dim3((unsigned)NP), dim3(256), 0, st, patches, black, h->O * h->O);
         HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(msiren::compact_flags_kernel, dim3(1), dim3(256), 0, st, black, (int)NP, (h->P + 31) / 32, plan);
+        hipLaunchKernelGGL(msiren::compact_flags_kernel, dim3(1), dim3(256), 0, st, black, (int)NP, upp, plan);
         HIPCHK(hipGetLastError());
     }
     Call pc = c;  // the model runs over the kept patches only: their count stays on the device
@@ -698,16 +705,17 @@ static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images
     if ((rc = launch_encoder_modulator(h, pc, patches, NP, (float*)sc.latent.p, (float*)sc.mods.p))) return rc;
     if ((rc = launch_trunk(h, pc, (const float*)sc.mods.p, NP, rec))) return rc;
     if ((rc = queue_reset_after_plan_launch(h, c.stream, fused))) return rc;
-    const int64_t total = n * nV * h->I * (int64_t)nH * h->I;
+    const int64_t total = n * nV * oI * (int64_t)nH * oI;
+    if ((total + 255) / 256 > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "reconstruction too large for one call: %lld pixels", (long long)total);
     hipLaunchKernelGGL(msiren::weighted_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       rec, h->d_foldw, recon_dev, black, plan + 2 + NP, n, nV, nH, h->S, h->I, (h->S - h->I) / 2,
+                       rec, foldw, recon_dev, black, plan + 2 + NP, n, nV, nH, oS, oI, opad,
                        fused && sc.queue.p ? (int*)sc.queue.p : nullptr);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 // slice pipeline on the call's stream (the host-pointer entry point enqueues its copies around it)
-int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev) {
+int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og) {
     int rc;
     if (n < 0 || (n > 0 && (!images_dev || !recon_dev))) return fail(MSIREN_E_INVALID, "bad arguments");
     if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
@@ -722,7 +730,24 @@ int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, 
         return fail(MSIREN_E_INVALID, "image %dx%d is too small for reflect padding of %d/%d", height, width, padr + vpad, padr + hpad);
     auto& sc = h->sc[c.stream];
     if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float)))) return rc;
-    return reconstruct_tiles(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, recon_dev);
+    return reconstruct_tiles(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, recon_dev, og);
+}
+
+// msiren_weighted_fold_dev with the output side of another stride (kernel S', stride I', padding pad'): complete tiles, no black flags
+int weighted_fold_dev(msiren_handle h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og) {
+    const int64_t total = n * nV * og.stride * (int64_t)nH * og.stride;
+    if ((total + 255) / 256 > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "reconstruction too large for one call: %lld pixels", (long long)total);
+    hipLaunchKernelGGL(msiren::weighted_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, h->sc[c.stream].s,
+                       tiles_dev, og.foldw, recon_dev, nullptr, nullptr, n, nV, nH, og.tile, og.stride, og.pad, (int*)nullptr);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+int reconstruct_tiles_dev(msiren_handle h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og) {
+    if (n < 0 || nV < 1 || nH < 1 || (n > 0 && (!tiles_dev || !recon_dev))) return fail(MSIREN_E_INVALID, "bad arguments");
+    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
+    if (n == 0) return 0;
+    return reconstruct_tiles(h, c, nullptr, 0, 0, nullptr, tiles_dev, n, nV, nH, recon_dev, og);
 }
 
 }  // namespace mh
@@ -732,11 +757,7 @@ extern "C" {
 int msiren_reconstruct_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev) {
     int rc = check(h);
     if (rc) return rc;
-    const Call c = dev_call(h);
-    if (n < 0 || nV < 1 || nH < 1 || (n > 0 && (!tiles_dev || !recon_dev))) return fail(MSIREN_E_INVALID, "bad arguments");
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
-    if (n == 0) return 0;
-    return reconstruct_tiles(h, c, nullptr, 0, 0, nullptr, tiles_dev, n, nV, nH, recon_dev);
+    return reconstruct_tiles_dev(h, dev_call(h), tiles_dev, n, nV, nH, recon_dev);
 }
 
 int msiren_reconstruct_slices_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev) {

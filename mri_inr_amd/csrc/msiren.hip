@@ -94,9 +94,11 @@ int profile_collect(msiren_ctx* h) {
         if (r.kernel < 0) continue;  // (the launch between the pair failed)
         float ms = 0.f;
         HIPCHK(hipEventElapsedTime(&ms, r.a, r.b));
-        h->prof_ms += ms;
-        h->prof_launches++;
         auto& k = h->prof_kernels[r.kernel];
+        if (k.trunk) {  // (the layer-0 table kernel of a sampling call is listed per kernel only)
+            h->prof_ms += ms;
+            h->prof_launches++;
+        }
         k.ms += ms;
         k.launches++;
         k.coords += r.coords;
@@ -198,6 +200,7 @@ int msiren_destroy(msiren_handle h) {
     for (auto& c : h->sc)
         if (c.s) (void)hipStreamSynchronize(c.s);
     if (h->comm) (void)comm_destroy(h);
+    drop_lattices(h);
     if (h->status_host) (void)hipHostFree((void*)h->status_host);
     if (h->ws_comm.p) (void)hipFree(h->ws_comm.p);
     if (h->d_wp16n) (void)hipFree(h->d_wp16n);
@@ -205,12 +208,12 @@ int msiren_destroy(msiren_handle h) {
     if (h->d_emc2) (void)hipFree(h->d_emc2);
     for (void* q : {h->d_woutx1, h->d_wpx1n, h->d_wpx1w, (void*)h->d_bias32x1})
         if (q) (void)hipFree(q);
-    float* ptrs[] = {h->d_dump, h->d_s0t512, h->d_s0t, h->d_bias16, h->d_wout16, h->d_grid, h->d_l0, h->d_wp, h->d_bias, h->d_wout, h->d_modw, h->d_modw_rm, h->d_modb, h->d_encw, h->d_foldw, h->d_embias};
+    float* ptrs[] = {h->d_w0raw, h->d_b0raw, h->d_dump, h->d_s0t512, h->d_s0t, h->d_bias16, h->d_wout16, h->d_grid, h->d_l0, h->d_wp, h->d_bias, h->d_wout, h->d_modw, h->d_modw_rm, h->d_modb, h->d_encw, h->d_foldw, h->d_embias};
     for (float* p : ptrs)
         if (p) (void)hipFree(p);
     std::vector<DevBuf*> bufs = {&h->ws_out, &h->ws_tiles, &h->ws_in, &h->ws_img};
     for (auto& c : h->sc)
-        for (DevBuf* b : {&c.cscratch, &c.mods, &c.modpad, &c.latent, &c.patches, &c.keep, &c.rec, &c.queue, &c.feat, &c.plan, &c.score}) bufs.push_back(b);
+        for (DevBuf* b : {&c.cscratch, &c.mods, &c.modpad, &c.latent, &c.patches, &c.keep, &c.rec, &c.queue, &c.feat, &c.plan, &c.score, &c.coords, &c.l0tab}) bufs.push_back(b);
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& pr : h->prof_events) {
@@ -253,6 +256,7 @@ int msiren_commit_weights(msiren_handle h) {
     int rc = check(h, false);
     if (rc) return rc;
     if ((rc = sync_all(h))) return rc;
+    drop_lattices(h);  // (the kept layer-0 tables of other output strides depend on net.layers.0: sample_grid.hip)
     if ((rc = pack_trunk(h))) return rc;
     if ((rc = pack_trunk_f16x3(h))) return rc;
     if ((rc = pack_trunk_x1(h))) return rc;
@@ -533,21 +537,26 @@ int msiren_forward_tiles(msiren_handle h, const float* tiles_host, int64_t B, fl
     return take_range_flag_after(h, msiren_forward_tiles_impl(h, tiles_host, B, out_host));
 }
 
-static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, float* recon_host) {
+// out_stride: 0 or inner_patch_size = the model's own output side; another: msiren_reconstruct_slices_scaled
+static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, float* recon_host,
+                                          int32_t out_stride = 0) {
     int rc = check(h);
     if (rc) return rc;
+    if (out_stride == 0) out_stride = h->I;
     if (n < 0 || (n > 0 && (!images_host || !recon_host))) return fail(MSIREN_E_INVALID, "bad arguments");
     if (n == 0) return 0;
     int32_t nV, nH;
     if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
     const size_t ni = (size_t)n * height * width * sizeof(float);
-    const size_t nr = (size_t)n * nV * h->I * nH * h->I * sizeof(float);
+    const size_t nr = (size_t)n * nV * out_stride * nH * out_stride * sizeof(float);
     if ((rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, h->ws_img, nr))) return rc;
     // As in msiren_forward_tiles: where the caller's reconstruction array is page-locked memory (the Python mirror's outputs are, by default)
     // the fold stores straight into it; the image always arrives by a copy (DMA from page-locked memory, through the runtime from pageable
     // memory): read in place every pixel would cross the link four times (32 x 32 tiles at a stride of 16; profiles/r5/09_*).
-    const Call c = make_call(h, true);
+    Call c = make_call(h, true);
     auto& sc = h->sc[c.stream];
+    OutGeom og;
+    if (out_stride != h->I && (rc = scaled_call(h, c, out_stride, &og))) return rc;
     const HostSrc src(images_host, ni);
     const HostDst dst(recon_host, nr);
     HOSTBUF_OK(src);
@@ -555,7 +564,7 @@ static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_h
     DrainOnExit drain(h);
     float* const d_rec = dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_img.p;
     HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-    if ((rc = reconstruct_slices(h, c, (const float*)h->ws_in.p, n, height, width, d_rec))) return rc;
+    if ((rc = reconstruct_slices(h, c, (const float*)h->ws_in.p, n, height, width, d_rec, out_stride != h->I ? &og : nullptr))) return rc;
     if (d_rec == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_img.p, nr, hipMemcpyDeviceToHost, sc.s));
     HIPCHK(hipStreamSynchronize(sc.s));
     drain.disarm();
@@ -566,6 +575,13 @@ static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_h
 int msiren_reconstruct_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, float* recon_host) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");
     return take_range_flag_after(h, msiren_reconstruct_slices_impl(h, images_host, n, height, width, recon_host));
+}
+
+int msiren_reconstruct_slices_scaled(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, int32_t out_stride,
+                                     float* recon_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    if (out_stride < 1) return fail(MSIREN_E_INVALID, "out_stride must be positive, got %d", out_stride);
+    return take_range_flag_after(h, msiren_reconstruct_slices_impl(h, images_host, n, height, width, recon_host, out_stride));
 }
 
 int msiren_set_streams(msiren_handle h, int32_t n) {

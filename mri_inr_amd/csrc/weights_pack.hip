@@ -117,7 +117,13 @@ int pack_trunk(msiren_ctx* h) {
     h->cg0 = (float)(-0.5 * log2e * (two_pi / h->cfg.w0_initial) * (two_pi / h->cfg.w0_initial));
     h->cg = (float)(-0.5 * log2e * (two_pi / h->cfg.w0) * (two_pi / h->cfg.w0));
 
+    // layer 0 as stored, for the layer-0 table of a call's own coordinate set (sample_grid.hip.h: the arithmetic of the host loops below)
+    std::vector<float> w0raw((size_t)HP * 2, 0.f), b0raw(HP, 0.f);
+    std::copy(W[0]->begin(), W[0]->end(), w0raw.begin());
+    if (Bv[0]) std::copy(Bv[0]->begin(), Bv[0]->end(), b0raw.begin());
+
     int rc;
+    if ((rc = upload(&h->d_w0raw, w0raw)) || (rc = upload(&h->d_b0raw, b0raw))) return rc;
     if ((rc = upload(&h->d_grid, grid))) return rc;
     if ((rc = upload(&h->d_l0, l0))) return rc;
     if ((rc = upload(&h->d_wp, wp))) return rc;
@@ -535,10 +541,9 @@ int pack_prologue_f16x3(msiren_ctx* h) {
     return 0;
 }
 
-int pack_fold_weights(msiren_ctx* h) {
-    // w[i][j] = exp(-0.1 * dist((i,j), centre)) / max   (src/util/tiling.py:67-88; fp64 maths
-    // rounded to fp32 element-wise, then divided by the fp32 maximum, as the reference does)
-    const int S = h->S;
+// w[i][j] = exp(-0.1 * dist((i,j), centre)) / max   (src/util/tiling.py:67-88; fp64 maths
+// rounded to fp32 element-wise, then divided by the fp32 maximum, as the reference does)
+std::vector<float> fold_weight_matrix(int S) {
     std::vector<float> w((size_t)S * S);
     const double c = (S - 1) / 2.0;
     float mx = 0.f;
@@ -549,7 +554,9 @@ int pack_fold_weights(msiren_ctx* h) {
             mx = std::max(mx, w[(size_t)i * S + j]);
         }
     for (auto& v : w) v = v / mx;
-    return upload(&h->d_foldw, w);
+    return w;
 }
+
+int pack_fold_weights(msiren_ctx* h) { return upload(&h->d_foldw, fold_weight_matrix(h->S)); }
 
 }  // namespace mh

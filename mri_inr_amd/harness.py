@@ -175,9 +175,11 @@ def patches_to_image_weighted_average(patches, image_information, patch_size, in
     return d_o.numpy() if host else d_o
 
 
-def reconstruct_from_patches(model, undersampled, img_information):
+def reconstruct_from_patches(model, undersampled, img_information, out_stride=None):
     """filter_and_remember_black_patches -> model -> reintegrate_black_patches -> patches_to_image_weighted_average
-    (error.py:229-249): (n*nV*nH, O, O) tiles -> (n, nV*I, nH*I), one device call (msiren_reconstruct_tiles_dev)."""
+    (error.py:229-249): (n*nV*nH, O, O) tiles -> (n, nV*I, nH*I), one device call (msiren_reconstruct_tiles_dev).
+    ``out_stride`` (build-defined): the output side at stride I' instead of I -> (n, nV*I', nH*I')
+    (msiren_reconstruct_tiles_scaled_dev)."""
     model._ensure_committed()
     d_t, host = _to_device(model, undersampled, 3)
     nv, nh = img_information[0]
@@ -185,8 +187,14 @@ def reconstruct_from_patches(model, undersampled, img_information):
     O = model.outer_patch_size
     if d_t.shape != (n * nv * nh, O, O):  # (the device call reads O x O floats per tile)
         raise ValueError(f"tiles {d_t.shape} do not match image_information {img_information[0]} / {O}x{O} tiles")
-    d_o = model.device_array((n, nv * model.inner_patch_size, nh * model.inner_patch_size))
-    _lib.check(model._lib.msiren_reconstruct_tiles_dev(model._h, d_t.ptr, n, nv, nh, d_o.ptr))
+    if out_stride is None:
+        d_o = model.device_array((n, nv * model.inner_patch_size, nh * model.inner_patch_size))
+        _lib.check(model._lib.msiren_reconstruct_tiles_dev(model._h, d_t.ptr, n, nv, nh, d_o.ptr))
+    else:
+        out_stride = int(out_stride)
+        model._upsampled_geometry(out_stride)  # (ValueError before anything is allocated)
+        d_o = model.device_array((n, nv * out_stride, nh * out_stride))
+        _lib.check(model._lib.msiren_reconstruct_tiles_scaled_dev(model._h, d_t.ptr, n, nv, nh, out_stride, d_o.ptr))
     model.sync()
     return d_o.numpy() if host else d_o
 

@@ -517,13 +517,123 @@ class ModulatedSiren:
             c = coords.detach().cpu().numpy() if _is_torch(coords) else np.asarray(coords)
             g = np.asarray(self.grid, dtype=np.float32)
             if c.shape[-2:] != g.shape or not np.array_equal(np.broadcast_to(g, c.shape), c.astype(np.float32)):
-                raise ValueError("net(coords, mods): the trunk evaluates the model's own grid only (pass coords=None or model.grid repeated over the batch)")
+                raise ValueError("net(coords, mods): the trunk evaluates the model's own grid only (pass coords=None or model.grid repeated over "
+                                 "the batch); sample_mods(mods, coords) evaluates one coordinate set (Q, 2) shared by the batch")
         out = self.forward_mods(mods)
         return out.reshape(out.shape[0], -1, 1)
 
-    def reconstruct(self, images):
+    # ---- the representation off its own grid: caller-chosen coordinates, other output resolutions ----
+    def _sample(self, host_fn, dev_fn, x, coords, in_tail, batch_axis):
+        """Marshalling of sample / sample_mods: ``x`` as in _run (numpy / torch / DeviceArray), ``coords`` (Q, 2) as numpy, torch or a
+        DeviceArray.  A DeviceArray or device tensor on either side takes the *_dev entry point (the other side is uploaded)."""
+        self._ensure_committed()
+        x_t, c_t = _is_torch(x), _is_torch(coords)
+        cshape = tuple(coords.shape)
+        if len(cshape) != 2 or cshape[1] != 2:
+            raise ValueError(f"expected coords of shape (Q, 2), got {cshape}")
+        Q = cshape[0]
+        if not 1 <= Q <= 65536:
+            raise ValueError(f"the number of coordinates must be in [1, 65536], got {Q}")
+        x_dev = isinstance(x, DeviceArray) or (x_t and x.is_cuda)
+        c_dev = isinstance(coords, DeviceArray) or (c_t and coords.is_cuda)
+        keep = []  # device arrays of this call stay alive until the sync below
+
+        def host_array(a):
+            return np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float32)
+
+        def dev_ptr(a):
+            if isinstance(a, DeviceArray):
+                return a.ptr
+            if _is_torch(a) and a.is_cuda:
+                import torch
+
+                if a.device.index != self._device:
+                    raise ValueError(f"input is on cuda:{a.device.index}, model on cuda:{self._device}")
+                t = a.detach().to(torch.float32).contiguous()
+                torch.cuda.current_stream(a.device).synchronize()
+                keep.append(t)
+                return t.data_ptr()
+            h = host_array(a)
+            d = self.device_array(h.shape).copy_from(h)
+            keep.append(d)
+            return d.ptr
+
+        self._check_tail(tuple(x.shape), in_tail)
+        B = int(x.shape[batch_axis])
+        if not (x_dev or c_dev):
+            a, c = host_array(x), host_array(coords)
+            out = self._pinned.array((B, Q), strict=False) if self._pin_outputs and B else None
+            if out is None:
+                out = np.empty((B, Q), dtype=np.float32)
+            _lib.check(host_fn(self._h, c.ctypes.data, Q, a.ctypes.data if a.size else None, B, out.ctypes.data if out.size else None))
+            if x_t:
+                import torch
+
+                return torch.from_numpy(out)
+            return out
+        if x_t and x.is_cuda:
+            import torch
+
+            out = torch.empty((B, Q), dtype=torch.float32, device=x.device)
+            out_ptr = out.data_ptr()
+        else:
+            out = self.device_array((B, Q))
+            out_ptr = out.ptr
+        _lib.check(dev_fn(self._h, dev_ptr(coords), Q, dev_ptr(x) if B else None, B, out_ptr if B else None))
+        _lib.check(self._lib.msiren_sync(self._h))
+        if isinstance(x, DeviceArray) or (x_t and x.is_cuda):
+            return out
+        res = out.numpy()  # x came from the host, only the coordinates live on the device
+        if x_t:
+            import torch
+
+            return torch.from_numpy(res)
+        return res
+
+    def sample(self, tiles, coords):
+        """tiles (B, O, O), coords (Q, 2) -> (B, Q): ``ModulatedSiren.forward`` with the trunk evaluated at ``coords`` instead of the
+        model's grid -- ``net(coords, modulator(encoder(tiles)))`` of the reference (modulated_siren.py:435-457, 215-233), one coordinate
+        set shared by the batch.  Column 0 of ``coords`` is the row coordinate, as in ``model.grid``."""
+        if self.encoder_type != "custom":
+            raise AttributeError("'Encoder' object has no attribute 'encoder'")  # as the reference fails
+        O = self.outer_patch_size
+        self._ensure_handle()
+        return self._sample(self._lib.msiren_sample_tiles, self._lib.msiren_sample_tiles_dev, tiles, coords, (None, O, O), 0)
+
+    def sample_mods(self, mods, coords):
+        """mods (L, B, H) (or the Modulator's tuple), coords (Q, 2) -> (B, Q): ``SirenNet.forward(coords, mods)``
+        (modulated_siren.py:215-233) for one coordinate set shared by the batch."""
+        if isinstance(mods, (tuple, list)):
+            if _is_torch(mods[0]):
+                import torch
+
+                mods = torch.stack(list(mods), 0)
+            else:
+                mods = np.stack([np.asarray(m) for m in mods], 0)
+        self._ensure_handle()
+        return self._sample(self._lib.msiren_sample_mods, self._lib.msiren_sample_mods_dev, mods, coords,
+                            (self.num_layers, None, self.dim_hidden), 1)
+
+    def _upsampled_geometry(self, out_stride):
+        """(S', pad') of an output stride I': output tile S' = S I'/I and fold padding (S' - I')/2 (msiren_upsampled_geometry; no device).
+        ValueError where they are not integers."""
+        lib = _lib.load()
+        tile, pad = C.c_int32(), C.c_int32()
+        _lib.check(lib.msiren_upsampled_geometry(self.siren_patch_size, self.inner_patch_size, int(out_stride), C.byref(tile), C.byref(pad)))
+        return tile.value, pad.value
+
+    def upsampled_grid(self, out_stride) -> np.ndarray:
+        """(S'*S', 2) float32: the pixel centres of a tile at output stride I', in ``indexing="ij"`` order like ``model.grid`` (built from
+        msiren_upsampled_lattice; no device).  ``sample(tiles, upsampled_grid(I'))`` is the trunk step of ``reconstruct(.., out_stride=I')``."""
+        tile, _ = self._upsampled_geometry(out_stride)
+        lin = np.empty(tile, dtype=np.float32)
+        _lib.check(_lib.load().msiren_upsampled_lattice(self.siren_patch_size, self.inner_patch_size, int(out_stride), lin.ctypes.data))
+        return np.stack(np.meshgrid(lin, lin, indexing="ij"), axis=-1).reshape(tile * tile, 2)
+
+    def reconstruct(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (n, nV*I, nH*I): the whole slice pipeline of
-        metrics_error (src/util/error.py:231-249) on the device."""
+        metrics_error (src/util/error.py:231-249) on the device.  ``out_stride`` (build-defined): the same
+        tiles evaluated and folded at output stride I' -> (n, nV*I', nH*I'); I' = 2 I doubles the resolution."""
         self._ensure_committed()
         a = images.detach().cpu().numpy() if _is_torch(images) else np.asarray(images)
         a = np.ascontiguousarray(a, dtype=np.float32)
@@ -535,11 +645,16 @@ class ModulatedSiren:
         n, Hh, Ww = a.shape
         nv, nh = C.c_int32(), C.c_int32()
         _lib.check(self._lib.msiren_recon_shape(self._h, Hh, Ww, C.byref(nv), C.byref(nh)))
-        I = self.inner_patch_size
+        I = self.inner_patch_size if out_stride is None else int(out_stride)
+        if out_stride is not None:
+            self._upsampled_geometry(I)  # (ValueError before anything is allocated)
         out = self._pinned.array((n, nv.value * I, nh.value * I), strict=False) if self._pin_outputs and n else None
         if out is None:
             out = np.empty((n, nv.value * I, nh.value * I), dtype=np.float32)
-        _lib.check(self._lib.msiren_reconstruct_slices(self._h, a.ctypes.data, n, Hh, Ww, out.ctypes.data))
+        if out_stride is None:
+            _lib.check(self._lib.msiren_reconstruct_slices(self._h, a.ctypes.data, n, Hh, Ww, out.ctypes.data))
+        else:
+            _lib.check(self._lib.msiren_reconstruct_slices_scaled(self._h, a.ctypes.data, n, Hh, Ww, I, out.ctypes.data))
         res = out[0] if single else out
         if _is_torch(images):
             import torch
