@@ -65,9 +65,9 @@ struct CallMode {
 // ---- trunk -------------------------------------------------------------------------------------------------------------------
 // what follows a 16-bit trunk launch when a scaled modulation leaves the fp16 domain
 enum class Guard : int {
-    none,      // bf16: fp32's exponent range
+    none,      // the exact-fp32 trunk: nothing to guard
     f32_cond,  // siren_trunk_f32_cond_kernel<ACT> behind it on the same stream (conditional: leaves unless flagged)
-    f32_512,   // fp16 at H = 512: siren_trunk_f32_kernel<512,ACT,RES> as the conditional launch
+    f32_512,   // fp16 and bf16 at H = 512 (both read an fp16 modulation table): siren_trunk_f32_kernel<512,ACT,RES> as the conditional launch
     host,      // the flag in host memory, read by the call after its wait (no launch)
 };
 struct TrunkPick {
@@ -98,7 +98,7 @@ inline TrunkPick pick_trunk(const DispatchHandle& d, const CallMode& m, int64_t 
         //  the half-empty last round -- 111.2 against 109.3 Mpixel/s, profiles/r4/09_*)
         t.balanced = d.L >= 3 && m.alone();
         t.inst = d.L >= 3 ? instance(Kernel::x1w, bf, act, res) : instance(Kernel::x1n, bf, act, res, 3);
-        t.guard = bf ? Guard::none : Guard::f32_512;
+        t.guard = Guard::f32_512;
         return t;
     }
     if (!use_f16x3(d)) {

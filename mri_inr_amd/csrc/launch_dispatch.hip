@@ -283,7 +283,7 @@ static int launch_trunk_x1(msiren_ctx* h, const Call& c, const msiren::TrunkPick
     }
     int rc = queue_for_launch(h, c.stream, npasses, &p.pass_counter, &p.pass_base);
     if (rc) return rc;
-    p.status = p.pass_counter + 16;  // the stream's flag word, behind the pass counter's line (fp16 operands: the domain guard)
+    p.status = p.pass_counter + 16;  // the stream's flag word, behind the pass counter's line (the domain guard of the fp16 modulation table)
     p.status_val = (int)h->range_epoch;
     const int lds = ws ? msiren::X1wLds::total(h->L) : msiren::X1nLds<3>::total(h->L);
     return queue_launched(h, c.stream, launch(h, c.stream, t.inst, grid, lds, p, true));

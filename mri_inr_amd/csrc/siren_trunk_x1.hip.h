@@ -5,7 +5,9 @@
 // The reference's residual model lives on a branch that is not in the container (README.md:27-29),
 // so the residual semantics are this build's own and PARITY IS UNPINNED against the reference:
 //     x_{l+1} = x_l + mod_l * act(W_l x_l + b_l)   for l >= 1      (layer 0 and last_layer unchanged)
-// (oracle/siren_oracle.py: siren_forward(residual=True)); the tolerance is the 16-bit format's, not 1e-4.
+// (oracle/siren_oracle.py: siren_forward(residual=True)).  Against that fp64 oracle the distance is the 16-bit format's, not 1e-4;
+// against the same arithmetic with the operands rounded where this header and pack_trunk_x1 round them (oracle/x1_oracle.py) it is
+// the accumulation order's and the hardware sine's: tests/test_gpu_x1.py gates every instance at 4 x that floor.
 //
 // (Round 1's kernel on 32x32x16 tiles, which this header used to hold, was kept as a record under tools/experiments/ until round 6 (commit 27d6e80 has it); same-box
 // A/B against its successor: profiles/r4/04_config5_x1n_vs_x1_ab.txt.)
@@ -35,9 +37,10 @@ struct TrunkX1Params {
     const int* plan;          // optional (compact_flags_kernel): the unit count is plan[1] (<= total_units)
     int* pass_counter;        // work queue (never reset: the host passes the value it holds at launch)
     unsigned pass_base;
-    // fp16 operands only (BF = 0): a launch that stores a non-finite output writes its own number to *status -- an activation,
-    // a modulation or a residual sum beyond fp16's 65 504 became inf, and inf is NaN one sine later, where the reference's fp32
-    // stays finite; the conditional exact-fp32 launch behind it (siren_trunk_f32_kernel with p.cond) then redoes the batch
+    // A launch that stores a non-finite output writes its own number to *status -- fp16 operands: an activation, a modulation or
+    // a residual sum beyond fp16's 65 504 became inf; bf16 operands: a modulation did (the modulation table in LDS is fp16 in
+    // both) -- and inf is NaN one sine later, where the reference's fp32 stays finite; the conditional exact-fp32 launch behind
+    // it (siren_trunk_f32_kernel with p.cond) then redoes the batch
     int* status;
     int status_val;
 };

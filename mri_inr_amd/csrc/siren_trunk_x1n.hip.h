@@ -8,7 +8,9 @@
 //     this shape at the same bytes per FLOP (1.78-1.81 vs 1.48 PFLOP/s on the bare MFMA streams, DESIGN.md sections 4.2, 8);
 //   * a thinner epilogue: the bias (fp32, in revolutions) enters as the C operand of a tile's first MFMAs, so the
 //     accumulator IS the sine argument (bf16 weights carry no power-of-two scale; the fp16 instance keeps one multiply);
-//     activation x modulation + residual is ONE v_fma_mix (fp16 modulation table read as the mixed operand).
+//     activation x modulation + residual is ONE v_fma_mix (fp16 modulation table read as the mixed operand) for tiles 0..14 of a
+//     layer; the layer's last tile, finished in the next layer's "pending" slot, rounds twice: fmaf(x, rf, fp32(s * m)), rf = 0
+//     for layer 0's tile (epi_half, !steady) -- one fp32 ulp in front of the 16-bit rounding.
 // Data flow unchanged: a wave owns one UNIT = 32 coordinates of one patch (two column groups of 16) through all layers with
 // its activations in AGPRs -- B fragment [2 s + g], element j = feature 32 s + 16 (j >> 2) + 4 q + (j & 3) at the lane's
 // coordinate of group g: the four accumulator registers of the two 16-feature sub-tiles of a 32-feature tile, so a tile's
@@ -434,9 +436,8 @@ __global__ __launch_bounds__(256, 1) void siren_trunk_x1n_kernel(TrunkX1Params p
             const float o_ = sin_rev(sv + p.bout);
             if (q < 2 && pv) {
                 p.out[(size_t)b * p.P + pc] = o_;
-                if constexpr (!BF) {
-                    if (!(__builtin_fabsf(o_) <= 2.f) && p.status) *p.status = p.status_val;  // NaN: the fp16 domain was left (or the input was NaN)
-                }
+                // NaN: the fp16 domain was left (or the input was NaN) -- bf16 operands too: their modulation table is fp16
+                if (!(__builtin_fabsf(o_) <= 2.f) && p.status) *p.status = p.status_val;
             }
         }
         cur_pass = __builtin_amdgcn_readfirstlane(qslot[(pass + 1) & 1]);

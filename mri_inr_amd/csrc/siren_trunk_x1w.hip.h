@@ -569,9 +569,8 @@ __global__ __launch_bounds__(256, 1) void siren_trunk_x1w_kernel(TrunkX1Params p
             const float o_ = sin_rev(s + p.bout);
             if (lv && cu + c < P) {
                 p.out[(size_t)pu * P + cu + c] = o_;
-                if constexpr (!BF) {
-                    if (!(__builtin_fabsf(o_) <= 2.f) && p.status) *p.status = p.status_val;  // NaN: the fp16 domain was left (or the input was NaN)
-                }
+                // NaN: the fp16 domain was left (or the input was NaN) -- bf16 operands too: their modulation table is fp16
+                if (!(__builtin_fabsf(o_) <= 2.f) && p.status) *p.status = p.status_val;
             }
         }
         cur_pass = __builtin_amdgcn_readfirstlane(qslot[pass & 1]);

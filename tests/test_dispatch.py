@@ -169,7 +169,7 @@ PROG = textwrap.dedent(r"""
         }
 
         // bf16 / f16, H = 512: weight-stationary for L >= 3 (the balanced grid when nothing runs beside it), x1n<...,3> at L = 2;
-        // f16 has the conditional f32<512> behind it
+        // both have the conditional f32<512> behind them (bf16 too: its modulation table in LDS is fp16)
         for (int prec : {MSIREN_PREC_BF16, MSIREN_PREC_F16})
             for (int act : {0, 1})
                 for (int res : {0, 1}) {
@@ -177,7 +177,7 @@ PROG = textwrap.dedent(r"""
                     char w[64], n[64];
                     std::snprintf(w, 64, "siren_trunk_x1w_kernel<%d,%d,%d>", bf, act, res);
                     std::snprintf(n, 64, "siren_trunk_x1n_kernel<%d,%d,%d,3>", bf, act, res);
-                    const Guard g = bf ? Guard::none : Guard::f32_512;
+                    const Guard g = Guard::f32_512;
                     for (int L : {3, 5, 10}) {
                         const DispatchHandle d = x1(prec, L, act ? MSIREN_ACT_MORLET : MSIREN_ACT_SINE, res);
                         TrunkPick t = pick_trunk(d, dev(1), 400);
