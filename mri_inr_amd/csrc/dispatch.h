@@ -118,7 +118,8 @@ inline TrunkPick pick_trunk(const DispatchHandle& d, const CallMode& m, int64_t 
     }
     // R = 3 leaves ~35 KB of LDS per CU free, enough for an encoder / modulator workgroup of the NEXT call (other stream) to run
     // beside the persistent trunk workgroup; R = 4 fills the CU.  Depths other than 5 run the loop form of the kernel: with a ring of 3
-    // hipcc gives it all 512 registers (and scratch), so nothing could run beside it anyway -- the ring of 4 has neither.
+    // hipcc gives it all 512 registers (and scratch), so nothing could run beside it anyway -- the ring of 4 has neither.  The ring of 4
+    // fits the LDS up to L = 5 only, so depths 6..11 run the ring-of-3 loop form in every mode (L = 2..4: the ring of 4).
     const bool room = !m.alone() || m.trunk == 1;
     t.ring = (!room || d.L != 5) && d.f16_ring4_fits ? 4 : 3;
     t.inst = t.half ? instance(Kernel::f16x3h, act, t.ring, 5) : instance(Kernel::f16x3n, act, t.ring, d.L == 5 ? 5 : 0);

@@ -44,6 +44,9 @@ void describe_for_dispatch(msiren_ctx* h) {
     d.act = h->cfg.activation, d.res = h->cfg.residual, d.num_cus = h->num_cus;
     d.f16x3_ready = h->f16x3_ready, d.x1_ready = h->x1_ready, d.em_enc = h->em_enc, d.em_mod = h->em_mod;
     static_assert(msiren::WsLds<4>::total(msiren::WS_MAX_L) <= 160 * 1024, "unit images + tables of the deepest supported model must fit the LDS");
+    // the depths at which each ring stops fitting (tests/test_dispatch.py and tests/trunk_cases.py model the two flags below by them)
+    static_assert(msiren::F16Lds<4>::total(5) <= 160 * 1024 && msiren::F16Lds<4>::total(6) > 160 * 1024, "ring of 4: num_layers <= 5");
+    static_assert(msiren::F16Lds<3>::total(11) <= 160 * 1024 && msiren::F16Lds<3>::total(12) > 160 * 1024, "ring of 3: num_layers <= 11");
     d.f16_ring3_fits = msiren::F16Lds<3>::total(h->L) <= 160 * 1024;
     d.f16_ring4_fits = msiren::F16Lds<4>::total(h->L) <= 160 * 1024;
     d.ws_depth_ok = h->L >= msiren::WS_MIN_L && h->L <= msiren::WS_MAX_L;

@@ -26,12 +26,13 @@ PROG = textwrap.dedent(r"""
         return false;
     }
 
-    // a committed handle as msiren_commit_weights describes it (LDS facts: F16Lds<4> fits up to L = 11, WS_MIN_L = 3, WS_MAX_L = 5)
+    // a committed handle as msiren_commit_weights describes it (LDS facts, pinned by static_assert in
+    // launch_dispatch.hip: F16Lds<4> fits up to L = 5, F16Lds<3> up to L = 11; WS_MIN_L = 3, WS_MAX_L = 5)
     static DispatchHandle f16x3(int L, int act = MSIREN_ACT_SINE) {
         DispatchHandle d;
         d.precision = MSIREN_PREC_F16X3; d.H = d.HP = 256; d.L = L; d.Z = 256; d.P = 24 * 24; d.act = act; d.num_cus = 256;
         d.f16x3_ready = d.em_enc = d.em_mod = true;
-        d.f16_ring3_fits = true; d.f16_ring4_fits = L <= 11; d.ws_depth_ok = L >= 3 && L <= 5;
+        d.f16_ring3_fits = L <= 11; d.f16_ring4_fits = L <= 5; d.ws_depth_ok = L >= 3 && L <= 5;
         return d;
     }
     static DispatchHandle fp32(int H, int act, int res) {
@@ -127,13 +128,19 @@ PROG = textwrap.dedent(r"""
                 assert(is(pick_trunk(f16x3(L, A), dev(1), 400).inst, w4));
                 assert(is(pick_trunk(f16x3(L, A), dev(1), 28).inst, w4));  // (no half-unit instance below depth 5)
             }
-            // L = 2 or 6...11: loop form, ring of 4 -- ring of 3 where 4 does not fit the LDS
-            for (int L : {2, 6, 8, 11}) {
-                for (CallMode m : {dev(1), dev(2), sync(2)}) assert(is(pick_trunk(f16x3(L, A), m, 400).inst, n40));
-                DispatchHandle big = f16x3(L, A);
-                big.f16_ring4_fits = false;
-                t = pick_trunk(big, dev(1), 400);
-                assert(is(t.inst, n30) && t.ring == 3);
+            // L = 2: loop form with the ring of 4 in every mode; L = 6...11: the ring of 4 does not fit the LDS, loop form with the ring of 3
+            for (CallMode m : {dev(1), dev(2), sync(2)}) {
+                t = pick_trunk(f16x3(2, A), m, 400);
+                assert(is(t.inst, n40) && t.ring == 4);
+                for (int L : {6, 8, 11}) {
+                    t = pick_trunk(f16x3(L, A), m, 400);
+                    assert(is(t.inst, n30) && t.ring == 3 && !t.half);
+                }
+            }
+            {   // (the flag alone decides: a depth whose ring of 4 did fit would run it)
+                DispatchHandle fits = f16x3(6, A);
+                fits.f16_ring4_fits = true;
+                assert(is(pick_trunk(fits, dev(1), 400).inst, n40));
             }
             // a pipelined host call's chunks: trunk 1 -> register-resident with room beside it, trunk 2 -> weight-stationary
             CallMode chunk = sync(2);

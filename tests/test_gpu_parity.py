@@ -399,8 +399,9 @@ def test_f16x3_full_forward_matches_fp32_path():
 @pytest.mark.gpu
 @pytest.mark.parametrize("L", [3, 4, 6])
 def test_two_streams_at_other_depths_same_bits_as_one_stream(L):
-    """Depths other than 5 run the loop form of the register-resident trunk in two-stream mode (with the ring of 4: the ring-of-3
-    instance of that form spills); one stream: the weight-stationary trunk (3..5) or the same loop form.  Same bits."""
+    """Depths other than 5 run the loop form of the register-resident trunk in two-stream mode (3 and 4 with the ring of 4; from 6
+    layers on the ring of 4 does not fit the LDS and the ring of 3 runs in every mode); one stream: the weight-stationary trunk
+    (3..5) or the same loop form.  Same bits."""
     from mri_inr_amd import _lib
 
     sd = syn.make_state_dict(seed=5, num_layers=L, trained_like=True)

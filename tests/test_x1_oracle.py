@@ -122,12 +122,15 @@ def test_every_instance_and_every_deep_layer_has_a_case():
         assert {c.isolate for c in xc.ISOLATED if c.fmt == f and c.act == "morlet"} == {1, 9}
     assert {c.S * c.S for c in xc.SHAPES} == {49, 100, 576, 1089} and {c.B for c in xc.SHAPES} == {1, 2, 7, 57}
     assert all(c.res and c.L == 10 and c.kernel.startswith("siren_trunk_x1w") for c in xc.ISOLATED)
+    # the middle hidden layer of the four instances without the residual: three layers, errors seeded into layer 1
+    assert {c.kernel for c in xc.MIDDLE} == {f"siren_trunk_x1w_kernel<{b},{a},0>" for b in (0, 1) for a in (0, 1)}
+    assert all(c.L == 3 and not c.res and c.B == 9 and c.S == 24 and xc.seeded_layer(c) == 1 and c.caps == xc.CAP_SHALLOW for c in xc.MIDDLE)
     for c in xc.ISOLATED:  # the isolation is exact: every other hidden layer's modulation row is zero
         m = xc.mods(c)
         assert all((m[l] == 0).all() == (l not in (0, c.isolate)) for l in range(c.L))
 
 
-@pytest.mark.parametrize("c", xc.END_TO_END + xc.ISOLATED, ids=lambda c: c.id)
+@pytest.mark.parametrize("c", xc.END_TO_END + xc.ISOLATED + xc.MIDDLE, ids=lambda c: c.id)
 def test_seeded_errors_land_outside_the_gate(c):
     """Each error goes into ONE hidden layer of the restatement (x1_cases.seeded_errors) on the inputs the GPU file uses.
 

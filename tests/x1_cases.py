@@ -46,6 +46,7 @@ class Case:
     mod_scale: float = 1.0   # the U(0.1, 0.6) modulations times this
     sd_seed: int = 21
     mod_seed: int = 8
+    seed_layer: int = 0      # l > 0: the hidden layer seeded_errors puts its errors into (0: seeded_layer's rule)
 
     @property
     def id(self) -> str:
@@ -156,7 +157,13 @@ OPTIONS = ([Case(fmt=f, L=4, use_bias=False, mod_scale=0.25) for f in FMTS]
 # modulation magnitudes inside the fp16 table's range: 1e-4 .. 6e-4, 10 .. 60, 3e3 .. 1.8e4 (fp16 normals: 6.1e-5 .. 65 504)
 MAGNITUDES = [Case(fmt=f, L=L, mod_scale=s) for f in FMTS for L in (3, 10) for s in (1e-3, 1e2, 3e4)]
 
-GATED = END_TO_END + ISOLATED + SHAPES + OPTIONS + MAGNITUDES
+# The four RES = 0 weight-stationary instances with a MIDDLE hidden layer between the input and the output: three layers without
+# the residual.  In the ten-layer end-to-end cases without the residual every later layer attenuates what a middle layer got wrong
+# and the isolated-layer cases need the residual, so nothing else gates a wrong fragment or rounding in a middle layer of these
+# instances; here layer 1 is one attenuating layer away from the output, at a floor of ~2e-4.  Errors are seeded into layer 1.
+MIDDLE = [Case(fmt=f, act=a, res=False, L=3, seed_layer=1) for f in FMTS for a in ("sine", "morlet")]
+
+GATED = END_TO_END + ISOLATED + SHAPES + OPTIONS + MAGNITUDES + MIDDLE
 
 
 # ---- seeded errors (test-only hooks of x1_forward): what the gate has to catch ----------------------------------------------------
@@ -164,6 +171,8 @@ def seeded_layer(c: Case) -> int:
     """The hidden layer that takes the error: the one an isolated case isolates; end to end the LAST hidden layer -- without the
     residual every later layer attenuates a perturbation (|m| |W| < 1 for U(0.1, 0.6) modulations), so an error further up says
     less about the gate than about the model, and the layers further up are what the isolated cases are for."""
+    if c.seed_layer:   # (the three-layer cases without the residual: the middle hidden layer)
+        return c.seed_layer
     return c.isolate if c.isolate else c.L - 1
 
 
