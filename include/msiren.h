@@ -33,12 +33,13 @@
 extern "C" {
 #endif
 
-/* 4: msiren_sample_* (the trunk at caller-chosen coordinates), msiren_upsampled_geometry / _lattice and the *_scaled slice pipeline
+/* 5: msiren_encode_modulate_tiles(_dev) (the prologue of msiren_forward_tiles alone) and msiren_last_prologue_kernel added.
+ * 4: msiren_sample_* (the trunk at caller-chosen coordinates), msiren_upsampled_geometry / _lattice and the *_scaled slice pipeline
  * (another output stride) added.  3 (round 6): msiren_runtime_info, msiren_host_range_kind added; the large-call split (MSIREN_SPLIT_MIN) and the per-call page-locking of
  * caller buffers (MSIREN_HOST_REGISTER) left the library.  2 (round 5): msiren_chain_* gone, msiren_profile_read_kernel /
  * msiren_last_trunk_kernel / msiren_device_pci added; sync no longer returns MSIREN_E_RANGE.  A library of another number refuses
  * msiren_create. */
-#define MSIREN_ABI_VERSION 4
+#define MSIREN_ABI_VERSION 5
 
 #if defined(__GNUC__)
 #define MSIREN_API __attribute__((visibility("default")))
@@ -170,6 +171,13 @@ MSIREN_API int msiren_encode_tiles(msiren_handle h, const float* tiles_host, int
 MSIREN_API int msiren_encode_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, float* latent_dev);
 MSIREN_API int msiren_modulate(msiren_handle h, const float* latent_host, int64_t B, float* mods_host);
 MSIREN_API int msiren_modulate_dev(msiren_handle h, const float* latent_dev, int64_t B, float* mods_dev);
+/* The prologue of msiren_forward_tiles(_dev) and nothing else: tiles (B, O, O) -> modulations (L, B, H), by the very launches that call
+ * makes in front of its trunk (on a 16-bit handle ONE latent_mods launch in which the latent never leaves the workgroup, with the ring
+ * depth and the prefetch workgroups the call's mode -- streams, synchronous or not, batch size, the chunks of a large host call -- gives
+ * it; on an fp32 handle the per-layer launches).  `latent` may be NULL; otherwise the latent (B, Z) is stored as well.
+ * msiren_forward_mods of these modulations == msiren_forward_tiles, bit for bit. */
+MSIREN_API int msiren_encode_modulate_tiles(msiren_handle h, const float* tiles_host, int64_t B, float* latent_host, float* mods_host);
+MSIREN_API int msiren_encode_modulate_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, float* latent_dev, float* mods_dev);
 /* ModulatedSiren.forward (modulated_siren.py:435-457), custom-encoder branch
  * (siren_encoder.py:503-512,565-577): tiles (B,O,O) -> out (B,S,S). */
 MSIREN_API int msiren_forward_tiles(msiren_handle h, const float* tiles_host, int64_t B, float* out_host);
@@ -344,6 +352,9 @@ MSIREN_API int msiren_profile_read(msiren_handle h, int64_t* launches, double* t
 MSIREN_API int msiren_profile_read_kernel(msiren_handle h, int32_t index, char* name128, int64_t* launches, double* ms_total,
                                           int64_t* coords_total);
 MSIREN_API int msiren_last_trunk_kernel(msiren_handle h, char* name128);
+/* The one-launch prologue's counterpart: the instance of the handle's most recent latent_mods launch, e.g.
+ * "latent_mods_f16x3_kernel<2,2,8,3>" (<NPH,NPZ,DEPTH,MODE>); empty behind the per-layer exact-fp32 launches (and before any). */
+MSIREN_API int msiren_last_prologue_kernel(msiren_handle h, char* name128);
 
 /* name (<=255 chars + NUL), compute units, clock in MHz, total HBM bytes of the handle's device. */
 MSIREN_API int msiren_device_info(msiren_handle h, char* name256, int32_t* compute_units, int32_t* clock_mhz,

@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MSIREN_LIB") or os.path.join(_HERE, "libmsiren.so")  # MSIREN_LIB: A/B builds
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "msiren.h")
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 ACT_SINE, ACT_MORLET = 0, 1
 PREC_F32, PREC_BF16, PREC_F16X3, PREC_F16 = 0, 1, 2, 3
 E_INVALID, E_STATE, E_SHAPE, E_HIP, E_NOMEM, E_RANGE = -1, -2, -3, -4, -5, -6
@@ -70,6 +70,8 @@ PROTOTYPES = {
     "msiren_encode_tiles_dev": (C.c_int, [_vp, _vp, _i64, _vp]),
     "msiren_modulate": (C.c_int, [_vp, _vp, _i64, _vp]),
     "msiren_modulate_dev": (C.c_int, [_vp, _vp, _i64, _vp]),
+    "msiren_encode_modulate_tiles": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "msiren_encode_modulate_tiles_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "msiren_forward_latent": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "msiren_forward_latent_dev": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "msiren_forward_tiles": (C.c_int, [_vp, _vp, _i64, _vp]),
@@ -112,6 +114,7 @@ PROTOTYPES = {
     "msiren_profile_read": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(C.c_double)]),
     "msiren_profile_read_kernel": (C.c_int, [_vp, _i32, C.c_char_p, C.POINTER(_i64), C.POINTER(C.c_double), C.POINTER(_i64)]),
     "msiren_last_trunk_kernel": (C.c_int, [_vp, C.c_char_p]),
+    "msiren_last_prologue_kernel": (C.c_int, [_vp, C.c_char_p]),
     "msiren_device_info": (C.c_int, [_vp, C.c_char_p, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(C.c_uint64)]),
     "msiren_device_pci": (C.c_int, [_vp, C.c_char_p]),
     "msiren_flops_per_coord": (C.c_int, [_vp, C.POINTER(C.c_double)]),

@@ -12,7 +12,8 @@
 // (22 significant bits), a product is W_lo x_hi + W_hi x_lo + W_hi x_hi on v_mfma_f32_16x16x32_f16, fp32 accumulation.
 // Unlike the trunk's activations (|sin| <= 1) these operands have no natural range -- fastMRI intensities are ~1e-5, conv
 // features and modulations follow -- so both sides are scaled by exact powers of two first:
-//   * weights: per layer, max|W| -> [2^13, 2^14) (host, once);
+//   * weights: per layer, max|W| -> [2^13, 2^14) (host, once); the latent part and the hidden part of a Modulator layer each by its own
+//     power of two (two GEMMs, see below);
 //   * inputs: PER ROW, max_k |x[row][k]| -> [2^13, 2^14), computed where the row is produced (a row never sees another row's
 //     scale: an output does not depend on the batch it came in);
 //   * the accumulator is multiplied back by 2^-(a + s) (exact) before bias and activation.

@@ -71,6 +71,7 @@ struct msiren_ctx {
     int cur = 0, nstreams = 1;  // cur: the stream the next asynchronous (*_dev) call takes (next_stream rotates it)
     msiren::DispatchHandle dh;  // what dispatch.h reads of this handle: the knobs from msiren_create, the rest from msiren_commit_weights
     const char* last_trunk = "";  // name of the trunk instance launched last (msiren_last_trunk_kernel; msiren::kInstances)
+    const char* last_prologue = "";  // name of the latent_mods instance launched last, "" behind the per-layer fp32 launches (msiren_last_prologue_kernel)
     struct { const void* k = nullptr; int bytes = 0; } lds_set[8];  // the dynamic-LDS limit raised per kernel (launch_dispatch.hip: launch)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::map<std::string, std::vector<float>> tensors;  // state_dict, host copies
@@ -204,6 +205,7 @@ int launch_trunk(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B,
 int launch_trunk_f32_cond(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev, const int* flag_word = nullptr, unsigned flag_val = 0);
 int launch_modulator(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* mods_dev);
 int launch_encoder(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev);
+int encode_modulate_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev, float* mods_dev);  // z_dev may be null
 int forward_latent_dev(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* out_dev, float* mods_out_dev);
 int forward_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* out_dev);
 int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og = nullptr);

@@ -429,13 +429,16 @@ static int launch_prologue_f16x3(msiren_ctx* h, const Call& c, const float* tile
         p.pf_lines = (unsigned)(((size_t)h->em_wave_stride * 4 * 16 / 8 + 1023) / 1024);
     }
     const int lds = nph == 2 ? msiren::em_tail_lds_bytes<2, 2>() : msiren::em_tail_lds_bytes<4, 1>();
-    return launch(h, c.stream, pk.inst, nblk + p.pf_blocks, lds, p);
+    if ((rc = launch(h, c.stream, pk.inst, nblk + p.pf_blocks, lds, p))) return rc;
+    h->last_prologue = msiren::kInstances[pk.inst].name;
+    return 0;
 }
 
 int launch_modulator(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* mods_dev) {
     if (B == 0) return 0;
     if (!h->have_modulator) return fail(MSIREN_E_STATE, "modulator.* weights were not loaded");
     if (h->em_mod) return launch_prologue_f16x3(h, c, nullptr, z_dev, B, nullptr, mods_dev);
+    h->last_prologue = "";  // (the per-layer exact-fp32 launches)
     size_t off = 0;
     const bool mfma_ok = (h->H % 16 == 0) && (h->Z % 16 == 0);
     for (int l = 0; l < h->L && mfma_ok; ++l) {
@@ -484,6 +487,7 @@ int launch_encoder(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t
     if (B == 0) return 0;
     if (!h->have_encoder) return fail(MSIREN_E_STATE, "encoder.* weights were not loaded");
     if (h->em_enc) return launch_prologue_f16x3(h, c, tiles_dev, nullptr, B, z_dev, nullptr);
+    h->last_prologue = "";  // (the per-layer exact-fp32 launches)
     auto& sc = h->sc[c.stream];
     msiren::EncoderParams enc = h->enc;
     enc.plan = c.plan;
@@ -523,13 +527,25 @@ int launch_encoder(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t
     return launch_linear(h, c, mp);
 }
 
-// encoder + modulator: tiles -> latent -> modulations
-static int launch_encoder_modulator(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev, float* mods_dev) {
+// encoder + modulator: tiles -> latent -> modulations; z_out: where the one-launch prologue stores the latent as well (null: nowhere)
+static int launch_encoder_modulator(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev, float* mods_dev, float* z_out = nullptr) {
     if (B == 0) return 0;
-    if (h->em_enc && h->em_mod) return launch_prologue_f16x3(h, c, tiles_dev, nullptr, B, nullptr, mods_dev);  // (the latent stays in the workgroup)
+    if (h->em_enc && h->em_mod) return launch_prologue_f16x3(h, c, tiles_dev, nullptr, B, z_out, mods_dev);  // (the latent stays in the workgroup)
     int rc = launch_encoder(h, c, tiles_dev, B, z_dev);
     if (rc) return rc;
     return launch_modulator(h, c, z_dev, B, mods_dev);
+}
+
+// msiren_encode_modulate_tiles(_dev): what forward_tiles_dev runs in front of its trunk, and nothing else
+int encode_modulate_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev, float* mods_dev) {
+    if (!h->have_encoder || !h->have_modulator) return fail(MSIREN_E_STATE, "encoder.* / modulator.* weights were not loaded");
+    float* z = z_dev;
+    if (!z && !(h->em_enc && h->em_mod)) {  // (the per-layer launches pass the latent through HBM)
+        int rc = ensure(h, h->sc[c.stream].latent, (size_t)B * h->Z * sizeof(float));
+        if (rc) return rc;
+        z = (float*)h->sc[c.stream].latent.p;
+    }
+    return launch_encoder_modulator(h, c, tiles_dev, B, z, mods_dev, z_dev);
 }
 
 int forward_latent_dev(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* out_dev, float* mods_out_dev) {

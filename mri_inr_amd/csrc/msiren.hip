@@ -414,6 +414,59 @@ int msiren_modulate(msiren_handle h, const float* z_host, int64_t B, float* mods
     return 0;
 }
 
+// ---- the prologue of msiren_forward_tiles(_dev) alone: tiles -> [latent] -> modulations, by the launches that call would make ----
+int msiren_encode_modulate_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, float* latent_dev, float* mods_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    const Call c = dev_call(h);
+    if (B < 0 || (B > 0 && (!tiles_dev || !mods_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
+    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if (B == 0) return 0;
+    return encode_modulate_dev(h, c, tiles_dev, B, latent_dev, mods_dev);
+}
+
+int msiren_encode_modulate_tiles(msiren_handle h, const float* tiles_host, int64_t B, float* latent_host, float* mods_host) {
+    int rc = check(h);
+    if (rc) return rc;
+    if (B < 0 || (B > 0 && (!tiles_host || !mods_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
+    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if (B == 0) return 0;
+    const size_t tile_elems = (size_t)h->O * h->O, nt = (size_t)B * tile_elems * sizeof(float), nz = (size_t)B * h->Z * sizeof(float);
+    const size_t nm = (size_t)h->L * B * h->H * sizeof(float);
+    // device staging for the whole call (chunk k's modulations, (L, n_k, H), sit at L * lo_k * H): nothing is reallocated while a chunk runs
+    if ((rc = ensure(h, h->ws_tiles, nt)) || (rc = ensure(h, h->ws_out, nm)) || (rc = ensure(h, h->ws_img, nz))) return rc;
+    // the chunks, streams and CallMode of msiren_forward_tiles_impl (which see): every chunk reaches the instance it reaches there
+    std::vector<msiren::HostChunk> plan;
+    if (msiren::host_call_pipelines(h->dh, B)) plan = msiren::pipelined_host_plan(B, h->host_first, h->host_piece, h->cur);
+    else plan.push_back({0, B, h->cur, 0, false});
+    const HostSrc src(tiles_host, nt);
+    const HostDst dst_z(latent_host, nz), dst(mods_host, nm);
+    HOSTBUF_OK(src);
+    HOSTBUF_OK(dst_z);
+    HOSTBUF_OK(dst);
+    DrainOnExit drain(h);
+    Call call = make_call(h, true);
+    for (const msiren::HostChunk& c : plan) {
+        call.stream = c.stream;
+        call.mode.trunk = c.trunk;
+        call.mode.beside = c.beside;
+        hipStream_t s = h->sc[c.stream].s;
+        float* const d_t = (float*)h->ws_tiles.p + (size_t)c.lo * tile_elems;
+        float* const d_z = (float*)h->ws_img.p + (size_t)c.lo * h->Z;
+        float* const d_m = (float*)h->ws_out.p + (size_t)h->L * c.lo * h->H;
+        HIPCHK(hipMemcpyAsync(d_t, src.as<float>() + (size_t)c.lo * tile_elems, (size_t)c.n * tile_elems * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = encode_modulate_dev(h, call, d_t, c.n, latent_host ? d_z : nullptr, d_m))) return rc;
+        if (latent_host) HIPCHK(hipMemcpyAsync(dst_z.as<float>() + (size_t)c.lo * h->Z, d_z, (size_t)c.n * h->Z * sizeof(float), hipMemcpyDeviceToHost, s));
+        const size_t row = (size_t)c.n * h->H * sizeof(float);  // layer l of the chunk -> rows [lo, lo + n) of layer l of the call
+        HIPCHK(hipMemcpy2DAsync(dst.as<float>() + (size_t)c.lo * h->H, (size_t)B * h->H * sizeof(float), d_m, row, row, (size_t)h->L, hipMemcpyDeviceToHost, s));
+    }
+    if ((rc = sync_all(h))) return rc;
+    drain.disarm();
+    dst_z.finish();
+    dst.finish();
+    return 0;
+}
+
 int msiren_forward_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, float* out_dev) {
     int rc = check(h);
     if (rc) return rc;
@@ -735,6 +788,12 @@ int msiren_profile_read_kernel(msiren_handle h, int32_t index, char* name128, in
 int msiren_last_trunk_kernel(msiren_handle h, char* name128) {
     if (!h || !name128) return fail(MSIREN_E_INVALID, "null argument");
     std::snprintf(name128, 128, "%s", h->last_trunk);
+    return 0;
+}
+
+int msiren_last_prologue_kernel(msiren_handle h, char* name128) {
+    if (!h || !name128) return fail(MSIREN_E_INVALID, "null argument");
+    std::snprintf(name128, 128, "%s", h->last_prologue);
     return 0;
 }
 

@@ -409,8 +409,9 @@ int pack_encoder(msiren_ctx* h) {
 // x [64 lanes][8 x f16]; lane (m = lane & 15, q = lane >> 4), element j: output feature 16 T + m, input
 // k(s, q, j) = 32 s + 16 (j >> 2) + 4 q + (j & 3) of k-step s.  Sections: conv3 (32 k-steps: the wave's K half of its tile
 // pair), Linear(64, Z) (NPZ passes x 4 k-steps, the upper two zero), the latent part of every Modulator layer (L NPH passes
-// x Z / 32), the hidden part of layers 1.. ((L - 1) NPH passes x H / 32).  Each layer is scaled by the power of two that
-// brings max|W| into [2^13, 2^14) before the hi / lo split.
+// x Z / 32), the hidden part of layers 1.. ((L - 1) NPH passes x H / 32).  Each SECTION's matrix is scaled by the power of two that
+// brings its max|W| into [2^13, 2^14) before the hi / lo split: conv2, conv3, Linear(64, Z), and of a Modulator layer the latent part
+// W[:, Kh:] and the hidden part W[:, :H] each by its own (winv_z[l], winv_h[l]: they meet inputs with different row scales).
 int pack_prologue_f16x3(msiren_ctx* h) {
     h->em_enc = h->em_mod = false;
     const int H = h->H, Z = h->Z, L = h->L;

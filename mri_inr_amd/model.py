@@ -327,6 +327,14 @@ class ModulatedSiren:
         _lib.check(self._lib.msiren_last_trunk_kernel(self._h, buf))
         return buf.value.decode()
 
+    def last_prologue_kernel(self) -> str:
+        """Name of the latent_mods instance the handle's most recent prologue launch used, "" behind the per-layer exact-fp32
+        launches (msiren_last_prologue_kernel)."""
+        self._ensure_handle()
+        buf = C.create_string_buffer(128)
+        _lib.check(self._lib.msiren_last_prologue_kernel(self._h, buf))
+        return buf.value.decode()
+
     def profile_kernels(self) -> list:
         """Per trunk instance since msiren_profile_enable(h, 1): name, launches, summed ms, coordinates evaluated."""
         self._ensure_handle()
@@ -508,6 +516,22 @@ class ModulatedSiren:
                                   lambda s: (self.num_layers, s[0], self.dim_hidden))
         # msiren_modulate's batch argument is the latent's first dimension; the output is (L, B, H)
         return tuple(stacked[l] for l in range(self.num_layers))
+
+    def encode_modulate(self, tiles, return_latent=False):
+        """tiles (B, O, O) -> modulations (L, B, H) [and the latent (B, Z)]: the prologue of ``forward(tiles)`` alone, by the launches
+        that call makes in front of its trunk (msiren_encode_modulate_tiles).  numpy in, numpy out."""
+        if self.encoder_type != "custom":
+            raise AttributeError("'Encoder' object has no attribute 'encoder'")  # as the reference fails
+        self._ensure_committed()
+        O = self.outer_patch_size
+        a = np.ascontiguousarray(tiles, dtype=np.float32)
+        self._check_tail(a.shape, (None, O, O))
+        B = a.shape[0]
+        mods = np.empty((self.num_layers, B, self.dim_hidden), dtype=np.float32)
+        z = np.empty((B, self.latent_dim), dtype=np.float32) if return_latent else None
+        _lib.check(self._lib.msiren_encode_modulate_tiles(self._h, a.ctypes.data if B else None, B,
+                                                          z.ctypes.data if return_latent and B else None, mods.ctypes.data if B else None))
+        return (mods, z) if return_latent else mods
 
     def net(self, coords, mods):
         """``SirenNet.forward(coords, mods)`` (modulated_siren.py:215-233) -> (B, P, 1).  The trunk kernels evaluate the model's
