@@ -33,13 +33,14 @@
 extern "C" {
 #endif
 
-/* 5: msiren_encode_modulate_tiles(_dev) (the prologue of msiren_forward_tiles alone) and msiren_last_prologue_kernel added.
+/* 6: msiren_sample_grad_* and msiren_reconstruct_slices_grad(_dev) (the model's spatial gradient) added.
+ * 5: msiren_encode_modulate_tiles(_dev) (the prologue of msiren_forward_tiles alone) and msiren_last_prologue_kernel added.
  * 4: msiren_sample_* (the trunk at caller-chosen coordinates), msiren_upsampled_geometry / _lattice and the *_scaled slice pipeline
  * (another output stride) added.  3 (round 6): msiren_runtime_info, msiren_host_range_kind added; the large-call split (MSIREN_SPLIT_MIN) and the per-call page-locking of
  * caller buffers (MSIREN_HOST_REGISTER) left the library.  2 (round 5): msiren_chain_* gone, msiren_profile_read_kernel /
  * msiren_last_trunk_kernel / msiren_device_pci added; sync no longer returns MSIREN_E_RANGE.  A library of another number refuses
  * msiren_create. */
-#define MSIREN_ABI_VERSION 5
+#define MSIREN_ABI_VERSION 6
 
 #if defined(__GNUC__)
 #define MSIREN_API __attribute__((visibility("default")))
@@ -259,6 +260,38 @@ MSIREN_API int msiren_reconstruct_tiles_scaled_dev(msiren_handle h, const float*
 MSIREN_API int msiren_weighted_fold_scaled_dev(msiren_handle h, const float* tiles_dev /* (n*nV*nH, S', S') */, int64_t n_slices,
                                                int32_t n_vertical, int32_t n_horizontal, int32_t out_stride, float* recon_dev);
 
+/* The model's spatial gradient: what torch.autograd gives the reference for d SirenNet.forward / d coords
+ * (modulated_siren.py:215-233 is differentiable in coords), here by a forward-mode pass through the same layers in one kernel
+ * (siren_trunk_f32_jet.hip.h).  The arguments are msiren_sample_*'s and so are the coordinate rules: 1 <= Q <= 65 536, device
+ * coordinates 8-byte aligned, any real coordinate accepted, a non-finite coordinate makes value and gradient non-finite at that q only,
+ * B = 0 does nothing.  out (B, Q) may be NULL (the gradient alone); grad is PLANAR (2, B, Q): grad[0, b, q] = d out[b, q] / d coords[q, 0]
+ * (the row coordinate), grad[1, b, q] = d out[b, q] / d coords[q, 1].
+ * ALWAYS EXACT FP32, on handles of every precision: the call runs the fp32 jet trunk on the packed fp32 weights every handle holds; no
+ * layer-0 table is built and there is no domain guard, since there is no fp16 operand.  The value returned is the bits of an fp32
+ * handle's msiren_sample_* -- on a split-fp16 handle it is therefore the fp32 trunk's value, NOT the split-fp16 trunk's (the _tiles
+ * forms still run the handle's own prologue in front).  dim_hidden > 256 (value and two tangents of a chunk no longer fit the LDS) or
+ * residual = 1: MSIREN_E_INVALID.  msiren_last_trunk_kernel keeps naming the last trunk of the forward calls; under
+ * msiren_profile_enable the launch is reported as "siren_trunk_f32_jet_kernel<HP,ACT>".
+ * The _dev forms enqueue on the stream rotation like the forward calls; the host-pointer forms are synchronous one-chunk calls. */
+MSIREN_API int msiren_sample_grad_mods(msiren_handle h, const float* coords_host, int64_t Q, const float* mods_host, int64_t B,
+                                       float* out_host /* (B, Q) or NULL */, float* grad_host /* (2, B, Q) */);
+MSIREN_API int msiren_sample_grad_mods_dev(msiren_handle h, const float* coords_dev, int64_t Q, const float* mods_dev, int64_t B,
+                                           float* out_dev /* (B, Q) or NULL */, float* grad_dev /* (2, B, Q) */);
+MSIREN_API int msiren_sample_grad_tiles(msiren_handle h, const float* coords_host, int64_t Q, const float* tiles_host, int64_t B,
+                                        float* out_host /* (B, Q) or NULL */, float* grad_host /* (2, B, Q) */);
+MSIREN_API int msiren_sample_grad_tiles_dev(msiren_handle h, const float* coords_dev, int64_t Q, const float* tiles_dev, int64_t B,
+                                            float* out_dev /* (B, Q) or NULL */, float* grad_dev /* (2, B, Q) */);
+/* Build-defined, like the other output strides: the slice pipeline with the gradient of every tile, tiling -> black flags -> plan ->
+ * prologue -> jet trunk on the lattice of out_stride (out_stride = inner_patch_size: the model's own grid) -> the weighted fold, once
+ * for recon (n, nV*out_stride, nH*out_stride; may be NULL) and once per plane of grad (2, n, nV*out_stride, nH*out_stride).  The tile
+ * gradients are multiplied by float32(d / r), d = 2/(S-1), r = out_stride/inner_patch_size (fp64): grad is per OUTPUT PIXEL, plane 0
+ * along the rows, plane 1 along the columns, the fold-weighted average of the covering tiles' analytic gradients (black tiles
+ * contribute zeros with their weight).  recon is the exact-fp32 trunk's reconstruction at that stride. */
+MSIREN_API int msiren_reconstruct_slices_grad(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                              int32_t out_stride, float* recon_host, float* grad_host);
+MSIREN_API int msiren_reconstruct_slices_grad_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                                  int32_t out_stride, float* recon_dev, float* grad_dev);
+
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.
  * data range = max - min over both images (subtracted in float32); PSNR = 10 log10(range^2 / mean((o-p)^2));
@@ -348,7 +381,8 @@ MSIREN_API int msiren_profile_read(msiren_handle h, int64_t* launches, double* t
  * its name as launched (e.g. "siren_trunk_f16x3w_kernel<0,4>"), launch count, summed milliseconds and the coordinates
  * (patches x siren_patch_size^2) its launches evaluated -- a host call of several slices runs two trunk instances, so a roofline figure is per instance: msiren_flops_per_coord x coords_total / ms_total.  MSIREN_E_INVALID past
  * the last entry.  A msiren_sample_* call on a 16-bit handle adds an entry "layer0_table_kernel" (its coordinates: those of the call's set; not
- * part of msiren_profile_read's trunk totals).  msiren_last_trunk_kernel: the instance the most recent trunk launch of the handle used. */
+ * part of msiren_profile_read's trunk totals); a gradient call (msiren_sample_grad_*, msiren_reconstruct_slices_grad) adds
+ * "siren_trunk_f32_jet_kernel<HP,ACT>" in the same way (coordinates: B x Q).  msiren_last_trunk_kernel: the instance the most recent trunk launch of the handle used. */
 MSIREN_API int msiren_profile_read_kernel(msiren_handle h, int32_t index, char* name128, int64_t* launches, double* ms_total,
                                           int64_t* coords_total);
 MSIREN_API int msiren_last_trunk_kernel(msiren_handle h, char* name128);

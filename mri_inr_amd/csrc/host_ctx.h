@@ -9,7 +9,8 @@
 //     diagnostics.hip      stamped timeline builds, the sustained-MFMA probe
 //     scores.hip           PSNR / SSIM / NRMSE of image pairs (the evaluation harness's metrics; kernels: scores.hip.h)
 //     sample_grid.hip      the trunk at caller-chosen coordinates and the slice pipeline at another output stride: the per-call layer-0
-//                          table (kernel: sample_grid.hip.h), msiren_sample_*, msiren_upsampled_*, the *_scaled entry points
+//                          table (kernel: sample_grid.hip.h), msiren_sample_*, msiren_upsampled_*, the *_scaled entry points; the
+//                          gradient calls (msiren_sample_grad_*, msiren_reconstruct_slices_grad: siren_trunk_f32_jet.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -174,6 +175,9 @@ inline Call make_call(const msiren_ctx* h, bool sync) {
 // the output side of the slice pipeline where it is not the model's own (the call carries the lattice: Call::cs): tile S', stride I',
 // padding pad', fold weights (S', S')
 struct OutGeom { int tile = 0, stride = 0, pad = 0; const float* foldw = nullptr; };
+// the slice pipeline with its spatial gradient (msiren_reconstruct_slices_grad): the exact-fp32 jet trunk in place of the handle's trunk,
+// grad (2, n, nV*I', nH*I') folded plane by plane; every gradient multiplied by gscale (coordinate units per output pixel)
+struct GradOut { float* grad = nullptr; float gscale = 1.f; };
 
 // msiren.hip
 int use_device(msiren_ctx* h);
@@ -208,13 +212,17 @@ int launch_encoder(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t
 int encode_modulate_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* z_dev, float* mods_dev);  // z_dev may be null
 int forward_latent_dev(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B, float* out_dev, float* mods_out_dev);
 int forward_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* out_dev);
-int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og = nullptr);
+int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og = nullptr,
+                       const GradOut* go = nullptr);  // go: recon_dev may be null
+int jet_supported(msiren_ctx* h);  // 0, or MSIREN_E_INVALID: dim_hidden > 256 / residual (what the jet trunk does not take)
+int launch_trunk_f32_jet(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev /* may be null */, float* grad_dev, float gscale);
 
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 
 // sample_grid.hip
-int scaled_call(msiren_ctx* h, Call& c, int32_t out_stride, OutGeom* og);  // the call evaluates and folds the lattice of out_stride (built on first use)
+// the call evaluates and folds the lattice of out_stride (built on first use); table = false: without the 16-bit trunks' layer-0 table
+int scaled_call(msiren_ctx* h, Call& c, int32_t out_stride, OutGeom* og, bool table = true);
 void drop_lattices(msiren_ctx* h);  // msiren_commit_weights (the streams are idle), msiren_destroy
 
 // comm_rccl.hip

@@ -12,6 +12,7 @@
 #include "siren_trunk_f16x3h.hip.h"
 #include "siren_trunk_f16x3w.hip.h"
 #include "siren_trunk_f32.hip.h"
+#include "siren_trunk_f32_jet.hip.h"
 #include "siren_trunk_x1n.hip.h"
 #include "siren_trunk_x1w.hip.h"
 #include "tiling.hip.h"
@@ -19,6 +20,7 @@
 
 namespace msiren {  // the trunk / prologue kernels are compiled in their own translation units (k_*.hip)
 MSIREN_TRUNK_INSTANCES(MSIREN_EXTERN_TRUNK)
+MSIREN_F32_JET_INSTANCES(MSIREN_EXTERN_TRUNK)
 MSIREN_PROLOGUE_INSTANCES(MSIREN_EXTERN_PROLOGUE)
 }  // namespace msiren
 
@@ -52,11 +54,17 @@ void describe_for_dispatch(msiren_ctx* h) {
     d.ws_depth_ok = h->L >= msiren::WS_MIN_L && h->L <= msiren::WS_MAX_L;
 }
 
-// Launch of instance `inst` (a row of msiren::kInstances) with `lds` bytes of dynamic LDS on stream `s` of the handle.  The kernel's
-// LDS limit is raised once per handle; `named`: the launch is the trunk msiren_last_trunk_kernel and the profile report.
+// The exact-fp32 jet trunk's instances (trunk_instances.h: a list of its own, outside msiren::kInstances), in the list's order
+struct JetInstance { const void* k; const char* name; int HP, act; };
+const JetInstance kJetInstances[] = {
+#define MSIREN_JET_ROW(fam, hp, act) {(const void*)msiren::siren_trunk_##fam##_kernel<hp, act>, "siren_trunk_" #fam "_kernel<" #hp "," #act ">", hp, act},
+    MSIREN_F32_JET_INSTANCES(MSIREN_JET_ROW)
+#undef MSIREN_JET_ROW
+};
+
+// Launch of kernel `k` with `lds` bytes of dynamic LDS on stream `s` of the handle.  The kernel's LDS limit is raised once per handle.
 template <typename P>
-int launch(msiren_ctx* h, int s, int inst, int64_t grid, int lds, P p, bool named = false) {
-    const void* k = kKernels[inst];
+int launch_kernel(msiren_ctx* h, int s, const void* k, int64_t grid, int lds, P p) {
     if (lds > 64 * 1024) {
         auto* e = std::begin(h->lds_set);
         while (e != std::end(h->lds_set) && e->k && e->k != k) ++e;
@@ -68,8 +76,15 @@ int launch(msiren_ctx* h, int s, int inst, int64_t grid, int lds, P p, bool name
     void* args[] = {&p};
     (void)hipLaunchKernel(k, dim3((unsigned)grid), dim3(256), args, (size_t)lds, h->sc[s].s);  // (as hipLaunchKernelGGL: errors below)
     HIPCHK(hipGetLastError());
-    if (named) h->last_trunk = msiren::kInstances[inst].name;
     return 0;
+}
+
+// Launch of instance `inst` (a row of msiren::kInstances); `named`: the launch is the trunk msiren_last_trunk_kernel and the profile report.
+template <typename P>
+int launch(msiren_ctx* h, int s, int inst, int64_t grid, int lds, P p, bool named = false) {
+    const int rc = launch_kernel(h, s, kKernels[inst], grid, lds, p);
+    if (!rc && named) h->last_trunk = msiren::kInstances[inst].name;
+    return rc;
 }
 
 msiren::TrunkParams make_trunk_params(msiren_ctx* h, const Call& c, const float* mods, int stride, int64_t B, float* out_dev) {
@@ -292,29 +307,62 @@ static int launch_trunk_x1(msiren_ctx* h, const Call& c, const msiren::TrunkPick
     return queue_launched(h, c.stream, launch(h, c.stream, t.inst, grid, lds, p, true));
 }
 
+// the fp32 trunks read modulation rows as float4: where dim_hidden is not its padded width, zero-padded copies in the stream's scratch
+static int pad_mods(msiren_ctx* h, const Call& c, int64_t B, const float** mods, int* stride) {
+    if (h->HP == h->H) return 0;
+    auto& sc = h->sc[c.stream];
+    int rc = ensure(h, sc.modpad, (size_t)h->L * B * h->HP * sizeof(float));
+    if (rc) return rc;
+    const int64_t n = (int64_t)h->L * B * h->HP;
+    hipLaunchKernelGGL(msiren::pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc.s,
+                       *mods, (float*)sc.modpad.p, (int64_t)h->L * B, h->H, h->HP);
+    HIPCHK(hipGetLastError());
+    *mods = (const float*)sc.modpad.p;
+    *stride = h->HP;
+    return 0;
+}
+
 // exact-fp32 trunk: one workgroup per 64 coordinates of a patch
 static int launch_trunk_f32(msiren_ctx* h, const Call& c, int inst, const float* mods_dev, int64_t B, float* out_dev) {
     const int chunks = (c.P(h) + 63) / 64;
     if (B * (int64_t)chunks > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
-    auto& sc = h->sc[c.stream];
     const float* mods = mods_dev;
-    int stride = h->H;
-    if (h->HP != h->H) {  // zero-pad the feature axis once so the kernel can use float4 loads
-        int rc = ensure(h, sc.modpad, (size_t)h->L * B * h->HP * sizeof(float));
-        if (rc) return rc;
-        const int64_t n = (int64_t)h->L * B * h->HP;
-        hipLaunchKernelGGL(msiren::pad_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc.s,
-                           mods_dev, (float*)sc.modpad.p, (int64_t)h->L * B, h->H, h->HP);
-        HIPCHK(hipGetLastError());
-        mods = (const float*)sc.modpad.p;
-        stride = h->HP;
-    }
+    int stride = h->H, rc;
+    if ((rc = pad_mods(h, c, B, &mods, &stride))) return rc;
     const msiren::TrunkParams p = make_trunk_params(h, c, mods, stride, B, out_dev);
     const int lds = h->HP * 256 + h->HP * 16;  // X image + layer-0 rows
     hipEvent_t e1 = nullptr;
-    int rc;
     if ((rc = profile_begin(h, c.stream, &e1)) || (rc = launch(h, c.stream, inst, B * chunks, lds, p, true))) return rc;
     return profile_end(h, c.stream, e1, B * c.P(h));
+}
+
+int jet_supported(msiren_ctx* h) {
+    if (h->HP > 256)
+        return fail(MSIREN_E_INVALID, "the gradient calls need dim_hidden <= 256 (value and two tangents of 32 coordinates fill the LDS at 256), got %d", h->H);
+    if (h->cfg.residual) return fail(MSIREN_E_INVALID, "the gradient calls do not support residual=1");
+    return 0;
+}
+
+// Exact-fp32 trunk with its spatial gradient (siren_trunk_f32_jet.hip.h): one workgroup per 32 coordinates of a patch, on handles of
+// every precision (the packed fp32 weights are on the device for every H <= 256).  Not msiren_last_trunk_kernel's trunk; the profile
+// report names it like layer0_table_kernel, outside the trunk totals.
+int launch_trunk_f32_jet(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev, float* grad_dev, float gscale) {
+    int rc = jet_supported(h);
+    if (rc || B == 0) return rc;
+    const int chunks = (c.P(h) + 31) / 32;
+    if (B * (int64_t)chunks > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "batch too large for one launch: B=%lld", (long long)B);
+    const int act = h->cfg.activation == MSIREN_ACT_MORLET ? 1 : 0;
+    const JetInstance* ji = std::begin(kJetInstances);
+    while (ji != std::end(kJetInstances) && (ji->HP != h->HP || ji->act != act)) ++ji;
+    if (ji == std::end(kJetInstances)) return fail(MSIREN_E_INVALID, "dim_hidden=%d (padded %d) is not supported by the gradient trunk", h->H, h->HP);
+    const float* mods = mods_dev;
+    int stride = h->H;
+    if ((rc = pad_mods(h, c, B, &mods, &stride))) return rc;
+    msiren::TrunkJetParams p{make_trunk_params(h, c, mods, stride, B, out_dev), grad_dev, gscale};
+    p.t.chunks = chunks;
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1)) || (rc = launch_kernel(h, c.stream, ji->k, B * chunks, msiren::jet_lds_bytes(h->HP), p))) return rc;
+    return profile_end(h, c.stream, e1, B * c.P(h), ji->name);
 }
 
 // Behind every split-fp16 trunk launch, on the same stream: the exact-fp32 trunk over the same batch as a conditional launch
@@ -681,7 +729,8 @@ namespace mh {
 // `images_dev` given: `patches` is scratch that image_to_patches fills; null: `patches` are the caller's tiles
 // `og` (with c.cs): the output side at another stride (msiren_*_scaled); null: the model's own S, I and fold weights
 static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw,
-                             const float* patches_ro, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og) {
+                             const float* patches_ro, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og,
+                             const GradOut* go = nullptr) {
     int rc;
     auto& sc = h->sc[c.stream];
     const int64_t NP = n * nV * nH;
@@ -690,7 +739,7 @@ static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images
     const float* foldw = og ? og->foldw : h->d_foldw;
     if (NP > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "too many patches for one call: %lld", (long long)NP);
     if ((rc = ensure(h, sc.keep, (size_t)(NP + 64) * sizeof(int)))) return rc;
-    if ((rc = ensure(h, sc.rec, (size_t)NP * P * sizeof(float)))) return rc;
+    if ((rc = ensure(h, sc.rec, (size_t)NP * P * sizeof(float) * (go ? 3 : 1)))) return rc;  // (go: [value][d/d row][d/d column])
     if ((rc = ensure(h, sc.latent, (size_t)NP * h->Z * sizeof(float)))) return rc;
     if ((rc = ensure(h, sc.mods, (size_t)h->L * NP * h->H * sizeof(float)))) return rc;
     int* black = (int*)sc.keep.p;
@@ -722,21 +771,31 @@ static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images
     pc.plan = plan;
     pc.mode.plan = true;
     if ((rc = launch_encoder_modulator(h, pc, patches, NP, (float*)sc.latent.p, (float*)sc.mods.p))) return rc;
-    if ((rc = launch_trunk(h, pc, (const float*)sc.mods.p, NP, rec))) return rc;
+    if (go) rc = launch_trunk_f32_jet(h, pc, (const float*)sc.mods.p, NP, recon_dev ? rec : nullptr, rec + (size_t)NP * P, go->gscale);
+    else rc = launch_trunk(h, pc, (const float*)sc.mods.p, NP, rec);
+    if (rc) return rc;
     if ((rc = queue_reset_after_plan_launch(h, c.stream, fused))) return rc;
     const int64_t total = n * nV * oI * (int64_t)nH * oI;
     if ((total + 255) / 256 > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "reconstruction too large for one call: %lld pixels", (long long)total);
-    hipLaunchKernelGGL(msiren::weighted_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                       rec, foldw, recon_dev, black, plan + 2 + NP, n, nV, nH, oS, oI, opad,
-                       fused && sc.queue.p ? (int*)sc.queue.p : nullptr);
-    HIPCHK(hipGetLastError());
+    int* reset_word = fused && sc.queue.p ? (int*)sc.queue.p : nullptr;
+    // value, then (go) the two gradient planes: the same weighted fold, black tiles contributing zeros with their weight
+    for (int k = 0; k < (go ? 3 : 1); ++k) {
+        float* dst = k == 0 ? recon_dev : go->grad + (size_t)(k - 1) * total;
+        if (!dst) continue;
+        hipLaunchKernelGGL(msiren::weighted_fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
+                           rec + (size_t)k * NP * P, foldw, dst, black, plan + 2 + NP, n, nV, nH, oS, oI, opad, reset_word);
+        HIPCHK(hipGetLastError());
+        reset_word = nullptr;
+    }
     return 0;
 }
 
 // slice pipeline on the call's stream (the host-pointer entry point enqueues its copies around it)
-int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og) {
+int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og,
+                       const GradOut* go) {
     int rc;
-    if (n < 0 || (n > 0 && (!images_dev || !recon_dev))) return fail(MSIREN_E_INVALID, "bad arguments");
+    if (n < 0 || (n > 0 && (!images_dev || (go ? !go->grad : !recon_dev)))) return fail(MSIREN_E_INVALID, "bad arguments");
+    if (go && (rc = jet_supported(h))) return rc;
     if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
     if (n == 0) return 0;
     int32_t nV, nH;
@@ -749,7 +808,7 @@ int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, 
         return fail(MSIREN_E_INVALID, "image %dx%d is too small for reflect padding of %d/%d", height, width, padr + vpad, padr + hpad);
     auto& sc = h->sc[c.stream];
     if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float)))) return rc;
-    return reconstruct_tiles(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, recon_dev, og);
+    return reconstruct_tiles(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, recon_dev, og, go);
 }
 
 // msiren_weighted_fold_dev with the output side of another stride (kernel S', stride I', padding pad'): complete tiles, no black flags

@@ -73,11 +73,22 @@ void lattice(int32_t S, int32_t I, int32_t out_stride, int32_t tile, float* lin)
 using Lattice = msiren_ctx::StreamCtx::Lattice;
 
 // The lattice of an output stride on stream `s`: coordinates, table and fold weights, built on first use (uploads and the table kernel
-// on that stream, so whatever the stream runs next sees them) and kept until msiren_commit_weights.
-int get_lattice(msiren_ctx* h, int s, int32_t out_stride, const Lattice** out) {
+// on that stream, so whatever the stream runs next sees them) and kept until msiren_commit_weights.  `table` false (the gradient calls:
+// the exact-fp32 jet trunk reads the coordinates): no layer-0 table is built; a later call that needs it adds it to the kept lattice.
+int get_lattice(msiren_ctx* h, int s, int32_t out_stride, const Lattice** out, bool table = true) {
     auto& sc = h->sc[s];
-    for (const Lattice& l : sc.lattices)
+    table = table && needs_table(h);
+    for (Lattice& l : sc.lattices)
         if (l.out_stride == out_stride) {
+            if (table && !l.table) {
+                const size_t Q = (size_t)l.tile * l.tile;
+                if (hipMalloc((void**)&l.table, (size_t)h->H * Q * sizeof(float)) != hipSuccess) {
+                    l.table = nullptr;
+                    return fail(MSIREN_E_NOMEM, "no device memory for the lattice of out_stride=%d: %s", out_stride, hipGetErrorString(hipGetLastError()));
+                }
+                const int rc = launch_table(h, s, l.coords, (int)Q, l.table);
+                if (rc) return rc;
+            }
             *out = &l;
             return 0;
         }
@@ -101,7 +112,7 @@ int get_lattice(msiren_ctx* h, int s, int32_t out_stride, const Lattice** out) {
     Lattice& k = sc.lattices.back();  // (in place first: the uploads read k.host, which has to outlive this call)
     rc = 0;
     if (hipMalloc((void**)&k.coords, Q * 2 * sizeof(float)) != hipSuccess || hipMalloc((void**)&k.foldw, Q * sizeof(float)) != hipSuccess ||
-        (needs_table(h) && hipMalloc((void**)&k.table, (size_t)h->H * Q * sizeof(float)) != hipSuccess))
+        (table && hipMalloc((void**)&k.table, (size_t)h->H * Q * sizeof(float)) != hipSuccess))
         rc = fail(MSIREN_E_NOMEM, "no device memory for the lattice of out_stride=%d: %s", out_stride, hipGetErrorString(hipGetLastError()));
     else if (hipMemcpyAsync(k.coords, k.host.data(), Q * 2 * sizeof(float), hipMemcpyHostToDevice, sc.s) != hipSuccess ||
         hipMemcpyAsync(k.foldw, k.host.data() + Q * 2, Q * sizeof(float), hipMemcpyHostToDevice, sc.s) != hipSuccess)
@@ -187,6 +198,100 @@ int sample_dev(msiren_ctx* h, const float* coords_dev, int64_t Q, const float* i
     return tiles ? forward_tiles_dev(h, c, in_dev, B, out_dev) : launch_trunk(h, c, in_dev, B, out_dev);
 }
 
+// ---- value and spatial gradient: the exact-fp32 jet trunk on handles of every precision (siren_trunk_f32_jet.hip.h) -----------------
+
+int check_grad_args(msiren_ctx* h, const float* coords, int64_t Q, const float* in, int64_t B, const float* grad, bool tiles) {
+    int rc = check_coords(coords, Q);
+    if (rc || (rc = jet_supported(h))) return rc;
+    if (B < 0 || (B > 0 && (!in || !grad))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
+    if (tiles && h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    return 0;
+}
+
+// the call's coordinates as they are (no layer-0 table: the jet trunk forms layer 0 itself)
+int attach_coords_only(Call& c, const float* coords_dev, int64_t Q) {
+    if ((uintptr_t)coords_dev % 8) return fail(MSIREN_E_INVALID, "device coordinates must be 8-byte aligned (they are read as (row, column) pairs)");
+    c = with_coords(c, CoordSet{coords_dev, nullptr, (int)Q});
+    return 0;
+}
+
+// [encoder -> Modulator ->] jet trunk on the call's stream
+int grad_dev_impl(msiren_ctx* h, const Call& c, const float* in_dev, int64_t B, float* out_dev, float* grad_dev, bool tiles) {
+    const float* mods = in_dev;
+    if (tiles) {
+        if (!h->have_encoder || !h->have_modulator) return fail(MSIREN_E_STATE, "encoder.* / modulator.* weights were not loaded");
+        auto& sc = h->sc[c.stream];
+        int rc = ensure(h, sc.mods, (size_t)h->L * B * h->H * sizeof(float));
+        if (rc || (rc = encode_modulate_dev(h, c, in_dev, B, nullptr, (float*)sc.mods.p))) return rc;
+        mods = (const float*)sc.mods.p;
+    }
+    return launch_trunk_f32_jet(h, c, mods, B, out_dev, grad_dev, 1.0f);
+}
+
+int sample_grad_dev(msiren_ctx* h, const float* coords_dev, int64_t Q, const float* in_dev, int64_t B, float* out_dev, float* grad_dev, bool tiles) {
+    int rc = check(h);
+    if (rc || (rc = check_grad_args(h, coords_dev, Q, in_dev, B, grad_dev, tiles))) return rc;
+    if ((uintptr_t)coords_dev % 8) return fail(MSIREN_E_INVALID, "device coordinates must be 8-byte aligned (they are read as (row, column) pairs)");
+    if (B == 0) return 0;
+    Call c = dev_call(h);
+    if ((rc = attach_coords_only(c, coords_dev, Q))) return rc;
+    return grad_dev_impl(h, c, in_dev, B, out_dev, grad_dev, tiles);
+}
+
+// one synchronous one-chunk call on host pointers, as sample_host_impl: coords + (tiles | mods) -> [out], grad
+int sample_grad_host(msiren_ctx* h, const float* coords_host, int64_t Q, const float* in_host, int64_t B, float* out_host, float* grad_host, bool tiles) {
+    int rc = check(h);
+    if (rc || (rc = check_grad_args(h, coords_host, Q, in_host, B, grad_host, tiles))) return rc;
+    if (B == 0) return 0;
+    Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
+    const size_t nc = (size_t)Q * 2 * sizeof(float), no = (size_t)B * Q * sizeof(float);
+    const size_t ni = tiles ? (size_t)B * h->O * h->O * sizeof(float) : (size_t)h->L * B * h->H * sizeof(float);
+    DevBuf& in_buf = tiles ? h->ws_tiles : h->ws_in;  // (sc.mods is where the _tiles form's prologue writes)
+    if ((rc = ensure(h, sc.coords, nc)) || (rc = ensure(h, in_buf, ni)) || (rc = ensure(h, h->ws_out, no)) || (rc = ensure(h, h->ws_img, 2 * no))) return rc;
+    const HostSrc csrc(coords_host, nc), src(in_host, ni);
+    const HostDst dst(out_host, out_host ? no : 0), gdst(grad_host, 2 * no);
+    HOSTBUF_OK(csrc);
+    HOSTBUF_OK(src);
+    HOSTBUF_OK(dst);
+    HOSTBUF_OK(gdst);
+    DrainOnExit drain(h);
+    HIPCHK(hipMemcpyAsync(sc.coords.p, csrc.as<float>(), nc, hipMemcpyHostToDevice, sc.s));
+    if ((rc = attach_coords_only(c, (const float*)sc.coords.p, Q))) return rc;
+    const float* d_in = tiles ? src.dev<float>() : nullptr;  // (page-locked tiles are read in place; modulations are read once per unit: copied)
+    if (!d_in) {
+        HIPCHK(hipMemcpyAsync(in_buf.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
+        d_in = (const float*)in_buf.p;
+    }
+    float* const d_out = !out_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_out.p;
+    float* const d_grad = gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_img.p;
+    if ((rc = grad_dev_impl(h, c, d_in, B, d_out, d_grad, tiles))) return rc;
+    if (d_out && d_out == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
+    if (d_grad == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_img.p, 2 * no, hipMemcpyDeviceToHost, sc.s));
+    HIPCHK(hipStreamSynchronize(sc.s));
+    drain.disarm();
+    dst.finish();
+    gdst.finish();
+    return 0;
+}
+
+// The slice pipeline with its gradient at output stride out_stride: coordinates, fold geometry and the factor d/r that turns a gradient per
+// coordinate unit into one per OUTPUT PIXEL (d = 2/(S-1): one pixel of the model's grid; r = I'/I), fp64 rounded once.  out_stride =
+// inner_patch_size is the model's own grid and fold weights.
+int grad_slices_call(msiren_ctx* h, Call& c, int32_t out_stride, OutGeom* og, float* gscale) {
+    if (out_stride < 1) return fail(MSIREN_E_INVALID, "out_stride must be positive, got %d", out_stride);
+    if (out_stride == h->I) {
+        c = with_coords(c, CoordSet{h->d_grid, nullptr, h->P});
+        *og = OutGeom{h->S, h->I, (h->S - h->I) / 2, h->d_foldw};
+    } else {
+        const int rc = scaled_call(h, c, out_stride, og, false);
+        if (rc) return rc;
+    }
+    const double d = 2.0 / (double)(h->S - 1), r = (double)out_stride / (double)h->I;
+    *gscale = (float)(d / r);
+    return 0;
+}
+
 }  // namespace
 
 namespace mh {
@@ -200,9 +305,9 @@ void drop_lattices(msiren_ctx* h) {
     }
 }
 
-int scaled_call(msiren_ctx* h, Call& c, int32_t out_stride, OutGeom* og) {
+int scaled_call(msiren_ctx* h, Call& c, int32_t out_stride, OutGeom* og, bool table) {
     const Lattice* l;
-    int rc = get_lattice(h, c.stream, out_stride, &l);
+    int rc = get_lattice(h, c.stream, out_stride, &l, table);
     if (rc) return rc;
     c = with_coords(c, CoordSet{l->coords, l->table, l->tile * l->tile});
     *og = OutGeom{l->tile, l->out_stride, l->pad, l->foldw};
@@ -270,6 +375,68 @@ int msiren_weighted_fold_scaled_dev(msiren_handle h, const float* tiles_dev, int
     if (n < 0 || nV < 1 || nH < 1 || (n > 0 && (!tiles_dev || !recon_dev))) return fail(MSIREN_E_INVALID, "bad arguments");
     if (n == 0) return 0;
     return weighted_fold_dev(h, c, tiles_dev, n, nV, nH, recon_dev, og);
+}
+
+int msiren_sample_grad_mods(msiren_handle h, const float* coords_host, int64_t Q, const float* mods_host, int64_t B, float* out_host, float* grad_host) {
+    return sample_grad_host(h, coords_host, Q, mods_host, B, out_host, grad_host, false);
+}
+int msiren_sample_grad_mods_dev(msiren_handle h, const float* coords_dev, int64_t Q, const float* mods_dev, int64_t B, float* out_dev, float* grad_dev) {
+    return sample_grad_dev(h, coords_dev, Q, mods_dev, B, out_dev, grad_dev, false);
+}
+int msiren_sample_grad_tiles(msiren_handle h, const float* coords_host, int64_t Q, const float* tiles_host, int64_t B, float* out_host, float* grad_host) {
+    return sample_grad_host(h, coords_host, Q, tiles_host, B, out_host, grad_host, true);
+}
+int msiren_sample_grad_tiles_dev(msiren_handle h, const float* coords_dev, int64_t Q, const float* tiles_dev, int64_t B, float* out_dev, float* grad_dev) {
+    return sample_grad_dev(h, coords_dev, Q, tiles_dev, B, out_dev, grad_dev, true);
+}
+
+int msiren_reconstruct_slices_grad_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, int32_t out_stride,
+                                       float* recon_dev, float* grad_dev) {
+    int rc = check(h);
+    if (rc || (rc = jet_supported(h))) return rc;
+    if (n < 0 || (n > 0 && (!images_dev || !grad_dev))) return fail(MSIREN_E_INVALID, "bad arguments");
+    if (n == 0) return 0;
+    Call c = dev_call(h);
+    OutGeom og;
+    GradOut go{grad_dev, 1.f};
+    if ((rc = grad_slices_call(h, c, out_stride, &og, &go.gscale))) return rc;
+    return reconstruct_slices(h, c, images_dev, n, height, width, recon_dev, &og, &go);
+}
+
+int msiren_reconstruct_slices_grad(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, int32_t out_stride,
+                                   float* recon_host, float* grad_host) {
+    int rc = check(h);
+    if (rc || (rc = jet_supported(h))) return rc;
+    if (n < 0 || (n > 0 && (!images_host || !grad_host))) return fail(MSIREN_E_INVALID, "bad arguments");
+    if (n == 0) return 0;
+    if (out_stride < 1) return fail(MSIREN_E_INVALID, "out_stride must be positive, got %d", out_stride);
+    int32_t nV, nH;
+    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
+    const size_t ni = (size_t)n * height * width * sizeof(float);
+    const size_t nr = (size_t)n * nV * out_stride * nH * out_stride * sizeof(float);
+    if ((rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, h->ws_img, nr)) || (rc = ensure(h, h->ws_out, 2 * nr))) return rc;
+    Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
+    OutGeom og;
+    GradOut go;
+    if ((rc = grad_slices_call(h, c, out_stride, &og, &go.gscale))) return rc;
+    const HostSrc src(images_host, ni);
+    const HostDst dst(recon_host, recon_host ? nr : 0), gdst(grad_host, 2 * nr);
+    HOSTBUF_OK(src);
+    HOSTBUF_OK(dst);
+    HOSTBUF_OK(gdst);
+    DrainOnExit drain(h);
+    float* const d_rec = !recon_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_img.p;
+    go.grad = gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_out.p;
+    HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
+    if ((rc = reconstruct_slices(h, c, (const float*)h->ws_in.p, n, height, width, d_rec, &og, &go))) return rc;
+    if (d_rec && d_rec == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_img.p, nr, hipMemcpyDeviceToHost, sc.s));
+    if (go.grad == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_out.p, 2 * nr, hipMemcpyDeviceToHost, sc.s));
+    HIPCHK(hipStreamSynchronize(sc.s));
+    drain.disarm();
+    dst.finish();
+    gdst.finish();
+    return 0;
 }
 
 }  // extern "C"

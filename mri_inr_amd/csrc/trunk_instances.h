@@ -28,6 +28,10 @@
     MSIREN_F32_INSTANCES(X) MSIREN_F16X3N_INSTANCES(X) MSIREN_F16X3H_INSTANCES(X) MSIREN_F16X3W_INSTANCES(X) \
     MSIREN_X1N_INSTANCES(X) MSIREN_X1W_INSTANCES(X)
 
+// The exact-fp32 trunk with its spatial gradient (siren_trunk_f32_jet.hip.h; <HP,ACT>): a list of its own, like layer0_table_kernel it is
+// no row of the dispatch table -- msiren_sample_grad_* / msiren_reconstruct_slices_grad launch it on every handle with H <= 256.
+#define MSIREN_F32_JET_INSTANCES(X) X(f32_jet, 128,0) X(f32_jet, 128,1) X(f32_jet, 256,0) X(f32_jet, 256,1)
+
 // the one-launch prologue (<family>_f16x3_kernel: encoder_modulator_f16x3.hip.h); latent_mods<NPH,NPZ,DEPTH,MODE>
 #define MSIREN_PROLOGUE_INSTANCES(X)                                                              \
     X(latent_mods, 2,2,2,3) X(latent_mods, 2,2,4,3) X(latent_mods, 2,2,8,3)                       \
@@ -38,6 +42,7 @@
 // HIP units only (inside namespace msiren, behind the kernel headers): the parameter list of each family
 #define MSIREN_PARAMS_f32 (TrunkParams)
 #define MSIREN_PARAMS_f32_cond (TrunkParams)
+#define MSIREN_PARAMS_f32_jet (TrunkJetParams)
 #define MSIREN_PARAMS_f16x3n (TrunkF16Params)
 #define MSIREN_PARAMS_f16x3h (TrunkF16Params)
 #define MSIREN_PARAMS_f16x3w (TrunkWsParams)

@@ -547,9 +547,10 @@ class ModulatedSiren:
         return out.reshape(out.shape[0], -1, 1)
 
     # ---- the representation off its own grid: caller-chosen coordinates, other output resolutions ----
-    def _sample(self, host_fn, dev_fn, x, coords, in_tail, batch_axis):
+    def _sample(self, host_fn, dev_fn, x, coords, in_tail, batch_axis, grad=False):
         """Marshalling of sample / sample_mods: ``x`` as in _run (numpy / torch / DeviceArray), ``coords`` (Q, 2) as numpy, torch or a
-        DeviceArray.  A DeviceArray or device tensor on either side takes the *_dev entry point (the other side is uploaded)."""
+        DeviceArray.  A DeviceArray or device tensor on either side takes the *_dev entry point (the other side is uploaded).
+        ``grad``: the entry point takes a second output (2, B, Q) behind the first; the result is the pair."""
         self._ensure_committed()
         x_t, c_t = _is_torch(x), _is_torch(coords)
         cshape = tuple(coords.shape)
@@ -584,35 +585,36 @@ class ModulatedSiren:
 
         self._check_tail(tuple(x.shape), in_tail)
         B = int(x.shape[batch_axis])
+        shapes = [(B, Q), (2, B, Q)] if grad else [(B, Q)]
         if not (x_dev or c_dev):
             a, c = host_array(x), host_array(coords)
-            out = self._pinned.array((B, Q), strict=False) if self._pin_outputs and B else None
-            if out is None:
-                out = np.empty((B, Q), dtype=np.float32)
-            _lib.check(host_fn(self._h, c.ctypes.data, Q, a.ctypes.data if a.size else None, B, out.ctypes.data if out.size else None))
+            outs = []
+            for shape in shapes:
+                o = self._pinned.array(shape, strict=False) if self._pin_outputs and B else None
+                outs.append(np.empty(shape, dtype=np.float32) if o is None else o)
+            _lib.check(host_fn(self._h, c.ctypes.data, Q, a.ctypes.data if a.size else None, B, *[o.ctypes.data if o.size else None for o in outs]))
             if x_t:
                 import torch
 
-                return torch.from_numpy(out)
-            return out
+                outs = [torch.from_numpy(o) for o in outs]
+            return tuple(outs) if grad else outs[0]
         if x_t and x.is_cuda:
             import torch
 
-            out = torch.empty((B, Q), dtype=torch.float32, device=x.device)
-            out_ptr = out.data_ptr()
+            outs = [torch.empty(shape, dtype=torch.float32, device=x.device) for shape in shapes]
+            ptrs = [o.data_ptr() for o in outs]
         else:
-            out = self.device_array((B, Q))
-            out_ptr = out.ptr
-        _lib.check(dev_fn(self._h, dev_ptr(coords), Q, dev_ptr(x) if B else None, B, out_ptr if B else None))
+            outs = [self.device_array(shape) for shape in shapes]
+            ptrs = [o.ptr for o in outs]
+        _lib.check(dev_fn(self._h, dev_ptr(coords), Q, dev_ptr(x) if B else None, B, *[q if B else None for q in ptrs]))
         _lib.check(self._lib.msiren_sync(self._h))
-        if isinstance(x, DeviceArray) or (x_t and x.is_cuda):
-            return out
-        res = out.numpy()  # x came from the host, only the coordinates live on the device
-        if x_t:
-            import torch
+        if not (isinstance(x, DeviceArray) or (x_t and x.is_cuda)):
+            outs = [o.numpy() for o in outs]  # x came from the host, only the coordinates live on the device
+            if x_t:
+                import torch
 
-            return torch.from_numpy(res)
-        return res
+                outs = [torch.from_numpy(o) for o in outs]
+        return tuple(outs) if grad else outs[0]
 
     def sample(self, tiles, coords):
         """tiles (B, O, O), coords (Q, 2) -> (B, Q): ``ModulatedSiren.forward`` with the trunk evaluated at ``coords`` instead of the
@@ -637,6 +639,61 @@ class ModulatedSiren:
         self._ensure_handle()
         return self._sample(self._lib.msiren_sample_mods, self._lib.msiren_sample_mods_dev, mods, coords,
                             (self.num_layers, None, self.dim_hidden), 1)
+
+    # ---- the model's spatial gradient: what torch.autograd gives the reference for d forward / d coords ----
+    def sample_grad(self, tiles, coords):
+        """tiles (B, O, O), coords (Q, 2) -> (values (B, Q), grad (2, B, Q)): ``sample(tiles, coords)`` and its derivative by the
+        coordinates, grad[0] along ``coords[:, 0]`` (rows), grad[1] along ``coords[:, 1]`` (columns).  Always the exact-fp32 trunk,
+        whatever the model's precision (msiren_sample_grad_tiles)."""
+        if self.encoder_type != "custom":
+            raise AttributeError("'Encoder' object has no attribute 'encoder'")  # as the reference fails
+        O = self.outer_patch_size
+        self._ensure_handle()
+        return self._sample(self._lib.msiren_sample_grad_tiles, self._lib.msiren_sample_grad_tiles_dev, tiles, coords, (None, O, O), 0, grad=True)
+
+    def sample_mods_grad(self, mods, coords):
+        """mods (L, B, H) (or the Modulator's tuple), coords (Q, 2) -> (values (B, Q), grad (2, B, Q)): ``SirenNet.forward(coords, mods)``
+        and ``d SirenNet.forward / d coords`` for one coordinate set shared by the batch (msiren_sample_grad_mods)."""
+        if isinstance(mods, (tuple, list)):
+            if _is_torch(mods[0]):
+                import torch
+
+                mods = torch.stack(list(mods), 0)
+            else:
+                mods = np.stack([np.asarray(m) for m in mods], 0)
+        self._ensure_handle()
+        return self._sample(self._lib.msiren_sample_grad_mods, self._lib.msiren_sample_grad_mods_dev, mods, coords,
+                            (self.num_layers, None, self.dim_hidden), 1, grad=True)
+
+    def reconstruct_with_gradient(self, images, out_stride=None):
+        """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
+        and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
+        covering tiles' analytic gradients (build-defined: msiren_reconstruct_slices_grad).  ``out_stride`` None: inner_patch_size."""
+        self._ensure_committed()
+        a = images.detach().cpu().numpy() if _is_torch(images) else np.asarray(images)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        single = a.ndim == 2
+        if single:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError(f"expected (n, H, W) images, got {a.shape}")
+        n, Hh, Ww = a.shape
+        nv, nh = C.c_int32(), C.c_int32()
+        _lib.check(self._lib.msiren_recon_shape(self._h, Hh, Ww, C.byref(nv), C.byref(nh)))
+        I = self.inner_patch_size if out_stride is None else int(out_stride)
+        self._upsampled_geometry(I)  # (ValueError before anything is allocated)
+        outs = []
+        for shape in ((n, nv.value * I, nh.value * I), (2, n, nv.value * I, nh.value * I)):
+            o = self._pinned.array(shape, strict=False) if self._pin_outputs and n else None
+            outs.append(np.empty(shape, dtype=np.float32) if o is None else o)
+        _lib.check(self._lib.msiren_reconstruct_slices_grad(self._h, a.ctypes.data, n, Hh, Ww, I, outs[0].ctypes.data if n else None,
+                                                            outs[1].ctypes.data if n else None))
+        recon, grad = (outs[0][0], outs[1][:, 0]) if single else outs
+        if _is_torch(images):
+            import torch
+
+            return torch.from_numpy(recon), torch.from_numpy(grad)
+        return recon, grad
 
     def _upsampled_geometry(self, out_stride):
         """(S', pad') of an output stride I': output tile S' = S I'/I and fold padding (S' - I')/2 (msiren_upsampled_geometry; no device).
