@@ -33,14 +33,16 @@
 extern "C" {
 #endif
 
-/* 6: msiren_sample_grad_* and msiren_reconstruct_slices_grad(_dev) (the model's spatial gradient) added.
+/* 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
+ * arbitrary points) added.
+ * 6: msiren_sample_grad_* and msiren_reconstruct_slices_grad(_dev) (the model's spatial gradient) added.
  * 5: msiren_encode_modulate_tiles(_dev) (the prologue of msiren_forward_tiles alone) and msiren_last_prologue_kernel added.
  * 4: msiren_sample_* (the trunk at caller-chosen coordinates), msiren_upsampled_geometry / _lattice and the *_scaled slice pipeline
  * (another output stride) added.  3 (round 6): msiren_runtime_info, msiren_host_range_kind added; the large-call split (MSIREN_SPLIT_MIN) and the per-call page-locking of
  * caller buffers (MSIREN_HOST_REGISTER) left the library.  2 (round 5): msiren_chain_* gone, msiren_profile_read_kernel /
  * msiren_last_trunk_kernel / msiren_device_pci added; sync no longer returns MSIREN_E_RANGE.  A library of another number refuses
  * msiren_create. */
-#define MSIREN_ABI_VERSION 6
+#define MSIREN_ABI_VERSION 7
 
 #if defined(__GNUC__)
 #define MSIREN_API __attribute__((visibility("default")))
@@ -291,6 +293,53 @@ MSIREN_API int msiren_reconstruct_slices_grad(msiren_handle h, const float* imag
                                               int32_t out_stride, float* recon_host, float* grad_host);
 MSIREN_API int msiren_reconstruct_slices_grad_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
                                                   int32_t out_stride, float* recon_dev, float* grad_dev);
+
+/* One coordinate set PER PATCH ("ragged" sets): patch b is evaluated at coords[offsets[b] : offsets[b + 1]].
+ * coords (T, 2) as msiren_sample_*'s (any real value; a non-finite coordinate spoils only its own output; device coordinates 8-byte
+ * aligned), offsets (B + 1) int32, non-decreasing, offsets[0] = 0, offsets[B] = T; a patch may own no coordinate; T = 0 or B = 0 does
+ * nothing.  mods (L, B, H); out (T): the patches' outputs one behind the other, as coords; grad PLANAR (2, T).  T and B below 2^30.
+ * The host-pointer forms check the offsets (MSIREN_E_INVALID) and are synchronous one-chunk calls; the _dev forms read them on the
+ * device only -- offsets outside [0, T] or decreasing are clamped there, never followed outside the call's buffers -- and enqueue on the
+ * stream rotation.
+ * ALWAYS EXACT FP32, on handles of every precision, as the gradient calls above and for the same reason (a layer-0 table per (patch,
+ * coordinate) would be 4 H bytes an entry): out[offsets[b] + i] is the bits of an fp32 handle's msiren_sample_mods of patch b alone at
+ * that coordinate, value and gradient of the _grad forms the bits of msiren_sample_grad_mods.  The value forms take what the fp32
+ * trunk takes (dim_hidden <= 512, residual); the _grad forms what the gradient calls take (dim_hidden <= 256, no residual), out may be
+ * NULL there.  Under msiren_profile_enable the launches are reported as "siren_trunk_f32_ragged_kernel<HP,ACT,RES>" /
+ * "siren_trunk_f32_jet_ragged_kernel<HP,ACT>"; msiren_last_trunk_kernel keeps naming the last trunk of the forward calls. */
+MSIREN_API int msiren_sample_ragged_mods(msiren_handle h, const float* coords_host /* (T, 2) */, const int32_t* offsets_host /* (B + 1) */,
+                                         const float* mods_host, int64_t B, int64_t T, float* out_host /* (T) */);
+MSIREN_API int msiren_sample_ragged_mods_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B,
+                                             int64_t T, float* out_dev);
+MSIREN_API int msiren_sample_ragged_grad_mods(msiren_handle h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B,
+                                              int64_t T, float* out_host /* (T) or NULL */, float* grad_host /* (2, T) */);
+MSIREN_API int msiren_sample_ragged_grad_mods_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B,
+                                                  int64_t T, float* out_dev /* (T) or NULL */, float* grad_dev /* (2, T) */);
+
+/* Build-defined: the reconstruction of msiren_reconstruct_slices at arbitrary points, and its gradient.
+ * points (M, 2) = (Y, X) in RECONSTRUCTION PIXEL coordinates -- integer (Y, X) is the centre of recon[Y, X] -- one set shared by the n
+ * slices; out (n, M); grad PLANAR (2, n, M), per reconstruction pixel, plane 0 along the rows.
+ * With pad = (S - I) / 2, tile (v, h) of a slice covers a point iff  v I - pad <= Y <= v I - pad + S - 1  and likewise for X (closed
+ * ends; the fp32 coordinate is compared with the integers as it is).  For a covering tile, in fp64 and rounded once to fp32:
+ *     ty = Y - (v I - pad),  local coordinate x = -1 + ty 2 / (S - 1),  w = exp(-0.1 sqrt((ty - c)^2 + (tx - c)^2)),  c = (S - 1) / 2
+ *     out[s, m] = sum_k w_k val_k / sum_k w_k,   grad[., s, m] = (2 / (S - 1)) sum_k w_k g_k / sum_k w_k       (fp32)
+ * over the (at most ceil(S / I)^2) covering tiles in (v, h) row-major order: val_k, g_k the exact-fp32 trunk's value and gradient of tile
+ * k at the local coordinate, 0 for a black tile (which still counts with its weight).  At integer pixels this is the weighted fold of
+ * msiren_reconstruct_slices (_grad) on an fp32 handle; between pixels the blend jumps where a tile's cover begins or ends, as the
+ * fold's does from pixel to pixel.  The derivative of the weights is not part of grad.
+ * A point no tile covers and a non-finite point give NaN at that m and touch nothing else; a point under black tiles only gives 0.
+ * The pipeline, on the call's stream: tiling -> black flags -> plan -> the handle's own prologue (msiren_reconstruct_slices' steps) ->
+ * the points binned by tile -> the ragged exact-fp32 trunk (ALWAYS exact fp32; the _grad forms take what the gradient calls take) ->
+ * blend.  The order of the points does not influence any output bit.  8 M K and 12 n M K (K = ceil(S / I)^2) must stay below 2^31
+ * (MSIREN_E_INVALID beyond); ceil(S / I) <= 4.  n = 0 or M = 0 does nothing.  Host-pointer forms: synchronous one-chunk calls. */
+MSIREN_API int msiren_resample_slices(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                      const float* points_host, int64_t M, float* out_host);
+MSIREN_API int msiren_resample_slices_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                          const float* points_dev, int64_t M, float* out_dev);
+MSIREN_API int msiren_resample_slices_grad(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                           const float* points_host, int64_t M, float* out_host /* or NULL */, float* grad_host);
+MSIREN_API int msiren_resample_slices_grad_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                               const float* points_dev, int64_t M, float* out_dev /* or NULL */, float* grad_dev);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

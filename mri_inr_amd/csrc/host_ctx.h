@@ -11,6 +11,8 @@
 //     sample_grid.hip      the trunk at caller-chosen coordinates and the slice pipeline at another output stride: the per-call layer-0
 //                          table (kernel: sample_grid.hip.h), msiren_sample_*, msiren_upsampled_*, the *_scaled entry points; the
 //                          gradient calls (msiren_sample_grad_*, msiren_reconstruct_slices_grad: siren_trunk_f32_jet.hip.h)
+//     resample.hip         one coordinate set per patch: msiren_sample_ragged_* (kernels: siren_trunk_f32_ragged.hip.h), and the
+//                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -60,6 +62,7 @@ struct msiren_ctx {
         mh::DevBuf score;     // partials of msiren_score_images(_dev) (scores.hip.h)
         mh::DevBuf cscratch;  // split-fp16 Modulator: the latent part of layers 1.., lane-private (encoder_modulator_f16x3.hip.h)
         mh::DevBuf coords, l0tab;  // msiren_sample_*: the call's coordinates (host-pointer form) and its layer-0 table (sample_grid.hip)
+        mh::DevBuf ragged;         // per-patch coordinate sets (resample.hip): the item table of the ragged trunks, offsets of the host-pointer form
         struct Lattice {           // an output stride's lattice, kept per stream until the next msiren_commit_weights (sample_grid.hip)
             int out_stride = 0, tile = 0, pad = 0;  // I', S', pad'
             float *coords = nullptr, *table = nullptr, *foldw = nullptr;  // (S'S', 2); (H/4, S'S', 4) or null (fp32 trunk); (S', S')
@@ -217,6 +220,19 @@ int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, in
 int jet_supported(msiren_ctx* h);  // 0, or MSIREN_E_INVALID: dim_hidden > 256 / residual (what the jet trunk does not take)
 int launch_trunk_f32_jet(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev /* may be null */, float* grad_dev, float gscale);
 
+// One coordinate set per patch on the exact-fp32 trunks (siren_trunk_f32_ragged.hip.h), on handles of every precision.  Patch t of NP owns
+// coords[offsets[t] : offsets[t + 1]] of the T coordinates; `reps` replicas of the item range, replica s with the modulation rows of patch
+// s * NP + t (mods: (L, rows, H)), looked up through `pos` where given (negative: not evaluated).  items: scratch of NP + 1 words.
+struct RaggedSet { const float* coords; const int* offsets; int64_t T; int64_t NP; int64_t reps; const int* pos; int64_t rows; int* items; };
+int ragged_check(const RaggedSet& r, int chunk);  // 0, or MSIREN_E_INVALID: an index of the launch would leave 32 bits
+int launch_trunk_f32_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev /* (reps, T) */);
+int launch_trunk_f32_jet_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev /* may be null */, float* grad_dev /* (2, reps, T) */,
+                                float gscale);
+
+// the reconstruction of n slices at M points shared by them (resample.hip.h); grad: out_dev may be null, grad_dev (2, n, M)
+int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad);  // 0, or MSIREN_E_INVALID: the model, or too many points
+int resample_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
+                    float* grad_dev, bool grad);
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 

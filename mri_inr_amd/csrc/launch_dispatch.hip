@@ -13,14 +13,18 @@
 #include "siren_trunk_f16x3w.hip.h"
 #include "siren_trunk_f32.hip.h"
 #include "siren_trunk_f32_jet.hip.h"
+#include "siren_trunk_f32_ragged.hip.h"
 #include "siren_trunk_x1n.hip.h"
 #include "siren_trunk_x1w.hip.h"
 #include "tiling.hip.h"
+#include "resample.hip.h"
 #include "launch_dispatch.h"
 
 namespace msiren {  // the trunk / prologue kernels are compiled in their own translation units (k_*.hip)
 MSIREN_TRUNK_INSTANCES(MSIREN_EXTERN_TRUNK)
 MSIREN_F32_JET_INSTANCES(MSIREN_EXTERN_TRUNK)
+MSIREN_F32_RAGGED_INSTANCES(MSIREN_EXTERN_TRUNK)
+MSIREN_F32_JET_RAGGED_INSTANCES(MSIREN_EXTERN_TRUNK)
 MSIREN_PROLOGUE_INSTANCES(MSIREN_EXTERN_PROLOGUE)
 }  // namespace msiren
 
@@ -60,6 +64,16 @@ const JetInstance kJetInstances[] = {
 #define MSIREN_JET_ROW(fam, hp, act) {(const void*)msiren::siren_trunk_##fam##_kernel<hp, act>, "siren_trunk_" #fam "_kernel<" #hp "," #act ">", hp, act},
     MSIREN_F32_JET_INSTANCES(MSIREN_JET_ROW)
 #undef MSIREN_JET_ROW
+};
+
+// The ragged exact-fp32 trunks' instances (lists of their own as well): res = -1 marks the jet form
+struct RaggedInstance { const void* k; const char* name; int HP, act, res; };
+const RaggedInstance kRaggedInstances[] = {
+#define MSIREN_RAGGED_ROW(fam, hp, act, res) {(const void*)msiren::siren_trunk_##fam##_kernel<hp, act, res>, "siren_trunk_" #fam "_kernel<" #hp "," #act "," #res ">", hp, act, res},
+#define MSIREN_JET_RAGGED_ROW(fam, hp, act) {(const void*)msiren::siren_trunk_##fam##_kernel<hp, act>, "siren_trunk_" #fam "_kernel<" #hp "," #act ">", hp, act, -1},
+    MSIREN_F32_RAGGED_INSTANCES(MSIREN_RAGGED_ROW) MSIREN_F32_JET_RAGGED_INSTANCES(MSIREN_JET_RAGGED_ROW)
+#undef MSIREN_RAGGED_ROW
+#undef MSIREN_JET_RAGGED_ROW
 };
 
 // Launch of kernel `k` with `lds` bytes of dynamic LDS on stream `s` of the handle.  The kernel's LDS limit is raised once per handle.
@@ -363,6 +377,62 @@ int launch_trunk_f32_jet(msiren_ctx* h, const Call& c, const float* mods_dev, in
     hipEvent_t e1 = nullptr;
     if ((rc = profile_begin(h, c.stream, &e1)) || (rc = launch_kernel(h, c.stream, ji->k, B * chunks, msiren::jet_lds_bytes(h->HP), p))) return rc;
     return profile_end(h, c.stream, e1, B * c.P(h), ji->name);
+}
+
+// ---- one coordinate set per patch (siren_trunk_f32_ragged.hip.h) ----
+// Every index of the launch in 32 bits: coordinates and patches below 2^30 (the unit checks above are the model), the grid of
+// reps * (ceil(T / chunk) + NP) workgroups and the reps * T outputs below 2^31.
+int ragged_check(const RaggedSet& r, int chunk) {
+    if (r.T < 0 || r.NP < 0 || r.reps < 1 || r.T > 0x3fffffffLL || r.NP > 0x3fffffffLL)
+        return fail(MSIREN_E_INVALID, "per-patch coordinate sets: %lld coordinates over %lld patches are too many for one call (2^30 - 1 each)", (long long)r.T, (long long)r.NP);
+    const int64_t bound = (r.T + chunk - 1) / chunk + r.NP;
+    if (r.reps * bound > 0x7fffffffLL || r.reps * r.T > 0x7fffffffLL || r.reps * r.NP > 0x7fffffffLL)
+        return fail(MSIREN_E_INVALID, "per-patch coordinate sets: %lld x (%lld coordinates, %lld patches) are too many for one call", (long long)r.reps, (long long)r.T, (long long)r.NP);
+    return 0;
+}
+
+// item table, then the trunk over the upper bound of items (the device-side total sends the surplus workgroups home).  grad_dev null: values
+// only (siren_trunk_f32_ragged_kernel, what the fp32 trunk takes); else the jet (jet_supported).  The profile report names the kernels like
+// the jet's, outside the trunk totals; msiren_last_trunk_kernel does not.
+static int launch_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev, float* grad_dev, float gscale) {
+    const int chunk = grad_dev ? 32 : 64;
+    int rc = grad_dev ? jet_supported(h) : 0;
+    if (rc || (rc = ragged_check(r, chunk))) return rc;
+    if (r.T == 0 || r.NP == 0) return 0;
+    if (!grad_dev && !out_dev) return fail(MSIREN_E_INVALID, "null output");
+    const int act = h->cfg.activation == MSIREN_ACT_MORLET ? 1 : 0, res = grad_dev ? -1 : h->cfg.residual ? 1 : 0;
+    const RaggedInstance* ri = std::begin(kRaggedInstances);
+    while (ri != std::end(kRaggedInstances) && (ri->HP != h->HP || ri->act != act || ri->res != res)) ++ri;
+    if (ri == std::end(kRaggedInstances)) return fail(MSIREN_E_INVALID, "dim_hidden=%d (padded %d) is not supported by the exact-fp32 trunks", h->H, h->HP);
+    const float* mods = mods_dev;
+    int stride = h->H;
+    if ((rc = pad_mods(h, c, r.rows, &mods, &stride))) return rc;
+    msiren::TrunkRaggedParams p{};
+    Call plain = c;  // (the coordinates and the plan reach the kernel through the ragged fields)
+    plain.cs = CoordSet{};
+    plain.plan = nullptr;
+    p.t = make_trunk_params(h, plain, mods, stride, r.rows, out_dev);
+    p.t.grid = r.coords;
+    p.offsets = r.offsets, p.first = r.items, p.pos = r.pos, p.grad = grad_dev, p.gscale = gscale;
+    p.NP = (int)r.NP, p.T = (int)r.T, p.reps = (int)r.reps;
+    p.bound = (int)((r.T + chunk - 1) / chunk + r.NP);
+    hipStream_t st = h->sc[c.stream].s;
+    if (grad_dev) hipLaunchKernelGGL(msiren::ragged_items_kernel<32>, dim3(1), dim3(256), 0, st, r.offsets, p.NP, p.T, r.items);
+    else hipLaunchKernelGGL(msiren::ragged_items_kernel<64>, dim3(1), dim3(256), 0, st, r.offsets, p.NP, p.T, r.items);
+    HIPCHK(hipGetLastError());
+    const int lds = grad_dev ? msiren::jet_lds_bytes(h->HP) : h->HP * 256 + h->HP * 16;
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1)) || (rc = launch_kernel(h, c.stream, ri->k, r.reps * p.bound, lds, p))) return rc;
+    return profile_end(h, c.stream, e1, r.reps * r.T, ri->name);
+}
+
+int launch_trunk_f32_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev) {
+    return launch_ragged(h, c, r, mods_dev, out_dev, nullptr, 1.f);
+}
+
+int launch_trunk_f32_jet_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev, float* grad_dev, float gscale) {
+    if (!grad_dev) return fail(MSIREN_E_INVALID, "null gradient output");
+    return launch_ragged(h, c, r, mods_dev, out_dev, grad_dev, gscale);
 }
 
 // Behind every split-fp16 trunk launch, on the same stream: the exact-fp32 trunk over the same batch as a conditional launch
@@ -725,25 +795,20 @@ int msiren_patches_to_image_dev(msiren_handle h, const float* tiles_dev, int64_t
 
 namespace mh {
 
-// filter -> model -> reintegrate -> weighted fold on tiles that are already on the device (the call's stream)
-// `images_dev` given: `patches` is scratch that image_to_patches fills; null: `patches` are the caller's tiles
-// `og` (with c.cs): the output side at another stride (msiren_*_scaled); null: the model's own S, I and fold weights
-static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw,
-                             const float* patches_ro, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og,
-                             const GradOut* go = nullptr) {
+// What every slice call runs in front of its trunk: tiling -> black flags -> device-side plan -> the handle's prologue over the kept tiles.
+// Leaves the black flags in sc.keep, the plan in sc.plan, the kept tiles' modulations in sc.mods; *pc: the call with the plan attached.
+// `images_dev` given: `patches_rw` is scratch that image_to_patches fills; null: `patches_ro` are the caller's tiles
+static int slice_prologue(msiren_handle h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw, const float* patches_ro,
+                          int64_t n, int32_t nV, int32_t nH, Call* pc, bool* fused_out) {
     int rc;
     auto& sc = h->sc[c.stream];
     const int64_t NP = n * nV * nH;
-    const int P = c.P(h), upp = (P + 31) / 32;
-    const int oS = og ? og->tile : h->S, oI = og ? og->stride : h->I, opad = og ? og->pad : (h->S - h->I) / 2;
-    const float* foldw = og ? og->foldw : h->d_foldw;
+    const int upp = (c.P(h) + 31) / 32;
     if (NP > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "too many patches for one call: %lld", (long long)NP);
     if ((rc = ensure(h, sc.keep, (size_t)(NP + 64) * sizeof(int)))) return rc;
-    if ((rc = ensure(h, sc.rec, (size_t)NP * P * sizeof(float) * (go ? 3 : 1)))) return rc;  // (go: [value][d/d row][d/d column])
     if ((rc = ensure(h, sc.latent, (size_t)NP * h->Z * sizeof(float)))) return rc;
     if ((rc = ensure(h, sc.mods, (size_t)h->L * NP * h->H * sizeof(float)))) return rc;
     int* black = (int*)sc.keep.p;
-    float* rec = (float*)sc.rec.p;
     // The reference compacts the non-black tiles, runs the model on those only, and scatters zeros back
     // (tiling.py:244-303).  Same here, on the device: black flags -> list of kept patches (the "plan") ->
     // encoder / modulator / trunk over the kept patches only (their count stays on the device) -> the fold
@@ -767,10 +832,34 @@ static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images
         hipLaunchKernelGGL(msiren::compact_flags_kernel, dim3(1), dim3(256), 0, st, black, (int)NP, upp, plan);
         HIPCHK(hipGetLastError());
     }
-    Call pc = c;  // the model runs over the kept patches only: their count stays on the device
-    pc.plan = plan;
-    pc.mode.plan = true;
-    if ((rc = launch_encoder_modulator(h, pc, patches, NP, (float*)sc.latent.p, (float*)sc.mods.p))) return rc;
+    *pc = c;  // the model runs over the kept patches only: their count stays on the device
+    pc->plan = plan;
+    pc->mode.plan = true;
+    *fused_out = fused;
+    return launch_encoder_modulator(h, *pc, patches, NP, (float*)sc.latent.p, (float*)sc.mods.p);
+}
+
+// filter -> model -> reintegrate -> weighted fold on tiles that are already on the device (the call's stream)
+// `images_dev` given: `patches` is scratch that image_to_patches fills; null: `patches` are the caller's tiles
+// `og` (with c.cs): the output side at another stride (msiren_*_scaled); null: the model's own S, I and fold weights
+static int reconstruct_tiles(msiren_handle h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw,
+                             const float* patches_ro, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og,
+                             const GradOut* go = nullptr) {
+    int rc;
+    auto& sc = h->sc[c.stream];
+    const int64_t NP = n * nV * nH;
+    const int P = c.P(h);
+    const int oS = og ? og->tile : h->S, oI = og ? og->stride : h->I, opad = og ? og->pad : (h->S - h->I) / 2;
+    const float* foldw = og ? og->foldw : h->d_foldw;
+    if (NP > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "too many patches for one call: %lld", (long long)NP);
+    if ((rc = ensure(h, sc.rec, (size_t)NP * P * sizeof(float) * (go ? 3 : 1)))) return rc;  // (go: [value][d/d row][d/d column])
+    Call pc;
+    bool fused;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, patches_rw, patches_ro, n, nV, nH, &pc, &fused))) return rc;
+    int* black = (int*)sc.keep.p;
+    int* plan = (int*)sc.plan.p;
+    float* rec = (float*)sc.rec.p;
+    hipStream_t st = sc.s;
     if (go) rc = launch_trunk_f32_jet(h, pc, (const float*)sc.mods.p, NP, recon_dev ? rec : nullptr, rec + (size_t)NP * P, go->gscale);
     else rc = launch_trunk(h, pc, (const float*)sc.mods.p, NP, rec);
     if (rc) return rc;
@@ -809,6 +898,81 @@ int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, 
     auto& sc = h->sc[c.stream];
     if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float)))) return rc;
     return reconstruct_tiles(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, recon_dev, og, go);
+}
+
+// The reconstruction at arbitrary points (kernels: resample.hip.h): the slice prologue, then on the same stream
+// bin the points by covering tile -> ragged exact-fp32 trunk, replicated over the slices, patch s NP + t on the plan's row -> blend.
+// `grad`: value (out_dev may be null) and the two gradient planes grad_dev (2, n, M), per reconstruction pixel.
+int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad) {
+    int rc;
+    if (grad ? (rc = jet_supported(h)) : 0) return rc;
+    if (n < 0 || M < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, M=%lld)", (long long)n, (long long)M);
+    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    if (KA > msiren::RESAMPLE_MAX_KA)
+        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
+    int32_t nV, nH;
+    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
+    // every buffer of the call below 2^31 bytes, every index in 32 bits: the entries' coordinates (8 bytes each), the trunk's three planes
+    if (M > 0x0fffffffLL || n > 0x0fffffffLL || M * K * 8 > 0x7fffffffLL || n * M * K * 12 > 0x7fffffffLL || n * nV * nH > 0x3fffffffLL)
+        return fail(MSIREN_E_INVALID, "too many points for one call: %lld points x %d covering tiles x %lld slices (8 M K and 12 n M K must stay below 2^31)",
+                    (long long)M, K, (long long)n);
+    return 0;
+}
+
+int resample_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M,
+                    float* out_dev, float* grad_dev, bool grad) {
+    int rc = resample_check(h, n, height, width, M, grad);
+    if (rc) return rc;
+    if (n > 0 && M > 0 && (!images_dev || !points_dev || (grad ? !grad_dev : !out_dev))) return fail(MSIREN_E_INVALID, "null argument");
+    if (n == 0 || M == 0) return 0;
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    int32_t nV, nH;
+    (void)msiren_recon_shape(h, height, width, &nV, &nH);
+    const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, T = M * K;
+    if ((uintptr_t)points_dev % 8) return fail(MSIREN_E_INVALID, "device points must be 8-byte aligned (they are read as (row, column) pairs)");
+    const int padr = (h->O - h->I) / 2;
+    const int vpad = (h->I - height % h->I) % h->I, hpad = (h->I - width % h->I) % h->I;
+    if (padr + vpad >= height || padr + hpad >= width)  // the rule of msiren_image_to_patches_dev
+        return fail(MSIREN_E_INVALID, "image %dx%d is too small for reflect padding of %d/%d", height, width, padr + vpad, padr + hpad);
+    auto& sc = h->sc[c.stream];
+    // bins in the stream's scratch: [counts NPt][cursors NPt][offsets NPt + 1][items NPt + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T]
+    const size_t nint = (size_t)(4 * NPt + 2 + 2 * T + 1) & ~(size_t)1;
+    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, (nint + 3 * (size_t)T) * 4)) ||
+        (rc = ensure(h, sc.rec, (size_t)n * T * sizeof(float) * (grad ? 3 : 1))))
+        return rc;
+    Call pc;
+    bool fused;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &pc, &fused))) return rc;
+    hipStream_t st = sc.s;
+    int* const ib = (int*)sc.ragged.p;
+    msiren::ResampleParams rp{points_dev, (int)M, nV, nH, h->S, h->I, (h->S - h->I) / 2, KA};
+    rp.counts = ib, rp.cursors = ib + NPt, rp.offsets = ib + 2 * NPt;
+    int* const items = rp.offsets + NPt + 1;
+    rp.ent = items + NPt + 1, rp.tile = rp.ent + T, rp.coords = (float*)(ib + nint), rp.w = rp.coords + 2 * T;
+    const unsigned gm = (unsigned)((M + 255) / 256);
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+    HIPCHK(hipMemsetAsync(ib, 0, (size_t)2 * NPt * sizeof(int), st));
+    hipLaunchKernelGGL(msiren::resample_count_kernel, dim3(gm), dim3(256), 0, st, rp);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, rp.counts, (int)NPt, rp.offsets);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::resample_fill_kernel, dim3(gm), dim3(256), 0, st, rp);
+    HIPCHK(hipGetLastError());
+    if ((rc = profile_end(h, c.stream, e1, M, "resample_bin_kernels"))) return rc;
+    float* const rec = (float*)sc.rec.p;  // [value (n, T)][d/d row][d/d column]
+    const int* plan = (const int*)sc.plan.p;
+    const RaggedSet r{rp.coords, rp.offsets, T, NPt, n, plan + 2 + NP, NP, items};
+    const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
+    if (grad) rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, out_dev ? rec : nullptr, rec + (size_t)n * T, gscale);
+    else rc = launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
+    if (rc || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    const unsigned gb = (unsigned)((n * M + 255) / 256);
+    if (out_dev) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, out_dev, (int)n, (int)M, K, (int)NPt, (int)T, 1);
+    if (grad) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec + (size_t)n * T, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, grad_dev, (int)n, (int)M, K, (int)NPt, (int)T, 2);
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, n * M, "resample_blend_kernel");
 }
 
 // msiren_weighted_fold_dev with the output side of another stride (kernel S', stride I', padding pad'): complete tiles, no black flags

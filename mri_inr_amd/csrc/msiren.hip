@@ -213,7 +213,7 @@ int msiren_destroy(msiren_handle h) {
         if (p) (void)hipFree(p);
     std::vector<DevBuf*> bufs = {&h->ws_out, &h->ws_tiles, &h->ws_in, &h->ws_img};
     for (auto& c : h->sc)
-        for (DevBuf* b : {&c.cscratch, &c.mods, &c.modpad, &c.latent, &c.patches, &c.keep, &c.rec, &c.queue, &c.feat, &c.plan, &c.score, &c.coords, &c.l0tab}) bufs.push_back(b);
+        for (DevBuf* b : {&c.cscratch, &c.mods, &c.modpad, &c.latent, &c.patches, &c.keep, &c.rec, &c.queue, &c.feat, &c.plan, &c.score, &c.coords, &c.l0tab, &c.ragged}) bufs.push_back(b);
     for (DevBuf* b : bufs)
         if (b->p) (void)hipFree(b->p);
     for (auto& pr : h->prof_events) {

@@ -1,0 +1,156 @@
+// One coordinate set per patch (include/msiren.h): msiren_sample_ragged_* -- SirenNet.forward, and its spatial
+// gradient, with patch b evaluated at coords[offsets[b] : offsets[b + 1]].  Always the exact-fp32 trunks, on handles of every precision
+// (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
+#include "host_buffers.h"
+#include "host_ctx.h"
+
+using namespace mh;
+
+namespace {
+
+// what both forms check before anything is enqueued; `grad`: the jet's limits on the model (jet_supported)
+int check_ragged_args(msiren_ctx* h, const float* coords, const int32_t* offsets, const float* mods, int64_t B, int64_t T, const float* out, const float* grad_out,
+                      bool grad, RaggedSet* r) {
+    int rc = check(h);
+    if (rc || (grad && (rc = jet_supported(h)))) return rc;
+    if (!grad && h->HP > 512) return fail(MSIREN_E_INVALID, "dim_hidden=%d (padded %d) is not supported by the exact-fp32 trunks", h->H, h->HP);
+    if (B < 0 || T < 0) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld, T=%lld)", (long long)B, (long long)T);
+    *r = RaggedSet{coords, offsets, T, B, 1, nullptr, B, nullptr};
+    if ((rc = ragged_check(*r, grad ? 32 : 64))) return rc;
+    if (B > 0 && T > 0 && (!coords || !offsets || !mods || (grad ? !grad_out : !out))) return fail(MSIREN_E_INVALID, "null argument");
+    return 0;
+}
+
+int ragged_dev(msiren_ctx* h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B, int64_t T, float* out_dev, float* grad_dev, bool grad) {
+    RaggedSet r;
+    int rc = check_ragged_args(h, coords_dev, offsets_dev, mods_dev, B, T, out_dev, grad_dev, grad, &r);
+    if (rc || B == 0 || T == 0) return rc;
+    if ((uintptr_t)coords_dev % 8) return fail(MSIREN_E_INVALID, "device coordinates must be 8-byte aligned (they are read as (row, column) pairs)");
+    if ((uintptr_t)offsets_dev % 4) return fail(MSIREN_E_INVALID, "device offsets must be 4-byte aligned");
+    const Call c = dev_call(h);
+    auto& sc = h->sc[c.stream];
+    if ((rc = ensure(h, sc.ragged, (size_t)(B + 1) * sizeof(int)))) return rc;
+    r.items = (int*)sc.ragged.p;
+    return grad ? launch_trunk_f32_jet_ragged(h, c, r, mods_dev, out_dev, grad_dev, 1.0f) : launch_trunk_f32_ragged(h, c, r, mods_dev, out_dev);
+}
+
+// one synchronous one-chunk call on host pointers, as the sampling calls: coords + offsets + mods -> [out], [grad]
+int ragged_host(msiren_ctx* h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B, int64_t T, float* out_host, float* grad_host,
+                bool grad) {
+    RaggedSet r;
+    int rc = check_ragged_args(h, coords_host, offsets_host, mods_host, B, T, out_host, grad_host, grad, &r);
+    if (rc || B == 0 || T == 0) return rc;
+    if (offsets_host[0] != 0 || offsets_host[B] != T) return fail(MSIREN_E_INVALID, "offsets must run from 0 to T=%lld, got %d .. %d", (long long)T, offsets_host[0], offsets_host[B]);
+    for (int64_t b = 0; b < B; ++b)
+        if (offsets_host[b + 1] < offsets_host[b]) return fail(MSIREN_E_INVALID, "offsets must be non-decreasing: offsets[%lld] = %d > offsets[%lld] = %d", (long long)b, offsets_host[b], (long long)b + 1, offsets_host[b + 1]);
+    Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
+    const size_t nc = (size_t)T * 2 * sizeof(float), nf = (size_t)(B + 1) * sizeof(int), no = (size_t)T * sizeof(float);
+    const size_t ni = (size_t)h->L * B * h->H * sizeof(float);
+    if ((rc = ensure(h, sc.coords, nc)) || (rc = ensure(h, sc.ragged, 2 * nf)) || (rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, h->ws_out, no)) ||
+        (grad && (rc = ensure(h, h->ws_img, 2 * no))))
+        return rc;
+    const HostSrc csrc(coords_host, nc), osrc(offsets_host, nf), src(mods_host, ni);
+    const HostDst dst(out_host, out_host ? no : 0), gdst(grad_host, grad ? 2 * no : 0);
+    HOSTBUF_OK(csrc);
+    HOSTBUF_OK(osrc);
+    HOSTBUF_OK(src);
+    HOSTBUF_OK(dst);
+    HOSTBUF_OK(gdst);
+    DrainOnExit drain(h);
+    int* const d_off = (int*)sc.ragged.p;  // [offsets (B + 1)][item table (B + 1)]
+    HIPCHK(hipMemcpyAsync(sc.coords.p, csrc.as<float>(), nc, hipMemcpyHostToDevice, sc.s));
+    HIPCHK(hipMemcpyAsync(d_off, osrc.as<int>(), nf, hipMemcpyHostToDevice, sc.s));
+    HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));  // (modulations are read once per item: copied)
+    r.coords = (const float*)sc.coords.p, r.offsets = d_off, r.items = d_off + (B + 1);
+    float* const d_out = !out_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_out.p;
+    float* const d_grad = !grad ? nullptr : gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_img.p;
+    rc = grad ? launch_trunk_f32_jet_ragged(h, c, r, (const float*)h->ws_in.p, d_out, d_grad, 1.0f) : launch_trunk_f32_ragged(h, c, r, (const float*)h->ws_in.p, d_out);
+    if (rc) return rc;
+    if (d_out && d_out == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
+    if (d_grad && d_grad == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_img.p, 2 * no, hipMemcpyDeviceToHost, sc.s));
+    HIPCHK(hipStreamSynchronize(sc.s));
+    drain.disarm();
+    dst.finish();
+    gdst.finish();
+    return 0;
+}
+
+// the reconstruction at points, one synchronous one-chunk call on host pointers: images + points -> [out], [grad]
+int resample_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
+                  float* grad_host, bool grad) {
+    int rc = check(h);
+    if (rc || (rc = resample_check(h, n, height, width, M, grad))) return rc;
+    if (n == 0 || M == 0) return 0;
+    if (!images_host || !points_host || (grad ? !grad_host : !out_host)) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
+    const size_t ni = (size_t)n * height * width * sizeof(float), np = (size_t)M * 2 * sizeof(float), no = (size_t)n * M * sizeof(float);
+    if ((rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, sc.coords, np)) || (rc = ensure(h, h->ws_out, no)) || (grad && (rc = ensure(h, h->ws_img, 2 * no)))) return rc;
+    const HostSrc src(images_host, ni), psrc(points_host, np);
+    const HostDst dst(out_host, out_host ? no : 0), gdst(grad_host, grad ? 2 * no : 0);
+    HOSTBUF_OK(src);
+    HOSTBUF_OK(psrc);
+    HOSTBUF_OK(dst);
+    HOSTBUF_OK(gdst);
+    DrainOnExit drain(h);
+    HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
+    HIPCHK(hipMemcpyAsync(sc.coords.p, psrc.as<float>(), np, hipMemcpyHostToDevice, sc.s));
+    float* const d_out = !out_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_out.p;
+    float* const d_grad = !grad ? nullptr : gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_img.p;
+    if ((rc = resample_slices(h, c, (const float*)h->ws_in.p, n, height, width, (const float*)sc.coords.p, M, d_out, d_grad, grad))) return rc;
+    if (d_out && d_out == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
+    if (d_grad && d_grad == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_img.p, 2 * no, hipMemcpyDeviceToHost, sc.s));
+    HIPCHK(hipStreamSynchronize(sc.s));
+    drain.disarm();
+    dst.finish();
+    gdst.finish();
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int msiren_resample_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return resample_host(h, images_host, n, height, width, points_host, M, out_host, nullptr, false);
+}
+int msiren_resample_slices_grad(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
+                                float* grad_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return resample_host(h, images_host, n, height, width, points_host, M, out_host, grad_host, true);
+}
+int msiren_resample_slices_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    return resample_slices(h, dev_call(h), images_dev, n, height, width, points_dev, M, out_dev, nullptr, false);
+}
+int msiren_resample_slices_grad_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
+                                    float* grad_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    return resample_slices(h, dev_call(h), images_dev, n, height, width, points_dev, M, out_dev, grad_dev, true);
+}
+
+int msiren_sample_ragged_mods(msiren_handle h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B, int64_t T, float* out_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return ragged_host(h, coords_host, offsets_host, mods_host, B, T, out_host, nullptr, false);
+}
+int msiren_sample_ragged_mods_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B, int64_t T, float* out_dev) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return ragged_dev(h, coords_dev, offsets_dev, mods_dev, B, T, out_dev, nullptr, false);
+}
+int msiren_sample_ragged_grad_mods(msiren_handle h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B, int64_t T, float* out_host,
+                                   float* grad_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return ragged_host(h, coords_host, offsets_host, mods_host, B, T, out_host, grad_host, true);
+}
+int msiren_sample_ragged_grad_mods_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B, int64_t T, float* out_dev,
+                                       float* grad_dev) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return ragged_dev(h, coords_dev, offsets_dev, mods_dev, B, T, out_dev, grad_dev, true);
+}
+
+}  // extern "C"

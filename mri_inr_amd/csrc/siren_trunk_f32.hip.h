@@ -75,11 +75,20 @@ __device__ __forceinline__ float dot4_acc(float part, const f32x4 a, const f32x4
     return part + (s01 + s23);
 }
 
+// Where one work item's inputs and outputs are: a chunk of a coordinate set and the modulation rows that go with it.  The kernels over a
+// set shared by the batch (below) and the ones over one set per patch (siren_trunk_f32_ragged.hip.h) differ in nothing else.
+struct ItemSpan {
+    int b;                // modulation row: p.mods[(l * p.B + b) * p.mod_stride ...]
+    const float* coords;  // the set, (count, 2)
+    int first, count;     // the chunk's first coordinate; the size of the set (a ragged last chunk clamps inside it and stores only its own)
+    float* out;           // output of the set's coordinate 0 (the jet trunk: may be null)
+};
+
 // DBG = 1 is a separate diagnostic instantiation (msiren_trunk_timeline): wave 0 of every workgroup
 // stamps s_memtime at each phase boundary into p.stamps; the shipped kernel (DBG = 0) has no stamps.
-// One work item = (patch, chunk of 64 coordinates) = `item`; the kernels below are the callers.
+// One work item = (modulation row, chunk of 64 coordinates) = `sp`; `item` numbers it for the stamps.
 template <int HP, int ACT, int RES, int DBG>
-__device__ __forceinline__ void siren_trunk_f32_item(const TrunkParams& p, const int item) {
+__device__ __forceinline__ void siren_trunk_f32_body(const TrunkParams& p, const ItemSpan& sp, const int item) {
     constexpr int TT = HP / 128;  // 32-feature tiles per wave
     constexpr int QN = HP / 8;    // k-blocks of 8 per layer (16*TT/2 MFMAs each)
     constexpr int KG = HP / 4;    // k-groups of 4 (rows of the X image)
@@ -93,9 +102,7 @@ __device__ __forceinline__ void siren_trunk_f32_item(const TrunkParams& p, const
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
     const int c32 = lane & 31;
-    const int b = item / p.chunks;
-    const int ch = item - b * p.chunks;
-    if (p.plan && b >= p.plan[0]) return;  // workgroup-uniform, before any barrier
+    const int b = sp.b;
     const int L = p.L;
     int nstamp = 0;
     auto stamp = [&]() {
@@ -151,9 +158,9 @@ __device__ __forceinline__ void siren_trunk_f32_item(const TrunkParams& p, const
             w[3] = mod0[f];
             P0[f] = w;
         }
-        int pc = ch * 64 + lane;
-        pc = pc < p.P ? pc : p.P - 1;
-        const float2 xy = reinterpret_cast<const float2*>(p.grid)[pc];
+        int pc = sp.first + lane;
+        pc = pc < sp.count ? pc : sp.count - 1;
+        const float2 xy = reinterpret_cast<const float2*>(sp.coords)[pc];
         __syncthreads();
 #pragma unroll 4
         for (int i = 0; i < KG / 4; ++i) {
@@ -336,13 +343,22 @@ __device__ __forceinline__ void siren_trunk_f32_item(const TrunkParams& p, const
     __syncthreads();
     if (tid < 64) {
         const float s = red[tid] + red[64 + tid] + red[128 + tid] + red[192 + tid] + p.bout;
-        const int pc = ch * 64 + tid;
-        if (pc < p.P) p.out[(size_t)b * p.P + pc] = sin_rev(s);
+        const int pc = sp.first + tid;
+        if (pc < sp.count) sp.out[pc] = sin_rev(s);
     }
     stamp();  // end
     if constexpr (DBG) {
         if (tid == 0) p.stamps[(size_t)item * 32 + 31] = __builtin_amdgcn_s_memrealtime();
     }
+}
+
+// One work item = (patch, chunk of 64 coordinates of the set the batch shares) = `item`
+template <int HP, int ACT, int RES, int DBG>
+__device__ __forceinline__ void siren_trunk_f32_item(const TrunkParams& p, const int item) {
+    const int b = item / p.chunks;
+    const int ch = item - b * p.chunks;
+    if (p.plan && b >= p.plan[0]) return;  // workgroup-uniform, before any barrier
+    siren_trunk_f32_body<HP, ACT, RES, DBG>(p, ItemSpan{b, p.grid, ch * 64, p.P, p.out + (size_t)b * p.P}, item);
 }
 
 template <int HP, int ACT, int RES, int DBG = 0>

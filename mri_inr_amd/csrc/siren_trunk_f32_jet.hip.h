@@ -51,14 +51,15 @@ __device__ __forceinline__ float activate_d(float r, float cg) {
     }
 }
 
+// One work item = (modulation row, chunk of 32 coordinates) = `sp` (siren_trunk_f32.hip.h); grad0 / grad1: the two gradient planes'
+// entries of the set's coordinate 0.
 template <int HP, int ACT>
-__global__ __launch_bounds__(256, 1) void siren_trunk_f32_jet_kernel(TrunkJetParams pj) {
+__device__ __forceinline__ void siren_trunk_f32_jet_body(const TrunkParams& p, const ItemSpan& sp, float* grad0, float* grad1, const float gscale) {
     constexpr int TT = HP / 128;  // 32-feature tiles per wave
     constexpr int QN = HP / 8;    // k-blocks of 8 per layer
     constexpr int KG = HP / 4;    // k-groups of 4 (rows of the X image)
     constexpr int XS = 96;        // columns of the X image: 3 tiles of 32
     static_assert(HP == 128 || HP == 256, "the three-tile image fits the LDS up to a hidden width of 256");
-    const TrunkParams& p = pj.t;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     f32x4* X = reinterpret_cast<f32x4*>(lds);  // X[kg * 96 + 32 * tile + coord]   HP*384 B
     f32x4* P0 = X + KG * XS;                   // layer-0 rows {wx, wy, b, mod}    HP*16 B
@@ -68,10 +69,7 @@ __global__ __launch_bounds__(256, 1) void siren_trunk_f32_jet_kernel(TrunkJetPar
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int half = lane >> 5;
     const int c32 = lane & 31;
-    const int item = (int)blockIdx.x;
-    const int b = item / p.chunks;
-    const int ch = item - b * p.chunks;
-    if (p.plan && b >= p.plan[0]) return;  // workgroup-uniform, before any barrier
+    const int b = sp.b;
     const int L = p.L;
 
     // ---------------- weight stream: the ring of siren_trunk_f32_item ---------------------------
@@ -100,9 +98,9 @@ __global__ __launch_bounds__(256, 1) void siren_trunk_f32_jet_kernel(TrunkJetPar
             w[3] = mod0[f];
             P0[f] = w;
         }
-        int pc = ch * 32 + c32;
-        pc = pc < p.P ? pc : p.P - 1;
-        const float2 xy = reinterpret_cast<const float2*>(p.grid)[pc];
+        int pc = sp.first + c32;
+        pc = pc < sp.count ? pc : sp.count - 1;
+        const float2 xy = reinterpret_cast<const float2*>(sp.coords)[pc];
         __syncthreads();
 #pragma unroll 2
         for (int i = 0; i < KG / 8; ++i) {
@@ -283,15 +281,25 @@ __global__ __launch_bounds__(256, 1) void siren_trunk_f32_jet_kernel(TrunkJetPar
         const float s = red[tid] + red[32 + tid] + red[64 + tid] + red[96 + tid] + p.bout;
         const float sx = red[128 + tid] + red[160 + tid] + red[192 + tid] + red[224 + tid];
         const float sy = red[256 + tid] + red[288 + tid] + red[320 + tid] + red[352 + tid];
-        const int pc = ch * 32 + tid;
-        if (pc < p.P) {
-            const size_t o = (size_t)b * p.P + pc;
+        const int pc = sp.first + tid;
+        if (pc < sp.count) {
             const float dc = TWO_PI * cos_rev(s);
-            if (p.out) p.out[o] = sin_rev(s);
-            pj.grad[o] = (dc * sx) * pj.gscale;
-            pj.grad[(size_t)p.B * p.P + o] = (dc * sy) * pj.gscale;
+            if (sp.out) sp.out[pc] = sin_rev(s);
+            grad0[pc] = (dc * sx) * gscale;
+            grad1[pc] = (dc * sy) * gscale;
         }
     }
+}
+
+template <int HP, int ACT>
+__global__ __launch_bounds__(256, 1) void siren_trunk_f32_jet_kernel(TrunkJetParams pj) {
+    const TrunkParams& p = pj.t;
+    const int item = (int)blockIdx.x;
+    const int b = item / p.chunks;
+    const int ch = item - b * p.chunks;
+    if (p.plan && b >= p.plan[0]) return;  // workgroup-uniform, before any barrier
+    const size_t o = (size_t)b * p.P;
+    siren_trunk_f32_jet_body<HP, ACT>(p, ItemSpan{b, p.grid, ch * 32, p.P, p.out ? p.out + o : nullptr}, pj.grad + o, pj.grad + (size_t)p.B * p.P + o, pj.gscale);
 }
 
 }  // namespace msiren

@@ -32,6 +32,15 @@
 // no row of the dispatch table -- msiren_sample_grad_* / msiren_reconstruct_slices_grad launch it on every handle with H <= 256.
 #define MSIREN_F32_JET_INSTANCES(X) X(f32_jet, 128,0) X(f32_jet, 128,1) X(f32_jet, 256,0) X(f32_jet, 256,1)
 
+// The exact-fp32 trunks over one coordinate set per patch (siren_trunk_f32_ragged.hip.h; <HP,ACT,RES> and the jet's <HP,ACT>): lists of
+// their own like the jet's -- msiren_sample_ragged_* / msiren_resample_slices* launch them on handles of every precision.
+#define MSIREN_F32_RAGGED_INSTANCES(X)                                                            \
+    X(f32_ragged, 128,0,0) X(f32_ragged, 128,0,1) X(f32_ragged, 128,1,0) X(f32_ragged, 128,1,1)   \
+    X(f32_ragged, 256,0,0) X(f32_ragged, 256,0,1) X(f32_ragged, 256,1,0) X(f32_ragged, 256,1,1)   \
+    X(f32_ragged, 384,0,0) X(f32_ragged, 384,0,1) X(f32_ragged, 384,1,0) X(f32_ragged, 384,1,1)   \
+    X(f32_ragged, 512,0,0) X(f32_ragged, 512,0,1) X(f32_ragged, 512,1,0) X(f32_ragged, 512,1,1)
+#define MSIREN_F32_JET_RAGGED_INSTANCES(X) X(f32_jet_ragged, 128,0) X(f32_jet_ragged, 128,1) X(f32_jet_ragged, 256,0) X(f32_jet_ragged, 256,1)
+
 // the one-launch prologue (<family>_f16x3_kernel: encoder_modulator_f16x3.hip.h); latent_mods<NPH,NPZ,DEPTH,MODE>
 #define MSIREN_PROLOGUE_INSTANCES(X)                                                              \
     X(latent_mods, 2,2,2,3) X(latent_mods, 2,2,4,3) X(latent_mods, 2,2,8,3)                       \
@@ -43,6 +52,8 @@
 #define MSIREN_PARAMS_f32 (TrunkParams)
 #define MSIREN_PARAMS_f32_cond (TrunkParams)
 #define MSIREN_PARAMS_f32_jet (TrunkJetParams)
+#define MSIREN_PARAMS_f32_ragged (TrunkRaggedParams)
+#define MSIREN_PARAMS_f32_jet_ragged (TrunkRaggedParams)
 #define MSIREN_PARAMS_f16x3n (TrunkF16Params)
 #define MSIREN_PARAMS_f16x3h (TrunkF16Params)
 #define MSIREN_PARAMS_f16x3w (TrunkWsParams)

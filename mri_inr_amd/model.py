@@ -665,6 +665,146 @@ class ModulatedSiren:
         return self._sample(self._lib.msiren_sample_grad_mods, self._lib.msiren_sample_grad_mods_dev, mods, coords,
                             (self.num_layers, None, self.dim_hidden), 1, grad=True)
 
+    # ---- one coordinate set per patch: always the exact-fp32 trunks ----
+    def _sample_ragged(self, host_fn, dev_fn, mods, coords, offsets, grad):
+        """Marshalling of sample_mods_ragged(_grad): ``mods`` and ``coords`` as in _sample (numpy / torch / DeviceArray), ``offsets``
+        (B + 1) integers on the host (numpy, torch, a sequence) -- checked here and uploaded -- or an int32 device tensor.  Any device
+        operand takes the *_dev entry point.  The result follows ``mods``: a DeviceArray or device tensor gives device outputs."""
+        if isinstance(mods, (tuple, list)):
+            if _is_torch(mods[0]):
+                import torch
+
+                mods = torch.stack(list(mods), 0)
+            else:
+                mods = np.stack([np.asarray(m) for m in mods], 0)
+        self._ensure_handle()
+        self._ensure_committed()
+        m_t = _is_torch(mods)
+        cshape = tuple(coords.shape)
+        if len(cshape) != 2 or cshape[1] != 2:
+            raise ValueError(f"expected coords of shape (T, 2), got {cshape}")
+        T = cshape[0]
+        self._check_tail(tuple(mods.shape), (self.num_layers, None, self.dim_hidden))
+        B = int(mods.shape[1])
+        o_dev = _is_torch(offsets) and offsets.is_cuda
+        if tuple(offsets.shape if hasattr(offsets, "shape") else np.shape(offsets)) != (B + 1,):
+            raise ValueError(f"expected offsets of shape ({B + 1},) for {B} patches, got {tuple(np.shape(offsets))}")
+        if not o_dev:
+            o64 = np.asarray(offsets.detach().cpu().numpy() if _is_torch(offsets) else offsets)
+            if o64.dtype.kind not in "iu":
+                raise ValueError(f"offsets must be integers, got {o64.dtype}")
+            o64 = o64.astype(np.int64)
+            if o64[0] != 0 or o64[-1] != T or np.any(np.diff(o64) < 0):
+                raise ValueError(f"offsets must be non-decreasing from 0 to T={T}, got {o64.tolist() if B < 16 else o64}")
+            off = np.ascontiguousarray(o64, dtype=np.int32)
+        m_dev = isinstance(mods, DeviceArray) or (m_t and mods.is_cuda)
+        c_dev = isinstance(coords, DeviceArray) or (_is_torch(coords) and coords.is_cuda)
+        shapes = [(T,), (2, T)] if grad else [(T,)]
+        if B == 0 or T == 0:  # nothing to evaluate: no call
+            outs = [np.empty(shape, dtype=np.float32) for shape in shapes]
+            if m_t:
+                import torch
+
+                outs = [torch.from_numpy(o) for o in outs]
+            return tuple(outs) if grad else outs[0]
+        keep = []  # device arrays of this call stay alive until the sync below
+
+        def host_array(a):
+            return np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float32)
+
+        def dev_ptr(a, dtype=np.float32):
+            if isinstance(a, DeviceArray):
+                return a.ptr
+            if _is_torch(a) and a.is_cuda:
+                import torch
+
+                if a.device.index != self._device:
+                    raise ValueError(f"input is on cuda:{a.device.index}, model on cuda:{self._device}")
+                t = a.detach().to(torch.float32 if dtype == np.float32 else torch.int32).contiguous()
+                torch.cuda.current_stream(a.device).synchronize()
+                keep.append(t)
+                return t.data_ptr()
+            hst = host_array(a) if dtype == np.float32 else a
+            d = self.device_array(hst.shape)
+            _lib.check(self._lib.msiren_memcpy_h2d(self._h, d.ptr, hst.ctypes.data, hst.nbytes))  # (4-byte elements either way)
+            keep.append(d)
+            return d.ptr
+
+        if not (m_dev or c_dev or o_dev):
+            a, c = host_array(mods), host_array(coords)
+            outs = [np.empty(shape, dtype=np.float32) for shape in shapes]
+            _lib.check(host_fn(self._h, c.ctypes.data, off.ctypes.data, a.ctypes.data, B, T, *[o.ctypes.data for o in outs]))
+            if m_t:
+                import torch
+
+                outs = [torch.from_numpy(o) for o in outs]
+            return tuple(outs) if grad else outs[0]
+        if m_t and mods.is_cuda:
+            import torch
+
+            outs = [torch.empty(shape, dtype=torch.float32, device=mods.device) for shape in shapes]
+            ptrs = [o.data_ptr() for o in outs]
+        else:
+            outs = [self.device_array(shape) for shape in shapes]
+            ptrs = [o.ptr for o in outs]
+        _lib.check(dev_fn(self._h, dev_ptr(coords), dev_ptr(offsets if o_dev else off, np.int32), dev_ptr(mods), B, T, *ptrs))
+        _lib.check(self._lib.msiren_sync(self._h))
+        if not m_dev:
+            outs = [o.numpy() for o in outs]  # mods came from the host
+            if m_t:
+                import torch
+
+                outs = [torch.from_numpy(o) for o in outs]
+        return tuple(outs) if grad else outs[0]
+
+    def sample_mods_ragged(self, mods, coords, offsets):
+        """mods (L, B, H), coords (T, 2), offsets (B + 1) -> (T,): ``SirenNet.forward`` with patch b evaluated at its OWN coordinate
+        set ``coords[offsets[b]:offsets[b + 1]]`` (msiren_sample_ragged_mods).  Always the exact-fp32 trunk, whatever the model's
+        precision: out[offsets[b] + i] is the bits of an fp32 model's ``sample_mods(mods[:, b:b + 1], coords_b)[0, i]``."""
+        return self._sample_ragged(self._lib.msiren_sample_ragged_mods, self._lib.msiren_sample_ragged_mods_dev, mods, coords, offsets, False)
+
+    def sample_mods_ragged_grad(self, mods, coords, offsets):
+        """As sample_mods_ragged -> (values (T,), grad (2, T)): value and ``d SirenNet.forward / d coords`` per coordinate, grad[0] along
+        ``coords[:, 0]`` (rows) -- the bits of ``sample_mods_grad`` patch by patch (msiren_sample_ragged_grad_mods)."""
+        return self._sample_ragged(self._lib.msiren_sample_ragged_grad_mods, self._lib.msiren_sample_ragged_grad_mods_dev, mods, coords, offsets, True)
+
+    def _resample(self, images, points, grad):
+        self._ensure_committed()
+        a = images.detach().cpu().numpy() if _is_torch(images) else np.asarray(images)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        single = a.ndim == 2
+        if single:
+            a = a[None]
+        if a.ndim != 3:
+            raise ValueError(f"expected (n, H, W) images, got {a.shape}")
+        p = np.ascontiguousarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 2:
+            raise ValueError(f"expected points of shape (M, 2), got {p.shape}")
+        n, Hh, Ww = a.shape
+        M = p.shape[0]
+        outs = [np.empty(shape, dtype=np.float32) for shape in (((n, M), (2, n, M)) if grad else ((n, M),))]
+        fn = self._lib.msiren_resample_slices_grad if grad else self._lib.msiren_resample_slices
+        _lib.check(fn(self._h, a.ctypes.data, n, Hh, Ww, p.ctypes.data, M, *[o.ctypes.data for o in outs]))
+        if single:
+            outs = [outs[0][0]] + [o[:, 0] for o in outs[1:]]
+        if _is_torch(images):
+            import torch
+
+            outs = [torch.from_numpy(o) for o in outs]
+        return tuple(outs) if grad else outs[0]
+
+    def resample(self, images, points):
+        """images (n, Hh, Ww) or (Hh, Ww), points (M, 2) -> (n, M) or (M,): the reconstruction of ``reconstruct(images)`` read at real
+        positions ``points[m] = (Y, X)`` in reconstruction pixel coordinates (integer (Y, X): the centre of ``recon[Y, X]``), one point
+        set for all slices -- every covering tile's network evaluated at the point, blended with the fold's weights (build-defined,
+        DESIGN.md section 5.8; msiren_resample_slices).  Always the exact-fp32 trunk.  NaN where no tile covers the point."""
+        return self._resample(images, points, False)
+
+    def resample_with_gradient(self, images, points):
+        """As resample -> (values (n, M), grad (2, n, M)): grad per reconstruction pixel, grad[0] along the rows -- the weight-averaged
+        analytic gradients of the covering tiles, as ``reconstruct_with_gradient`` defines it (msiren_resample_slices_grad)."""
+        return self._resample(images, points, True)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
