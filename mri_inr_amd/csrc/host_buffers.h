@@ -1,4 +1,5 @@
-// What a caller's host buffer is to a synchronous entry point, and the RAII pieces a call wraps around it (msiren.hip uses them).
+// What a caller's host buffer is to a synchronous entry point, and the one protocol every such entry point wraps around its buffers
+// (SyncHostCall: msiren.hip, scores.hip, sample_grid.hip and resample.hip use it).
 #pragma once
 #include <cstring>
 
@@ -38,55 +39,89 @@ struct HostBounce {
     }
 };
 
-// A caller's input / output buffer of one synchronous call: `as<T>()` is what the call's copies use (the caller's pointer, or the
-// bounce buffer of a HOST_PARTIAL range), `dev<T>()` the device view of a HOST_PINNED range (nullptr otherwise: no in-place access).
-class HostSrc {
-    HostBounce b_;
-    const void* p_;
-    void* dev_ = nullptr;
-    bool ok_ = true;
+// How a synchronous call uses one of its caller's buffers.
+enum HostPolicy : unsigned {
+    // Always through device memory: staging, or the device buffer the call names.  Every input but the tiles of the sampling calls and of
+    // a one-chunk msiren_forward_tiles.  msiren_reconstruct_slices copies its image ON PURPOSE (DMA from page-locked memory, through the
+    // runtime from pageable memory): read in place every pixel would cross the link four times (32 x 32 tiles at a stride of 16;
+    // profiles/r5/09_*).  Modulations are read once per unit of the trunk: copied as well.
+    HOST_COPY = 0,
+    // The kernels read / write the range in place where it is page-locked (the device view of the caller's allocation; of the bounce
+    // buffer where the range is page-locked in part); a pageable range is copied.
+    HOST_IN_PLACE = 1,
+    // Staged, but the call enqueues the copies itself through host_src / host_dst: the chunk loops of msiren_forward_tiles and
+    // msiren_encode_modulate_tiles, whose copies go chunk by chunk on alternating streams.
+    HOST_OWN_COPIES = 2,
+    // Staged right behind the previous buffer, without alignment padding: the second image of msiren_score_images, whose kernels ask
+    // for 4-byte alignment only and whose two images have always shared one staging buffer of exactly their size.
+    HOST_PACKED = 4,
+};
 
+// One synchronous call on host pointers:
+//     SyncHostCall io(h, stream);
+//     const int a = io.in(...), b = io.out(...);   classify each buffer (once), bounce what is page-locked in part; nothing is enqueued
+//     if ((rc = io.begin())) return rc;             staging on the handle (grow-only, every size known: nothing is reallocated while the
+//                                                   call's work is queued), then the H2D copies in the order of in()
+//     ... the *_dev work on io.src<T>(a) / io.dst<T>(b) ...
+//     return io.finish();                           D2H of what was not in place, the wait, bounce buffers back to the caller
+// From begin() until a finish() that succeeded the destructor waits for the handle's streams -- a call that leaves early (a failed launch,
+// a failed copy) may have copies in flight on the caller's buffers or on a bounce buffer -- and the bounce buffers are members, so they
+// are freed behind that wait whatever the caller declares in which order.  A bounce buffer reaches the caller behind a successful wait only.
+//
+// What is used in place (everything else: copied / staged):
+//     forward_mods, forward_latent, encode_tiles, modulate, score_images   --
+//     memcpy_h2d / memcpy_d2h                                              -- (the device side is the caller's)
+//     forward_tiles, ONE chunk                  tiles; out; host-side domain check
+//     reconstruct_slices(_scaled)               recon
+//     reconstruct_slices_grad                   recon (optional), grad
+//     sample_{mods,tiles}                       tiles; out; host-side domain check
+//     sample_grad_{mods,tiles}                  tiles; out (optional), grad
+//     sample_ragged_(grad_)mods                 out (optional) / grad
+//     resample_slices(_grad)                    out (optional) / grad
+class SyncHostCall {
 public:
-    HostSrc(const void* host, size_t n) : p_(host) {
-        if (!host || !n) return;
-        if (host_range_kind(host, n, &dev_) != HOST_PARTIAL) return;
-        if (b_.alloc(n)) { std::memcpy(b_.p, host, n); p_ = b_.p; dev_ = host_pinned_dev(b_.p); } else ok_ = false;
-    }
-    bool ok() const { return ok_; }
-    template <typename T> const T* as() const { return (const T*)p_; }
-    template <typename T> const T* dev() const { return (const T*)dev_; }
-};
-class HostDst {
-    HostBounce b_;
-    void* user_;
-    void* p_;
-    void* dev_ = nullptr;
-    size_t n_;
-    bool ok_ = true;
+    static constexpr int kMax = 6;  // buffers per direction
+    // wait_all: finish() waits for all the handle's streams (sync_all) instead of `stream` alone
+    SyncHostCall(msiren_ctx* h, int stream, bool wait_all = false) : h_(h), stream_(stream), wait_all_(wait_all) {}
+    SyncHostCall(const SyncHostCall&) = delete;
+    SyncHostCall& operator=(const SyncHostCall&) = delete;
+    ~SyncHostCall();
 
-public:
-    HostDst(void* host, size_t n) : user_(host), p_(host), n_(n) {
-        if (!host || !n) return;
-        if (host_range_kind(host, n, &dev_) != HOST_PARTIAL) return;
-        if (b_.alloc(n)) { p_ = b_.p; dev_ = host_pinned_dev(b_.p); } else ok_ = false;
-    }
-    bool ok() const { return ok_; }
-    template <typename T> T* as() const { return (T*)p_; }
-    template <typename T> T* dev() const { return (T*)dev_; }
-    void finish() const { if (b_.p) std::memcpy(user_, b_.p, n_); }  // (behind the stream's synchronisation)
-};
-#define HOSTBUF_OK(x) do { if (!(x).ok()) return ::mh::fail(MSIREN_E_HIP, "no page-locked memory for a bounce buffer"); } while (0)
+    // -> the buffer's number for src / dst.  `dev`: the device memory the work reads the input from / leaves the output in (per-stream
+    // scratch such as sc.coords, sc.mods, sc.latent; ensured by the caller); null: staging.  A null `host` (an optional output left
+    // out): dst() is null, nothing is copied.
+    int in(const void* host, size_t bytes, unsigned policy, void* dev = nullptr) { return add(in_, nin_, in_bytes_, (void*)host, bytes, policy, dev, true); }
+    int out(void* host, size_t bytes, unsigned policy, const void* dev = nullptr) { return add(out_, nout_, out_bytes_, host, bytes, policy, (void*)dev, false); }
+    int begin();
+    template <typename T> const T* src(int i) const { return (const T*)device(in_[i], h_->stage_in); }
+    template <typename T> T* dst(int i) const { return (T*)device(out_[i], h_->stage_out); }
+    // the host side of a HOST_OWN_COPIES buffer: the caller's pointer, or the bounce buffer of a range that is page-locked in part
+    template <typename T> const T* host_src(int i) const { return (const T*)in_[i].p; }
+    template <typename T> T* host_dst(int i) const { return (T*)out_[i].p; }
+    int finish();  // may be called again behind further work on the stream (recheck does)
+    // The host-side domain check of a call whose trunk was launched with mode.host_check (host_ctx.h: HostCheck), behind finish(): where
+    // the trunk met a modulation outside the fp16 domain, the batch once more on the exact-fp32 trunk at the call's coordinates (the
+    // conditional kernel, its condition pointed at the word that has just been read), then finish() once more.
+    int recheck(const HostCheck& hc, const CoordSet& cs);
 
-// A synchronous call that leaves early (a failed launch, a failed copy) may have copies in flight on the caller's buffers or on a bounce
-// buffer that is about to be freed: declared BEHIND the HostSrc / HostDst objects, so it runs before they go, it waits for the handle's
-// streams unless the call has done so itself (disarm()).
-struct DrainOnExit {
-    msiren_ctx* h;
-    bool armed = true;
-    explicit DrainOnExit(msiren_ctx* hh) : h(hh) {}
-    void disarm() { armed = false; }
-    ~DrainOnExit();
-};
+private:
+    struct Item {
+        void* host = nullptr;  // the caller's pointer
+        void* p = nullptr;     // what copies use: `host`, or the bounce buffer
+        void* dev = nullptr;   // the device side: the page-locked view in place, or the buffer the call named; null: staging at `off`
+        size_t n = 0, off = 0;
+        bool copy = false;     // begin() / finish() copy it
+        HostBounce b;
+    };
+    int add(Item* items, int& count, size_t& staged, void* host, size_t n, unsigned policy, void* dev, bool input);
+    static void* device(const Item& it, const DevBuf& stage) { return !it.host ? nullptr : it.dev ? it.dev : (char*)stage.p + it.off; }
 
+    msiren_ctx* h_;
+    int stream_;
+    bool wait_all_, ok_ = true, too_many_ = false, armed_ = false;
+    int nin_ = 0, nout_ = 0;
+    size_t in_bytes_ = 0, out_bytes_ = 0;  // of staging, every buffer at a multiple of 128 (HOST_PACKED: none)
+    Item in_[kMax], out_[kMax];
+};
 
 }  // namespace mh

@@ -4,7 +4,8 @@
 //     launch_dispatch.hip  the launches of what dispatch.h picks: trunks, prologue, tiling / fold, the *_dev slice pipeline
 //     trunk_instances.h    the one list of kernel instances: k_*.hip instantiate it, the host units declare it extern
 //     weights_pack.hip     state_dict -> the kernels' weight layouts (host arithmetic + uploads)
-//     host_buffers.hip     what a caller's host range is (pageable / page-locked / page-locked in part), bounce buffers
+//     host_buffers.hip     what a caller's host range is (pageable / page-locked / page-locked in part), bounce buffers, and the one
+//                          protocol of a synchronous host-pointer call around them (SyncHostCall: every such entry point uses it)
 //     comm_rccl.hip        RCCL through dlopen: communicator, the one weight broadcast, barrier / MAX
 //     diagnostics.hip      stamped timeline builds, the sustained-MFMA probe
 //     scores.hip           PSNR / SSIM / NRMSE of image pairs (the evaluation harness's metrics; kernels: scores.hip.h)
@@ -124,7 +125,7 @@ struct msiren_ctx {
     int em_enabled = 1;            // MSIREN_PROLOGUE_F16X3=0: the exact-fp32 launches per layer on a split-fp16 handle (tests, A/B)
     float* d_foldw = nullptr;  // (S,S) overlap-add weights
     // workspaces
-    mh::DevBuf ws_out, ws_tiles, ws_in, ws_img;  // staging of the host-pointer entry points
+    mh::DevBuf stage_in, stage_out;  // staging of the host-pointer entry points, carved per call by SyncHostCall (host_buffers.h)
     // profiling
     bool profile = false;
     int64_t prof_launches = 0;
@@ -187,6 +188,10 @@ int use_device(msiren_ctx* h);
 int ensure(msiren_ctx* h, DevBuf& b, size_t bytes);                 // grow-only device workspace
 int upload(float** dst, const std::vector<float>& src);            // (re)allocate + blocking H2D copy
 int check(msiren_ctx* h, bool need_commit = true);
+// refusals that several entry points share; 0, or MSIREN_E_INVALID
+int check_tile_size(const msiren_ctx* h, bool cite = true);  // the custom encoder takes 32 x 32 tiles; cite: the wording that names the reference's line
+int check_reflect_padding(const msiren_ctx* h, int32_t height, int32_t width);  // torch's reflect padding requires pad < dim (F.pad raises otherwise)
+int check_pairs_aligned(const void* dev, const char* what);  // `what` (coordinates, points) is read as (row, column) pairs: 8-byte aligned
 int sync_all(msiren_ctx* h);
 bool take_range_flag(msiren_ctx* h);
 void next_stream(msiren_ctx* h);   // asynchronous forward entry points rotate over the configured streams

@@ -723,11 +723,7 @@ int msiren_image_to_patches_dev(msiren_handle h, const float* images_dev, int64_
     if (rc) return rc;
     if (n < 0 || height < 1 || width < 1) return fail(MSIREN_E_INVALID, "bad arguments");
     if (n == 0) return 0;
-    const int pad = (h->O - h->I) / 2;
-    const int vpad = (h->I - height % h->I) % h->I, hpad = (h->I - width % h->I) % h->I;
-    // torch's reflect padding requires pad < dim (F.pad raises otherwise)
-    if (pad + vpad >= height || pad + hpad >= width)
-        return fail(MSIREN_E_INVALID, "image %dx%d is too small for reflect padding of %d/%d", height, width, pad + vpad, pad + hpad);
+    if ((rc = check_reflect_padding(h, height, width))) return rc;
     return launch_image_to_patches(h, h->cur, images_dev, n, height, width, patches_dev);
 }
 
@@ -885,16 +881,12 @@ int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, 
     int rc;
     if (n < 0 || (n > 0 && (!images_dev || (go ? !go->grad : !recon_dev)))) return fail(MSIREN_E_INVALID, "bad arguments");
     if (go && (rc = jet_supported(h))) return rc;
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h, false))) return rc;
     if (n == 0) return 0;
     int32_t nV, nH;
     if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
     const int64_t NP = n * nV * nH;
-    const int padr = (h->O - h->I) / 2;
-    const int vpad = (h->I - height % h->I) % h->I, hpad = (h->I - width % h->I) % h->I;
-    // torch's reflect padding requires pad < dim (F.pad raises otherwise): the rule of msiren_image_to_patches_dev
-    if (padr + vpad >= height || padr + hpad >= width)
-        return fail(MSIREN_E_INVALID, "image %dx%d is too small for reflect padding of %d/%d", height, width, padr + vpad, padr + hpad);
+    if ((rc = check_reflect_padding(h, height, width))) return rc;
     auto& sc = h->sc[c.stream];
     if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float)))) return rc;
     return reconstruct_tiles(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, recon_dev, og, go);
@@ -907,7 +899,7 @@ int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int6
     int rc;
     if (grad ? (rc = jet_supported(h)) : 0) return rc;
     if (n < 0 || M < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, M=%lld)", (long long)n, (long long)M);
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h, false))) return rc;
     const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
     if (KA > msiren::RESAMPLE_MAX_KA)
         return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
@@ -930,11 +922,7 @@ int resample_slices(msiren_handle h, const Call& c, const float* images_dev, int
     int32_t nV, nH;
     (void)msiren_recon_shape(h, height, width, &nV, &nH);
     const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, T = M * K;
-    if ((uintptr_t)points_dev % 8) return fail(MSIREN_E_INVALID, "device points must be 8-byte aligned (they are read as (row, column) pairs)");
-    const int padr = (h->O - h->I) / 2;
-    const int vpad = (h->I - height % h->I) % h->I, hpad = (h->I - width % h->I) % h->I;
-    if (padr + vpad >= height || padr + hpad >= width)  // the rule of msiren_image_to_patches_dev
-        return fail(MSIREN_E_INVALID, "image %dx%d is too small for reflect padding of %d/%d", height, width, padr + vpad, padr + hpad);
+    if ((rc = check_pairs_aligned(points_dev, "points")) || (rc = check_reflect_padding(h, height, width))) return rc;
     auto& sc = h->sc[c.stream];
     // bins in the stream's scratch: [counts NPt][cursors NPt][offsets NPt + 1][items NPt + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T]
     const size_t nint = (size_t)(4 * NPt + 2 + 2 * T + 1) & ~(size_t)1;
@@ -987,7 +975,7 @@ int weighted_fold_dev(msiren_handle h, const Call& c, const float* tiles_dev, in
 
 int reconstruct_tiles_dev(msiren_handle h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og) {
     if (n < 0 || nV < 1 || nH < 1 || (n > 0 && (!tiles_dev || !recon_dev))) return fail(MSIREN_E_INVALID, "bad arguments");
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
+    if (int rc = check_tile_size(h, false)) return rc;
     if (n == 0) return 0;
     return reconstruct_tiles(h, c, nullptr, 0, 0, nullptr, tiles_dev, n, nV, nH, recon_dev, og);
 }

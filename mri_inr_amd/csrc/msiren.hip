@@ -113,6 +113,24 @@ int check(msiren_ctx* h, bool need_commit) {
     return use_device(h);
 }
 
+int check_tile_size(const msiren_ctx* h, bool cite) {
+    if (h->O == 32) return 0;
+    return cite ? fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O)
+                : fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles, outer_patch_size=%d", h->O);
+}
+
+int check_reflect_padding(const msiren_ctx* h, int32_t height, int32_t width) {
+    const int pad = (h->O - h->I) / 2;
+    const int vpad = (h->I - height % h->I) % h->I, hpad = (h->I - width % h->I) % h->I;
+    if (pad + vpad >= height || pad + hpad >= width)
+        return fail(MSIREN_E_INVALID, "image %dx%d is too small for reflect padding of %d/%d", height, width, pad + vpad, pad + hpad);
+    return 0;
+}
+
+int check_pairs_aligned(const void* dev, const char* what) {
+    if ((uintptr_t)dev % 8) return fail(MSIREN_E_INVALID, "device %s must be 8-byte aligned (they are read as (row, column) pairs)", what);
+    return 0;
+}
 
 }  // namespace mh
 
@@ -211,7 +229,7 @@ int msiren_destroy(msiren_handle h) {
     float* ptrs[] = {h->d_w0raw, h->d_b0raw, h->d_dump, h->d_s0t512, h->d_s0t, h->d_bias16, h->d_wout16, h->d_grid, h->d_l0, h->d_wp, h->d_bias, h->d_wout, h->d_modw, h->d_modw_rm, h->d_modb, h->d_encw, h->d_foldw, h->d_embias};
     for (float* p : ptrs)
         if (p) (void)hipFree(p);
-    std::vector<DevBuf*> bufs = {&h->ws_out, &h->ws_tiles, &h->ws_in, &h->ws_img};
+    std::vector<DevBuf*> bufs = {&h->stage_in, &h->stage_out};
     for (auto& c : h->sc)
         for (DevBuf* b : {&c.cscratch, &c.mods, &c.modpad, &c.latent, &c.patches, &c.keep, &c.rec, &c.queue, &c.feat, &c.plan, &c.score, &c.coords, &c.l0tab, &c.ragged}) bufs.push_back(b);
     for (DevBuf* b : bufs)
@@ -289,19 +307,11 @@ static int msiren_forward_mods_impl(msiren_handle h, const float* mods_host, int
     const Call c = make_call(h, true);
     auto& sc = h->sc[c.stream];
     const size_t nm = (size_t)h->L * B * h->H * sizeof(float), no = (size_t)B * h->P * sizeof(float);
-    if ((rc = ensure(h, sc.mods, nm)) || (rc = ensure(h, h->ws_out, no))) return rc;
-    const HostSrc src(mods_host, nm);
-    const HostDst dst(out_host, no);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(sc.mods.p, src.as<float>(), nm, hipMemcpyHostToDevice, sc.s));
-    if ((rc = launch_trunk(h, c, (const float*)sc.mods.p, B, (float*)h->ws_out.p))) return rc;
-    HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    return 0;
+    if ((rc = ensure(h, sc.mods, nm))) return rc;
+    SyncHostCall io(h, c.stream);
+    const int i_m = io.in(mods_host, nm, HOST_COPY, sc.mods.p), o_out = io.out(out_host, no, HOST_COPY);
+    if ((rc = io.begin()) || (rc = launch_trunk(h, c, io.src<float>(i_m), B, io.dst<float>(o_out)))) return rc;
+    return io.finish();
 }
 
 int msiren_forward_mods(msiren_handle h, const float* mods_host, int64_t B, float* out_host) {
@@ -326,22 +336,12 @@ static int msiren_forward_latent_impl(msiren_handle h, const float* z_host, int6
     auto& sc = h->sc[c.stream];
     const size_t nz = (size_t)B * h->Z * sizeof(float), no = (size_t)B * h->P * sizeof(float);
     const size_t nm = (size_t)h->L * B * h->H * sizeof(float);
-    if ((rc = ensure(h, sc.latent, nz)) || (rc = ensure(h, h->ws_out, no)) || (rc = ensure(h, sc.mods, nm))) return rc;
-    const HostSrc src(z_host, nz);
-    const HostDst dst(out_host, no), dst_mods(mods_out_host, nm);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    HOSTBUF_OK(dst_mods);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(sc.latent.p, src.as<float>(), nz, hipMemcpyHostToDevice, sc.s));
-    if ((rc = forward_latent_dev(h, c, (const float*)sc.latent.p, B, (float*)h->ws_out.p, (float*)sc.mods.p))) return rc;
-    HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
-    if (mods_out_host) HIPCHK(hipMemcpyAsync(dst_mods.as<float>(), sc.mods.p, nm, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    dst_mods.finish();
-    return 0;
+    if ((rc = ensure(h, sc.latent, nz)) || (rc = ensure(h, sc.mods, nm))) return rc;
+    SyncHostCall io(h, c.stream);
+    const int i_z = io.in(z_host, nz, HOST_COPY, sc.latent.p), o_out = io.out(out_host, no, HOST_COPY);
+    io.out(mods_out_host, nm, HOST_COPY, sc.mods.p);  // (the modulations are in the stream's scratch whether the caller takes them or not)
+    if ((rc = io.begin()) || (rc = forward_latent_dev(h, c, io.src<float>(i_z), B, io.dst<float>(o_out), (float*)sc.mods.p))) return rc;
+    return io.finish();
 }
 
 int msiren_forward_latent(msiren_handle h, const float* z_host, int64_t B, float* out_host, float* mods_out_host) {
@@ -355,7 +355,7 @@ int msiren_encode_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, 
     if (rc) return rc;
     const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!tiles_dev || !z_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h))) return rc;
     return launch_encoder(h, c, tiles_dev, B, z_dev);
 }
 
@@ -371,24 +371,16 @@ int msiren_encode_tiles(msiren_handle h, const float* tiles_host, int64_t B, flo
     int rc = check(h);
     if (rc) return rc;
     if (B < 0 || (B > 0 && (!tiles_host || !z_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h))) return rc;
     if (B == 0) return 0;
     const size_t nt = (size_t)B * h->O * h->O * sizeof(float), nz = (size_t)B * h->Z * sizeof(float);
     const Call call = make_call(h, false);  // (the prologue's MODE 1 / 2 instances have one ring depth, no prefetch: nothing to tell)
     auto& c = h->sc[call.stream];
-    if ((rc = ensure(h, h->ws_tiles, nt)) || (rc = ensure(h, c.latent, nz))) return rc;
-    const HostSrc src(tiles_host, nt);
-    const HostDst dst(z_host, nz);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(h->ws_tiles.p, src.as<float>(), nt, hipMemcpyHostToDevice, c.s));
-    if ((rc = launch_encoder(h, call, (const float*)h->ws_tiles.p, B, (float*)c.latent.p))) return rc;
-    HIPCHK(hipMemcpyAsync(dst.as<float>(), c.latent.p, nz, hipMemcpyDeviceToHost, c.s));
-    HIPCHK(hipStreamSynchronize(c.s));
-    drain.disarm();
-    dst.finish();
-    return 0;
+    if ((rc = ensure(h, c.latent, nz))) return rc;
+    SyncHostCall io(h, call.stream);
+    const int i_t = io.in(tiles_host, nt, HOST_COPY), o_z = io.out(z_host, nz, HOST_COPY, c.latent.p);
+    if ((rc = io.begin()) || (rc = launch_encoder(h, call, io.src<float>(i_t), B, io.dst<float>(o_z)))) return rc;
+    return io.finish();
 }
 
 int msiren_modulate(msiren_handle h, const float* z_host, int64_t B, float* mods_host) {
@@ -400,18 +392,10 @@ int msiren_modulate(msiren_handle h, const float* z_host, int64_t B, float* mods
     const Call call = make_call(h, false);  // (as msiren_encode_tiles)
     auto& c = h->sc[call.stream];
     if ((rc = ensure(h, c.latent, nz)) || (rc = ensure(h, c.mods, nm))) return rc;
-    const HostSrc src(z_host, nz);
-    const HostDst dst(mods_host, nm);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(c.latent.p, src.as<float>(), nz, hipMemcpyHostToDevice, c.s));
-    if ((rc = launch_modulator(h, call, (const float*)c.latent.p, B, (float*)c.mods.p))) return rc;
-    HIPCHK(hipMemcpyAsync(dst.as<float>(), c.mods.p, nm, hipMemcpyDeviceToHost, c.s));
-    HIPCHK(hipStreamSynchronize(c.s));
-    drain.disarm();
-    dst.finish();
-    return 0;
+    SyncHostCall io(h, call.stream);
+    const int i_z = io.in(z_host, nz, HOST_COPY, c.latent.p), o_m = io.out(mods_host, nm, HOST_COPY, c.mods.p);
+    if ((rc = io.begin()) || (rc = launch_modulator(h, call, io.src<float>(i_z), B, io.dst<float>(o_m)))) return rc;
+    return io.finish();
 }
 
 // ---- the prologue of msiren_forward_tiles(_dev) alone: tiles -> [latent] -> modulations, by the launches that call would make ----
@@ -420,7 +404,7 @@ int msiren_encode_modulate_tiles_dev(msiren_handle h, const float* tiles_dev, in
     if (rc) return rc;
     const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!tiles_dev || !mods_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h))) return rc;
     if (B == 0) return 0;
     return encode_modulate_dev(h, c, tiles_dev, B, latent_dev, mods_dev);
 }
@@ -429,42 +413,34 @@ int msiren_encode_modulate_tiles(msiren_handle h, const float* tiles_host, int64
     int rc = check(h);
     if (rc) return rc;
     if (B < 0 || (B > 0 && (!tiles_host || !mods_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h))) return rc;
     if (B == 0) return 0;
     const size_t tile_elems = (size_t)h->O * h->O, nt = (size_t)B * tile_elems * sizeof(float), nz = (size_t)B * h->Z * sizeof(float);
     const size_t nm = (size_t)h->L * B * h->H * sizeof(float);
-    // device staging for the whole call (chunk k's modulations, (L, n_k, H), sit at L * lo_k * H): nothing is reallocated while a chunk runs
-    if ((rc = ensure(h, h->ws_tiles, nt)) || (rc = ensure(h, h->ws_out, nm)) || (rc = ensure(h, h->ws_img, nz))) return rc;
     // the chunks, streams and CallMode of msiren_forward_tiles_impl (which see): every chunk reaches the instance it reaches there
     std::vector<msiren::HostChunk> plan;
     if (msiren::host_call_pipelines(h->dh, B)) plan = msiren::pipelined_host_plan(B, h->host_first, h->host_piece, h->cur);
     else plan.push_back({0, B, h->cur, 0, false});
-    const HostSrc src(tiles_host, nt);
-    const HostDst dst_z(latent_host, nz), dst(mods_host, nm);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst_z);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
+    // device staging for the whole call (chunk k's modulations, (L, n_k, H), sit at L * lo_k * H): nothing is reallocated while a chunk runs
+    SyncHostCall io(h, h->cur, true);
+    const int i_t = io.in(tiles_host, nt, HOST_OWN_COPIES), o_z = io.out(latent_host, nz, HOST_OWN_COPIES), o_m = io.out(mods_host, nm, HOST_OWN_COPIES);
+    if ((rc = io.begin())) return rc;
     Call call = make_call(h, true);
     for (const msiren::HostChunk& c : plan) {
         call.stream = c.stream;
         call.mode.trunk = c.trunk;
         call.mode.beside = c.beside;
         hipStream_t s = h->sc[c.stream].s;
-        float* const d_t = (float*)h->ws_tiles.p + (size_t)c.lo * tile_elems;
-        float* const d_z = (float*)h->ws_img.p + (size_t)c.lo * h->Z;
-        float* const d_m = (float*)h->ws_out.p + (size_t)h->L * c.lo * h->H;
-        HIPCHK(hipMemcpyAsync(d_t, src.as<float>() + (size_t)c.lo * tile_elems, (size_t)c.n * tile_elems * sizeof(float), hipMemcpyHostToDevice, s));
-        if ((rc = encode_modulate_dev(h, call, d_t, c.n, latent_host ? d_z : nullptr, d_m))) return rc;
-        if (latent_host) HIPCHK(hipMemcpyAsync(dst_z.as<float>() + (size_t)c.lo * h->Z, d_z, (size_t)c.n * h->Z * sizeof(float), hipMemcpyDeviceToHost, s));
+        float* const d_t = (float*)io.src<float>(i_t) + (size_t)c.lo * tile_elems;
+        float* const d_z = latent_host ? io.dst<float>(o_z) + (size_t)c.lo * h->Z : nullptr;
+        float* const d_m = io.dst<float>(o_m) + (size_t)h->L * c.lo * h->H;
+        HIPCHK(hipMemcpyAsync(d_t, io.host_src<float>(i_t) + (size_t)c.lo * tile_elems, (size_t)c.n * tile_elems * sizeof(float), hipMemcpyHostToDevice, s));
+        if ((rc = encode_modulate_dev(h, call, d_t, c.n, d_z, d_m))) return rc;
+        if (d_z) HIPCHK(hipMemcpyAsync(io.host_dst<float>(o_z) + (size_t)c.lo * h->Z, d_z, (size_t)c.n * h->Z * sizeof(float), hipMemcpyDeviceToHost, s));
         const size_t row = (size_t)c.n * h->H * sizeof(float);  // layer l of the chunk -> rows [lo, lo + n) of layer l of the call
-        HIPCHK(hipMemcpy2DAsync(dst.as<float>() + (size_t)c.lo * h->H, (size_t)B * h->H * sizeof(float), d_m, row, row, (size_t)h->L, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpy2DAsync(io.host_dst<float>(o_m) + (size_t)c.lo * h->H, (size_t)B * h->H * sizeof(float), d_m, row, row, (size_t)h->L, hipMemcpyDeviceToHost, s));
     }
-    if ((rc = sync_all(h))) return rc;
-    drain.disarm();
-    dst_z.finish();
-    dst.finish();
-    return 0;
+    return io.finish();
 }
 
 int msiren_forward_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B, float* out_dev) {
@@ -472,7 +448,7 @@ int msiren_forward_tiles_dev(msiren_handle h, const float* tiles_dev, int64_t B,
     if (rc) return rc;
     const Call c = dev_call(h);
     if (B < 0 || (B > 0 && (!tiles_dev || !out_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h))) return rc;
     return forward_tiles_dev(h, c, tiles_dev, B, out_dev);
 }
 
@@ -480,10 +456,9 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
     int rc = check(h);
     if (rc) return rc;
     if (B < 0 || (B > 0 && (!tiles_host || !out_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if ((rc = check_tile_size(h))) return rc;
     if (B == 0) return 0;
     const size_t nt = (size_t)B * h->O * h->O * sizeof(float), no = (size_t)B * h->P * sizeof(float);
-    if ((rc = ensure(h, h->ws_tiles, nt)) || (rc = ensure(h, h->ws_out, no))) return rc;
     // From host_pipe_min tiles (2400 = six slices) up the call pipelines itself (round 5).  The device side of a slice is ~325 us; uploading
     // its 1.6 MB first and downloading its 0.9 MB afterwards added ~90 us in front and behind.  Patches are independent
     // (modulated_siren.py:435-457), so the batch is cut into chunks that alternate between the handle's two streams:
@@ -510,21 +485,23 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
     // memory (a plain numpy array) is copied by the runtime.  One-chunk calls only: same box, 400 tiles: 390 us with both copies, 369 with
     // the output in place, 360 with the tiles in place as well; a cut call of 3 200 tiles: 2.24 ms with copies (they run beside the other
     // chunk's kernels anyway), 2.35-2.87 ms in place (profiles/r5/04_host_call_pipelining.txt).
-    const HostSrc src(tiles_host, nt);  // (a range that is page-locked in part goes through a bounce buffer: host_range_kind)
-    const HostDst dst(out_host, no);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);  // (an early return waits for what is in flight on these buffers before they go)
-    tiles_host = src.as<float>();
-    out_host = dst.as<float>();
-    float* out_zc_ = nchunks == 1 ? dst.dev<float>() : nullptr;
-    const float* in_zc_ = nchunks == 1 ? src.dev<float>() : nullptr;
-    float* const out_zc = out_zc_;
-    const float* const in_zc = in_zc_;
-    float* const out_base = out_zc ? out_zc : (float*)h->ws_out.p;
+    // Who copies (a range that is page-locked in part goes through a bounce buffer either way: host_range_kind):
+    //   own   a cut call (nchunks > 1): never in place; this function enqueues every chunk's upload and download itself, on that chunk's
+    //         stream (HOST_OWN_COPIES: the helper classifies, bounces, reserves the staging and waits);
+    //   !own  one chunk: in place where page-locked, else the helper's copies -- the upload in begin(), the download in finish() -- so
+    //         the loop's H2D and the `download` lambda below have nothing to enqueue (they still take the trace's stamps: for one chunk
+    //         `h2d` is the time behind classification and upload, `d2h` the time at which finish() is about to be called).
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     auto us = [&]() { return std::chrono::duration<double, std::micro>(clk::now() - t0).count(); };
+    const bool own = nchunks > 1;
+    SyncHostCall io(h, cur0, true);
+    const int i_t = io.in(tiles_host, nt, own ? HOST_OWN_COPIES : HOST_IN_PLACE), o_out = io.out(out_host, no, own ? HOST_OWN_COPIES : HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    tiles_host = io.host_src<float>(i_t);
+    out_host = io.host_dst<float>(o_out);
+    const float* const d_tiles = io.src<float>(i_t);
+    float* const out_base = io.dst<float>(o_out);
     std::vector<double> tr_h2d(nchunks, 0.0), tr_launch(nchunks, 0.0), tr_d2h(nchunks, 0.0);
     HostCheck hc;
     Call call = make_call(h, true);
@@ -533,7 +510,7 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
     auto download = [&](int k) {
         const Chunk& c = plan[k];
         tr_d2h[k] = us();
-        if (out_zc) return;
+        if (!own) return;  // (finish() downloads what one chunk did not store in place)
         hipError_t e = hipMemcpyAsync(out_host + (size_t)c.lo * h->P, out_base + (size_t)c.lo * h->P, (size_t)c.n * h->P * sizeof(float),
                                       hipMemcpyDeviceToHost, h->sc[c.stream].s);
         if (e != hipSuccess && !rc) rc = fail(MSIREN_E_HIP, "hipMemcpyAsync(D2H): %s", hipGetErrorString(e));
@@ -544,8 +521,8 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
         call.stream = c.stream;
         call.mode.trunk = c.trunk;
         call.mode.beside = c.beside;
-        const float* d_t = in_zc ? in_zc + (size_t)c.lo * tile_elems : (const float*)h->ws_tiles.p + (size_t)c.lo * tile_elems;
-        if (!in_zc) {
+        const float* d_t = d_tiles + (size_t)c.lo * tile_elems;
+        if (own) {
             hipError_t e = hipMemcpyAsync((void*)d_t, tiles_host + (size_t)c.lo * tile_elems, (size_t)c.n * tile_elems * sizeof(float), hipMemcpyHostToDevice, h->sc[c.stream].s);
             if (e != hipSuccess) rc = fail(MSIREN_E_HIP, "hipMemcpyAsync(H2D): %s", hipGetErrorString(e));
         }
@@ -565,24 +542,14 @@ static int msiren_forward_tiles_impl(msiren_handle h, const float* tiles_host, i
         if (pipelined && k >= 1 && !rc) download(k - 1);
     }
     for (int k = pipelined ? nchunks - 1 : 0; k < nchunks && !rc; ++k) download(k);
-    int rs = sync_all(h);
-    if (!rc && !rs && hc.armed && (unsigned)h->status_host[8] == hc.epoch) {
-        // the trunk met a modulation outside the fp16 domain: the batch once more on the exact-fp32 trunk (the conditional kernel, its
-        // condition pointed at the word that has just been read), the download once more if there is one
-        Call fix = make_call(h, true);
-        fix.stream = plan[0].stream;
-        rc = launch_trunk_f32_cond(h, fix, hc.mods, hc.B, hc.out, h->status_dev + 8, hc.epoch);
-        if (!rc) download(0);
-        rs = sync_all(h);
-    }
-    if (!rs) drain.disarm();
-    if (!rc && !rs) dst.finish();
-    if (h->trace_host) {
+    if (!rc) rc = io.finish();
+    if (!rc) rc = io.recheck(hc, CoordSet{});  // (the domain check: one-chunk calls only, hc is armed by them)
+    if (h->trace_host) {  // (whatever the outcome; a call that failed is drained by the helper when it goes)
         std::fprintf(stderr, "msiren_forward_tiles B=%lld chunks=%d%s (us since entry): ", (long long)B, nchunks, pipelined ? " pipelined" : "");
         for (int k = 0; k < nchunks; ++k) std::fprintf(stderr, "[%lld tiles: h2d %.0f launched %.0f d2h %.0f] ", (long long)plan[k].n, tr_h2d[k], tr_launch[k], tr_d2h[k]);
         std::fprintf(stderr, "synced %.0f\n", us());
     }
-    return rc ? rc : rs;
+    return rc;
 }
 
 int msiren_forward_tiles(msiren_handle h, const float* tiles_host, int64_t B, float* out_host) {
@@ -602,27 +569,16 @@ static int msiren_reconstruct_slices_impl(msiren_handle h, const float* images_h
     if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
     const size_t ni = (size_t)n * height * width * sizeof(float);
     const size_t nr = (size_t)n * nV * out_stride * nH * out_stride * sizeof(float);
-    if ((rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, h->ws_img, nr))) return rc;
     // As in msiren_forward_tiles: where the caller's reconstruction array is page-locked memory (the Python mirror's outputs are, by default)
-    // the fold stores straight into it; the image always arrives by a copy (DMA from page-locked memory, through the runtime from pageable
-    // memory): read in place every pixel would cross the link four times (32 x 32 tiles at a stride of 16; profiles/r5/09_*).
+    // the fold stores straight into it; the image always arrives by a copy (host_buffers.h: HOST_COPY).
     Call c = make_call(h, true);
-    auto& sc = h->sc[c.stream];
     OutGeom og;
     if (out_stride != h->I && (rc = scaled_call(h, c, out_stride, &og))) return rc;
-    const HostSrc src(images_host, ni);
-    const HostDst dst(recon_host, nr);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
-    float* const d_rec = dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_img.p;
-    HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-    if ((rc = reconstruct_slices(h, c, (const float*)h->ws_in.p, n, height, width, d_rec, out_stride != h->I ? &og : nullptr))) return rc;
-    if (d_rec == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_img.p, nr, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    return 0;
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), o_rec = io.out(recon_host, nr, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = reconstruct_slices(h, c, io.src<float>(i_img), n, height, width, io.dst<float>(o_rec), out_stride != h->I ? &og : nullptr))) return rc;
+    return io.finish();
 }
 
 int msiren_reconstruct_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, float* recon_host) {
@@ -703,13 +659,11 @@ int msiren_memcpy_h2d(msiren_handle h, void* dst_dev, const void* src_host, size
     if (rc) return rc;
     if (bytes == 0) return 0;
     if ((rc = sync_all(h))) return rc;
-    const HostSrc src(src_host, bytes);
-    HOSTBUF_OK(src);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(dst_dev, src.as<void>(), bytes, hipMemcpyHostToDevice, h->sc[h->cur].s));
-    HIPCHK(hipStreamSynchronize(h->sc[h->cur].s));
-    drain.disarm();
-    return 0;
+    // (to the helper a null host pointer is an output left out and a null device side is staging: neither may be null here)
+    if (!dst_dev || !src_host) return fail(MSIREN_E_HIP, "msiren_memcpy_h2d: null pointer (invalid argument)");
+    SyncHostCall io(h, h->cur);
+    io.in(src_host, bytes, HOST_COPY, dst_dev);
+    return (rc = io.begin()) ? rc : io.finish();
 }
 
 int msiren_memcpy_d2h(msiren_handle h, void* dst_host, const void* src_dev, size_t bytes) {
@@ -717,14 +671,10 @@ int msiren_memcpy_d2h(msiren_handle h, void* dst_host, const void* src_dev, size
     if (rc) return rc;
     if (bytes == 0) return 0;
     if ((rc = sync_all(h))) return rc;
-    const HostDst dst(dst_host, bytes);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(dst.as<void>(), src_dev, bytes, hipMemcpyDeviceToHost, h->sc[h->cur].s));
-    HIPCHK(hipStreamSynchronize(h->sc[h->cur].s));
-    drain.disarm();
-    dst.finish();
-    return 0;
+    if (!dst_host || !src_dev) return fail(MSIREN_E_HIP, "msiren_memcpy_d2h: null pointer (invalid argument)");  // (as msiren_memcpy_h2d)
+    SyncHostCall io(h, h->cur);
+    io.out(dst_host, bytes, HOST_COPY, src_dev);
+    return (rc = io.begin()) ? rc : io.finish();
 }
 
 int msiren_timer_start(msiren_handle h) {

@@ -25,7 +25,7 @@ int ragged_dev(msiren_ctx* h, const float* coords_dev, const int32_t* offsets_de
     RaggedSet r;
     int rc = check_ragged_args(h, coords_dev, offsets_dev, mods_dev, B, T, out_dev, grad_dev, grad, &r);
     if (rc || B == 0 || T == 0) return rc;
-    if ((uintptr_t)coords_dev % 8) return fail(MSIREN_E_INVALID, "device coordinates must be 8-byte aligned (they are read as (row, column) pairs)");
+    if ((rc = check_pairs_aligned(coords_dev, "coordinates"))) return rc;
     if ((uintptr_t)offsets_dev % 4) return fail(MSIREN_E_INVALID, "device offsets must be 4-byte aligned");
     const Call c = dev_call(h);
     auto& sc = h->sc[c.stream];
@@ -47,33 +47,17 @@ int ragged_host(msiren_ctx* h, const float* coords_host, const int32_t* offsets_
     auto& sc = h->sc[c.stream];
     const size_t nc = (size_t)T * 2 * sizeof(float), nf = (size_t)(B + 1) * sizeof(int), no = (size_t)T * sizeof(float);
     const size_t ni = (size_t)h->L * B * h->H * sizeof(float);
-    if ((rc = ensure(h, sc.coords, nc)) || (rc = ensure(h, sc.ragged, 2 * nf)) || (rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, h->ws_out, no)) ||
-        (grad && (rc = ensure(h, h->ws_img, 2 * no))))
-        return rc;
-    const HostSrc csrc(coords_host, nc), osrc(offsets_host, nf), src(mods_host, ni);
-    const HostDst dst(out_host, out_host ? no : 0), gdst(grad_host, grad ? 2 * no : 0);
-    HOSTBUF_OK(csrc);
-    HOSTBUF_OK(osrc);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    HOSTBUF_OK(gdst);
-    DrainOnExit drain(h);
+    if ((rc = ensure(h, sc.coords, nc)) || (rc = ensure(h, sc.ragged, 2 * nf))) return rc;
     int* const d_off = (int*)sc.ragged.p;  // [offsets (B + 1)][item table (B + 1)]
-    HIPCHK(hipMemcpyAsync(sc.coords.p, csrc.as<float>(), nc, hipMemcpyHostToDevice, sc.s));
-    HIPCHK(hipMemcpyAsync(d_off, osrc.as<int>(), nf, hipMemcpyHostToDevice, sc.s));
-    HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));  // (modulations are read once per item: copied)
-    r.coords = (const float*)sc.coords.p, r.offsets = d_off, r.items = d_off + (B + 1);
-    float* const d_out = !out_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_out.p;
-    float* const d_grad = !grad ? nullptr : gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_img.p;
-    rc = grad ? launch_trunk_f32_jet_ragged(h, c, r, (const float*)h->ws_in.p, d_out, d_grad, 1.0f) : launch_trunk_f32_ragged(h, c, r, (const float*)h->ws_in.p, d_out);
-    if (rc) return rc;
-    if (d_out && d_out == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
-    if (d_grad && d_grad == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_img.p, 2 * no, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    gdst.finish();
-    return 0;
+    SyncHostCall io(h, c.stream);
+    const int i_c = io.in(coords_host, nc, HOST_COPY, sc.coords.p), i_off = io.in(offsets_host, nf, HOST_COPY, d_off);
+    const int i_m = io.in(mods_host, ni, HOST_COPY);  // (modulations are read once per item: copied)
+    const int o_out = io.out(out_host, no, HOST_IN_PLACE), o_grad = io.out(grad ? grad_host : nullptr, 2 * no, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    r.coords = io.src<float>(i_c), r.offsets = io.src<int>(i_off), r.items = d_off + (B + 1);
+    rc = grad ? launch_trunk_f32_jet_ragged(h, c, r, io.src<float>(i_m), io.dst<float>(o_out), io.dst<float>(o_grad), 1.0f)
+              : launch_trunk_f32_ragged(h, c, r, io.src<float>(i_m), io.dst<float>(o_out));
+    return rc ? rc : io.finish();
 }
 
 // the reconstruction at points, one synchronous one-chunk call on host pointers: images + points -> [out], [grad]
@@ -87,26 +71,13 @@ int resample_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t he
     Call c = make_call(h, true);
     auto& sc = h->sc[c.stream];
     const size_t ni = (size_t)n * height * width * sizeof(float), np = (size_t)M * 2 * sizeof(float), no = (size_t)n * M * sizeof(float);
-    if ((rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, sc.coords, np)) || (rc = ensure(h, h->ws_out, no)) || (grad && (rc = ensure(h, h->ws_img, 2 * no)))) return rc;
-    const HostSrc src(images_host, ni), psrc(points_host, np);
-    const HostDst dst(out_host, out_host ? no : 0), gdst(grad_host, grad ? 2 * no : 0);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(psrc);
-    HOSTBUF_OK(dst);
-    HOSTBUF_OK(gdst);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-    HIPCHK(hipMemcpyAsync(sc.coords.p, psrc.as<float>(), np, hipMemcpyHostToDevice, sc.s));
-    float* const d_out = !out_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_out.p;
-    float* const d_grad = !grad ? nullptr : gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_img.p;
-    if ((rc = resample_slices(h, c, (const float*)h->ws_in.p, n, height, width, (const float*)sc.coords.p, M, d_out, d_grad, grad))) return rc;
-    if (d_out && d_out == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
-    if (d_grad && d_grad == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_img.p, 2 * no, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    gdst.finish();
-    return 0;
+    if ((rc = ensure(h, sc.coords, np))) return rc;
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_p = io.in(points_host, np, HOST_COPY, sc.coords.p);
+    const int o_out = io.out(out_host, no, HOST_IN_PLACE), o_grad = io.out(grad ? grad_host : nullptr, 2 * no, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = resample_slices(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_p), M, io.dst<float>(o_out), io.dst<float>(o_grad), grad))) return rc;
+    return io.finish();
 }
 
 }  // namespace

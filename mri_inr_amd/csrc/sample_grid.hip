@@ -29,11 +29,12 @@ int check_coords(const float* coords, int64_t Q) {
     return 0;
 }
 
-// the call's coordinate set: device coordinates as given, the table (16-bit trunks) built into the stream's scratch in front of the trunk
-int attach_coords(msiren_ctx* h, Call& c, const float* coords_dev, int64_t Q) {
-    if ((uintptr_t)coords_dev % 8) return fail(MSIREN_E_INVALID, "device coordinates must be 8-byte aligned (they are read as (row, column) pairs)");
+// the call's coordinate set: device coordinates as given, the table (16-bit trunks) built into the stream's scratch in front of the trunk;
+// `table` false (the gradient calls: the jet trunk forms layer 0 itself): the coordinates as they are
+int attach_coords(msiren_ctx* h, Call& c, const float* coords_dev, int64_t Q, bool table = true) {
+    if (int rc = check_pairs_aligned(coords_dev, "coordinates")) return rc;
     CoordSet cs{coords_dev, nullptr, (int)Q};
-    if (needs_table(h)) {
+    if (table && needs_table(h)) {
         auto& sc = h->sc[c.stream];
         hipEvent_t e1 = nullptr;  // (msiren_profile_enable: the table kernel is reported beside the trunks, under its own name)
         int rc = ensure(h, sc.l0tab, (size_t)h->H * Q * sizeof(float));
@@ -136,7 +137,7 @@ int sample_host_impl(msiren_ctx* h, const float* coords_host, int64_t Q, const f
     if (rc) return rc;
     if ((rc = check_coords(coords_host, Q))) return rc;
     if (B < 0 || (B > 0 && (!in_host || !out_host))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (tiles && h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if (tiles && (rc = check_tile_size(h))) return rc;
     if (B == 0) return 0;
     HostCheck hc;
     Call c = make_call(h, true);
@@ -145,38 +146,16 @@ int sample_host_impl(msiren_ctx* h, const float* coords_host, int64_t Q, const f
     auto& sc = h->sc[c.stream];
     const size_t nc = (size_t)Q * 2 * sizeof(float), no = (size_t)B * Q * sizeof(float);
     const size_t ni = tiles ? (size_t)B * h->O * h->O * sizeof(float) : (size_t)h->L * B * h->H * sizeof(float);
-    DevBuf& in_buf = tiles ? h->ws_tiles : sc.mods;
-    if ((rc = ensure(h, sc.coords, nc)) || (rc = ensure(h, in_buf, ni)) || (rc = ensure(h, h->ws_out, no))) return rc;
-    const HostSrc csrc(coords_host, nc), src(in_host, ni);
-    const HostDst dst(out_host, no);
-    HOSTBUF_OK(csrc);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(sc.coords.p, csrc.as<float>(), nc, hipMemcpyHostToDevice, sc.s));
-    if ((rc = attach_coords(h, c, (const float*)sc.coords.p, Q))) return rc;
-    const float* d_in = tiles ? src.dev<float>() : nullptr;  // (page-locked tiles are read in place; modulations are read once per unit: copied)
-    if (!d_in) {
-        HIPCHK(hipMemcpyAsync(in_buf.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-        d_in = (const float*)in_buf.p;
-    }
-    float* const d_out = dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_out.p;
-    if ((rc = tiles ? forward_tiles_dev(h, c, d_in, B, d_out) : launch_trunk(h, c, d_in, B, d_out))) return rc;
-    auto download = [&]() -> int {
-        if (d_out == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
-        HIPCHK(hipStreamSynchronize(sc.s));
-        return 0;
-    };
-    if ((rc = download())) return rc;
-    if (hc.armed && (unsigned)h->status_host[8] == hc.epoch) {
-        // a modulation outside the fp16 domain: the batch once more on the exact-fp32 trunk, at the call's coordinates
-        Call fix = with_coords(make_call(h, true), c.cs);
-        fix.stream = c.stream;
-        if ((rc = launch_trunk_f32_cond(h, fix, hc.mods, hc.B, hc.out, h->status_dev + 8, hc.epoch)) || (rc = download())) return rc;
-    }
-    drain.disarm();
-    dst.finish();
-    return 0;
+    if ((rc = ensure(h, sc.coords, nc)) || (!tiles && (rc = ensure(h, sc.mods, ni)))) return rc;
+    SyncHostCall io(h, c.stream);
+    const int i_c = io.in(coords_host, nc, HOST_COPY, sc.coords.p);
+    const int i_in = tiles ? io.in(in_host, ni, HOST_IN_PLACE) : io.in(in_host, ni, HOST_COPY, sc.mods.p);
+    const int o_out = io.out(out_host, no, HOST_IN_PLACE);
+    if ((rc = io.begin()) || (rc = attach_coords(h, c, io.src<float>(i_c), Q))) return rc;  // (the coordinates are on the stream in front of the table kernel)
+    const float* const d_in = io.src<float>(i_in);
+    float* const d_out = io.dst<float>(o_out);
+    if ((rc = tiles ? forward_tiles_dev(h, c, d_in, B, d_out) : launch_trunk(h, c, d_in, B, d_out)) || (rc = io.finish())) return rc;
+    return io.recheck(hc, c.cs);
 }
 
 int sample_host(msiren_ctx* h, const float* coords_host, int64_t Q, const float* in_host, int64_t B, float* out_host, bool tiles) {
@@ -192,7 +171,7 @@ int sample_dev(msiren_ctx* h, const float* coords_dev, int64_t Q, const float* i
     Call c = dev_call(h);
     if ((rc = check_coords(coords_dev, Q))) return rc;
     if (B < 0 || (B > 0 && (!in_dev || !out_dev))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (tiles && h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
+    if (tiles && (rc = check_tile_size(h))) return rc;
     if (B == 0) return 0;
     if ((rc = attach_coords(h, c, coords_dev, Q))) return rc;
     return tiles ? forward_tiles_dev(h, c, in_dev, B, out_dev) : launch_trunk(h, c, in_dev, B, out_dev);
@@ -204,14 +183,7 @@ int check_grad_args(msiren_ctx* h, const float* coords, int64_t Q, const float* 
     int rc = check_coords(coords, Q);
     if (rc || (rc = jet_supported(h))) return rc;
     if (B < 0 || (B > 0 && (!in || !grad))) return fail(MSIREN_E_INVALID, "bad arguments (B=%lld)", (long long)B);
-    if (tiles && h->O != 32) return fail(MSIREN_E_INVALID, "the custom encoder is hard-wired to 32x32 tiles (siren_encoder.py:499), outer_patch_size=%d", h->O);
-    return 0;
-}
-
-// the call's coordinates as they are (no layer-0 table: the jet trunk forms layer 0 itself)
-int attach_coords_only(Call& c, const float* coords_dev, int64_t Q) {
-    if ((uintptr_t)coords_dev % 8) return fail(MSIREN_E_INVALID, "device coordinates must be 8-byte aligned (they are read as (row, column) pairs)");
-    c = with_coords(c, CoordSet{coords_dev, nullptr, (int)Q});
+    if (tiles && (rc = check_tile_size(h))) return rc;
     return 0;
 }
 
@@ -231,10 +203,10 @@ int grad_dev_impl(msiren_ctx* h, const Call& c, const float* in_dev, int64_t B, 
 int sample_grad_dev(msiren_ctx* h, const float* coords_dev, int64_t Q, const float* in_dev, int64_t B, float* out_dev, float* grad_dev, bool tiles) {
     int rc = check(h);
     if (rc || (rc = check_grad_args(h, coords_dev, Q, in_dev, B, grad_dev, tiles))) return rc;
-    if ((uintptr_t)coords_dev % 8) return fail(MSIREN_E_INVALID, "device coordinates must be 8-byte aligned (they are read as (row, column) pairs)");
+    if ((rc = check_pairs_aligned(coords_dev, "coordinates"))) return rc;
     if (B == 0) return 0;
     Call c = dev_call(h);
-    if ((rc = attach_coords_only(c, coords_dev, Q))) return rc;
+    if ((rc = attach_coords(h, c, coords_dev, Q, false))) return rc;
     return grad_dev_impl(h, c, in_dev, B, out_dev, grad_dev, tiles);
 }
 
@@ -247,32 +219,15 @@ int sample_grad_host(msiren_ctx* h, const float* coords_host, int64_t Q, const f
     auto& sc = h->sc[c.stream];
     const size_t nc = (size_t)Q * 2 * sizeof(float), no = (size_t)B * Q * sizeof(float);
     const size_t ni = tiles ? (size_t)B * h->O * h->O * sizeof(float) : (size_t)h->L * B * h->H * sizeof(float);
-    DevBuf& in_buf = tiles ? h->ws_tiles : h->ws_in;  // (sc.mods is where the _tiles form's prologue writes)
-    if ((rc = ensure(h, sc.coords, nc)) || (rc = ensure(h, in_buf, ni)) || (rc = ensure(h, h->ws_out, no)) || (rc = ensure(h, h->ws_img, 2 * no))) return rc;
-    const HostSrc csrc(coords_host, nc), src(in_host, ni);
-    const HostDst dst(out_host, out_host ? no : 0), gdst(grad_host, 2 * no);
-    HOSTBUF_OK(csrc);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    HOSTBUF_OK(gdst);
-    DrainOnExit drain(h);
-    HIPCHK(hipMemcpyAsync(sc.coords.p, csrc.as<float>(), nc, hipMemcpyHostToDevice, sc.s));
-    if ((rc = attach_coords_only(c, (const float*)sc.coords.p, Q))) return rc;
-    const float* d_in = tiles ? src.dev<float>() : nullptr;  // (page-locked tiles are read in place; modulations are read once per unit: copied)
-    if (!d_in) {
-        HIPCHK(hipMemcpyAsync(in_buf.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-        d_in = (const float*)in_buf.p;
-    }
-    float* const d_out = !out_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_out.p;
-    float* const d_grad = gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_img.p;
-    if ((rc = grad_dev_impl(h, c, d_in, B, d_out, d_grad, tiles))) return rc;
-    if (d_out && d_out == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_out.p, no, hipMemcpyDeviceToHost, sc.s));
-    if (d_grad == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_img.p, 2 * no, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    gdst.finish();
-    return 0;
+    if ((rc = ensure(h, sc.coords, nc))) return rc;
+    SyncHostCall io(h, c.stream);
+    const int i_c = io.in(coords_host, nc, HOST_COPY, sc.coords.p);
+    // (page-locked tiles are read in place; modulations go to staging: sc.mods is where the _tiles form's prologue writes)
+    const int i_in = io.in(in_host, ni, tiles ? HOST_IN_PLACE : HOST_COPY);
+    const int o_out = io.out(out_host, no, HOST_IN_PLACE), o_grad = io.out(grad_host, 2 * no, HOST_IN_PLACE);
+    if ((rc = io.begin()) || (rc = attach_coords(h, c, io.src<float>(i_c), Q, false))) return rc;
+    if ((rc = grad_dev_impl(h, c, io.src<float>(i_in), B, io.dst<float>(o_out), io.dst<float>(o_grad), tiles))) return rc;
+    return io.finish();
 }
 
 // The slice pipeline with its gradient at output stride out_stride: coordinates, fold geometry and the factor d/r that turns a gradient per
@@ -414,29 +369,16 @@ int msiren_reconstruct_slices_grad(msiren_handle h, const float* images_host, in
     if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
     const size_t ni = (size_t)n * height * width * sizeof(float);
     const size_t nr = (size_t)n * nV * out_stride * nH * out_stride * sizeof(float);
-    if ((rc = ensure(h, h->ws_in, ni)) || (rc = ensure(h, h->ws_img, nr)) || (rc = ensure(h, h->ws_out, 2 * nr))) return rc;
     Call c = make_call(h, true);
-    auto& sc = h->sc[c.stream];
     OutGeom og;
     GradOut go;
     if ((rc = grad_slices_call(h, c, out_stride, &og, &go.gscale))) return rc;
-    const HostSrc src(images_host, ni);
-    const HostDst dst(recon_host, recon_host ? nr : 0), gdst(grad_host, 2 * nr);
-    HOSTBUF_OK(src);
-    HOSTBUF_OK(dst);
-    HOSTBUF_OK(gdst);
-    DrainOnExit drain(h);
-    float* const d_rec = !recon_host ? nullptr : dst.dev<float>() ? dst.dev<float>() : (float*)h->ws_img.p;
-    go.grad = gdst.dev<float>() ? gdst.dev<float>() : (float*)h->ws_out.p;
-    HIPCHK(hipMemcpyAsync(h->ws_in.p, src.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-    if ((rc = reconstruct_slices(h, c, (const float*)h->ws_in.p, n, height, width, d_rec, &og, &go))) return rc;
-    if (d_rec && d_rec == (float*)h->ws_img.p) HIPCHK(hipMemcpyAsync(dst.as<float>(), h->ws_img.p, nr, hipMemcpyDeviceToHost, sc.s));
-    if (go.grad == (float*)h->ws_out.p) HIPCHK(hipMemcpyAsync(gdst.as<float>(), h->ws_out.p, 2 * nr, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    gdst.finish();
-    return 0;
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), o_rec = io.out(recon_host, nr, HOST_IN_PLACE), o_grad = io.out(grad_host, 2 * nr, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    go.grad = io.dst<float>(o_grad);
+    if ((rc = reconstruct_slices(h, c, io.src<float>(i_img), n, height, width, io.dst<float>(o_rec), &og, &go))) return rc;
+    return io.finish();
 }
 
 }  // extern "C"

@@ -61,24 +61,10 @@ int msiren_score_images(msiren_handle h, const float* original_host, const float
     int rc = score_args(h, original_host, predicted_host, n, height, width, scores_host);
     if (rc || n == 0) return rc;
     const size_t ni = (size_t)n * height * width * sizeof(float), ns = (size_t)n * 3 * sizeof(double);
-    if ((rc = ensure(h, h->ws_in, 2 * ni)) || (rc = ensure(h, h->ws_out, ns))) return rc;
-    auto& sc = h->sc[h->cur];
-    const HostSrc src_o(original_host, ni), src_p(predicted_host, ni);
-    const HostDst dst(scores_host, ns);
-    HOSTBUF_OK(src_o);
-    HOSTBUF_OK(src_p);
-    HOSTBUF_OK(dst);
-    DrainOnExit drain(h);
-    float* d_o = (float*)h->ws_in.p;
-    float* d_p = (float*)((char*)h->ws_in.p + ni);
-    HIPCHK(hipMemcpyAsync(d_o, src_o.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-    HIPCHK(hipMemcpyAsync(d_p, src_p.as<float>(), ni, hipMemcpyHostToDevice, sc.s));
-    if ((rc = score_on_current_stream(h, d_o, d_p, n, height, width, (double*)h->ws_out.p))) return rc;
-    HIPCHK(hipMemcpyAsync(dst.as<double>(), h->ws_out.p, ns, hipMemcpyDeviceToHost, sc.s));
-    HIPCHK(hipStreamSynchronize(sc.s));
-    drain.disarm();
-    dst.finish();
-    return 0;
+    SyncHostCall io(h, h->cur);
+    const int i_o = io.in(original_host, ni, HOST_COPY), i_p = io.in(predicted_host, ni, HOST_COPY | HOST_PACKED), o_s = io.out(scores_host, ns, HOST_COPY);
+    if ((rc = io.begin()) || (rc = score_on_current_stream(h, io.src<float>(i_o), io.src<float>(i_p), n, height, width, io.dst<double>(o_s)))) return rc;
+    return io.finish();
 }
 
 }  // extern "C"

@@ -117,3 +117,23 @@ def test_runtime_info_names_the_hip_runtime_the_library_is_bound_to():
     tl = os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so")
     if os.path.exists(tl):   # a ROCm wheel: the torch-first process is on the bundled runtime
         assert got["torch"]["info"]["torch_bundled"] is True and os.path.realpath(got["torch"]["info"]["libamdhip64"]) == os.path.realpath(tl)
+
+
+@pytest.mark.gpu
+def test_memcpy_refuses_null_pointers(lib):
+    """msiren_memcpy_h2d / _d2h with a NULL host or device pointer and bytes > 0: MSIREN_E_HIP (what the runtime's refusal of the copy has
+    always come back as), nothing copied; zero bytes is no copy and no error."""
+    from mri_inr_amd import synthetic as syn
+    from test_gpu_parity import make_model
+
+    m = make_model(syn.make_state_dict(seed=7, trained_like=True))
+    x = np.arange(64, dtype=np.float32)
+    y = np.full(64, -1.0, np.float32)
+    d = m.device_array((64,)).copy_from(x)
+    for args in ((None, x.ctypes.data), (d.ptr, None)):
+        assert lib.msiren_memcpy_h2d(m._h, *args, x.nbytes) == _lib.E_HIP
+        assert b"null" in lib.msiren_last_error()
+    for args in ((None, d.ptr), (y.ctypes.data, None)):
+        assert lib.msiren_memcpy_d2h(m._h, *args, y.nbytes) == _lib.E_HIP
+    assert (y == -1.0).all() and np.array_equal(d.numpy(), x)
+    assert lib.msiren_memcpy_h2d(m._h, None, None, 0) == 0 and lib.msiren_memcpy_d2h(m._h, None, None, 0) == 0
