@@ -33,7 +33,9 @@
 extern "C" {
 #endif
 
-/* 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
+/* 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
+ * points in the handle's own trunk arithmetic) added.
+ * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
  * arbitrary points) added.
  * 6: msiren_sample_grad_* and msiren_reconstruct_slices_grad(_dev) (the model's spatial gradient) added.
  * 5: msiren_encode_modulate_tiles(_dev) (the prologue of msiren_forward_tiles alone) and msiren_last_prologue_kernel added.
@@ -42,7 +44,7 @@ extern "C" {
  * caller buffers (MSIREN_HOST_REGISTER) left the library.  2 (round 5): msiren_chain_* gone, msiren_profile_read_kernel /
  * msiren_last_trunk_kernel / msiren_device_pci added; sync no longer returns MSIREN_E_RANGE.  A library of another number refuses
  * msiren_create. */
-#define MSIREN_ABI_VERSION 7
+#define MSIREN_ABI_VERSION 8
 
 #if defined(__GNUC__)
 #define MSIREN_API __attribute__((visibility("default")))
@@ -311,6 +313,21 @@ MSIREN_API int msiren_sample_ragged_mods(msiren_handle h, const float* coords_ho
                                          const float* mods_host, int64_t B, int64_t T, float* out_host /* (T) */);
 MSIREN_API int msiren_sample_ragged_mods_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B,
                                              int64_t T, float* out_dev);
+/* NATIVE: the value forms above in the handle's OWN trunk arithmetic -- same arguments, same checks, same clamping of device offsets.
+ * Where the handle's trunk is a split-fp16 one (MSIREN_PREC_F16X3, dim_hidden = 256, no residual, num_layers 2..11) the launch is
+ * "siren_trunk_f16x3n_ragged_kernel<ACT,R,LFIX>": the register-resident split-fp16 trunk with layer 0 computed in the kernel (the exact
+ * trunk's two fp32 FMAs and its sine) instead of read from a table, so an output is inside the project norm of the fp64 reference
+ * (max <= 1e-4, rms <= 1e-5 of max|ref|) but NOT the exact forms' bits, nor msiren_sample_mods' (whose layer-0 table is built in fp64).
+ * A coordinate's bits depend on the coordinate and its modulation rows only, not on its place in the set, the batch or the stream.
+ * Domain guard: behind the launch, on the same stream, "siren_trunk_f32_ragged_cond_kernel<ACT>" re-evaluates the whole call in exact fp32
+ * iff a scaled modulation row did not fit fp16 -- such a call returns the exact forms' bits, on the synchronous and the _dev form alike
+ * (msiren_range_events counts it at the next synchronisation).  On every other handle (fp32, the 16-bit trunks at dim_hidden = 512,
+ * MSIREN_PREC_F16 / BF16 elsewhere, residual) these ARE the exact forms: same launch, same bits.  msiren_profile_read_kernel names the
+ * kernel that ran.  The gradient forms have no native counterpart. */
+MSIREN_API int msiren_sample_ragged_mods_native(msiren_handle h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B,
+                                                int64_t T, float* out_host);
+MSIREN_API int msiren_sample_ragged_mods_native_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B,
+                                                    int64_t T, float* out_dev);
 MSIREN_API int msiren_sample_ragged_grad_mods(msiren_handle h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B,
                                               int64_t T, float* out_host /* (T) or NULL */, float* grad_host /* (2, T) */);
 MSIREN_API int msiren_sample_ragged_grad_mods_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B,
@@ -336,6 +353,12 @@ MSIREN_API int msiren_resample_slices(msiren_handle h, const float* images_host,
                                       const float* points_host, int64_t M, float* out_host);
 MSIREN_API int msiren_resample_slices_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
                                           const float* points_dev, int64_t M, float* out_dev);
+/* msiren_resample_slices(_dev) with the trunk step in the handle's own arithmetic (msiren_sample_ragged_mods_native above: kernel, domain
+ * guard and fallback are the same); binning, weights and blend are unchanged, so val_k is the native trunk's value in the formula above. */
+MSIREN_API int msiren_resample_slices_native(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                             const float* points_host, int64_t M, float* out_host);
+MSIREN_API int msiren_resample_slices_native_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                                 const float* points_dev, int64_t M, float* out_dev);
 MSIREN_API int msiren_resample_slices_grad(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
                                            const float* points_host, int64_t M, float* out_host /* or NULL */, float* grad_host);
 MSIREN_API int msiren_resample_slices_grad_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,

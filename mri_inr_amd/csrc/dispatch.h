@@ -126,6 +126,25 @@ inline TrunkPick pick_trunk(const DispatchHandle& d, const CallMode& m, int64_t 
     return t;
 }
 
+// ---- per-patch coordinate sets, the *_native forms (msiren_sample_ragged_mods_native, msiren_resample_slices_native) --------------
+// The handle's own trunk arithmetic where that is a split-fp16 trunk: siren_trunk_f16x3n_ragged_kernel<ACT,ring,lfix> (a list of its
+// own: trunk_instances.h), the instance by depth as pick_trunk chooses the register-resident one for a call on its own -- L = 5: the
+// straight-line form on the ring of 3; L = 2..4: the loop form on the ring of 4; L = 6..11: the loop form on the ring of 3.  Everything
+// else (fp32 handles, the single-product 16-bit trunks at H = 512, MSIREN_PREC_F16 / BF16 at other widths, residual models, H or L
+// outside the split-fp16 shape) is not native: those handles run the exact-fp32 ragged kernels and return their bits.
+struct RaggedNativePick {
+    bool native = false;
+    int ring = 0, lfix = 0;
+};
+inline RaggedNativePick ragged_native_pick(const DispatchHandle& d) {
+    RaggedNativePick r;
+    if (d.x1_ready || !use_f16x3(d) || d.H != 256 || d.L < 2) return r;
+    r.native = true;
+    r.lfix = d.L == 5 ? 5 : 0;
+    r.ring = d.L != 5 && d.f16_ring4_fits ? 4 : 3;
+    return r;
+}
+
 // ---- prologue (tiles -> modulations) ------------------------------------------------------------------------------------------
 // The split-fp16 one-launch prologue (handles with em_enc / em_mod; otherwise the exact-fp32 launches per layer).
 struct ProloguePick {

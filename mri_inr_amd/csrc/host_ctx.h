@@ -12,7 +12,8 @@
 //     sample_grid.hip      the trunk at caller-chosen coordinates and the slice pipeline at another output stride: the per-call layer-0
 //                          table (kernel: sample_grid.hip.h), msiren_sample_*, msiren_upsampled_*, the *_scaled entry points; the
 //                          gradient calls (msiren_sample_grad_*, msiren_reconstruct_slices_grad: siren_trunk_f32_jet.hip.h)
-//     resample.hip         one coordinate set per patch: msiren_sample_ragged_* (kernels: siren_trunk_f32_ragged.hip.h), and the
+//     resample.hip         one coordinate set per patch: msiren_sample_ragged_* (kernels: siren_trunk_f32_ragged.hip.h; the *_native
+//                          forms: siren_trunk_f16x3n_ragged.hip.h), and the
 //                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
@@ -234,10 +235,15 @@ int launch_trunk_f32_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, co
 int launch_trunk_f32_jet_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev /* may be null */, float* grad_dev /* (2, reps, T) */,
                                 float gscale);
 
+// The same sets in the handle's own trunk arithmetic (the *_native entry points): siren_trunk_f16x3n_ragged_kernel where
+// ragged_native_pick (dispatch.h) says so, with the exact-fp32 ragged trunk as the conditional launch of the domain guard behind it
+// (siren_trunk_f32_ragged_cond_kernel); on every other handle launch_trunk_f32_ragged, bit for bit.  items: NP + 1 words as above.
+int launch_trunk_ragged_native(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev /* (reps, T) */);
+
 // the reconstruction of n slices at M points shared by them (resample.hip.h); grad: out_dev may be null, grad_dev (2, n, M)
 int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad);  // 0, or MSIREN_E_INVALID: the model, or too many points
 int resample_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
-                    float* grad_dev, bool grad);
+                    float* grad_dev, bool grad, bool native = false);  // native (values only): launch_trunk_ragged_native
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 

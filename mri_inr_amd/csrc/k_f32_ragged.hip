@@ -4,4 +4,5 @@
 namespace msiren {
 MSIREN_F32_RAGGED_INSTANCES(MSIREN_DEFINE_TRUNK)
 MSIREN_F32_JET_RAGGED_INSTANCES(MSIREN_DEFINE_TRUNK)
+MSIREN_F32_RAGGED_COND_INSTANCES(MSIREN_DEFINE_TRUNK)
 }  // namespace msiren

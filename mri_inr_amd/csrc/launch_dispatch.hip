@@ -9,6 +9,7 @@
 #include "encoder_modulator.hip.h"
 #include "encoder_modulator_f16x3.hip.h"
 #include "siren_trunk_f16x3n.hip.h"
+#include "siren_trunk_f16x3n_ragged.hip.h"
 #include "siren_trunk_f16x3h.hip.h"
 #include "siren_trunk_f16x3w.hip.h"
 #include "siren_trunk_f32.hip.h"
@@ -25,6 +26,8 @@ MSIREN_TRUNK_INSTANCES(MSIREN_EXTERN_TRUNK)
 MSIREN_F32_JET_INSTANCES(MSIREN_EXTERN_TRUNK)
 MSIREN_F32_RAGGED_INSTANCES(MSIREN_EXTERN_TRUNK)
 MSIREN_F32_JET_RAGGED_INSTANCES(MSIREN_EXTERN_TRUNK)
+MSIREN_F16X3N_RAGGED_INSTANCES(MSIREN_EXTERN_TRUNK)
+MSIREN_F32_RAGGED_COND_INSTANCES(MSIREN_EXTERN_TRUNK)
 MSIREN_PROLOGUE_INSTANCES(MSIREN_EXTERN_PROLOGUE)
 }  // namespace msiren
 
@@ -74,6 +77,20 @@ const RaggedInstance kRaggedInstances[] = {
     MSIREN_F32_RAGGED_INSTANCES(MSIREN_RAGGED_ROW) MSIREN_F32_JET_RAGGED_INSTANCES(MSIREN_JET_RAGGED_ROW)
 #undef MSIREN_RAGGED_ROW
 #undef MSIREN_JET_RAGGED_ROW
+};
+
+// The split-fp16 ragged trunk's instances and the conditional exact-fp32 ragged trunk behind them (lists of their own, too)
+struct F16RaggedInstance { const void* k; const char* name; int act, ring, lfix; };
+const F16RaggedInstance kF16RaggedInstances[] = {
+#define MSIREN_F16_RAGGED_ROW(fam, act, ring, lfix) {(const void*)msiren::siren_trunk_##fam##_kernel<act, ring, lfix>, "siren_trunk_" #fam "_kernel<" #act "," #ring "," #lfix ">", act, ring, lfix},
+    MSIREN_F16X3N_RAGGED_INSTANCES(MSIREN_F16_RAGGED_ROW)
+#undef MSIREN_F16_RAGGED_ROW
+};
+struct RaggedCondInstance { const void* k; const char* name; };
+const RaggedCondInstance kRaggedCondInstances[] = {  // [ACT]
+#define MSIREN_RAGGED_COND_ROW(fam, act) {(const void*)msiren::siren_trunk_##fam##_kernel<act>, "siren_trunk_" #fam "_kernel<" #act ">"},
+    MSIREN_F32_RAGGED_COND_INSTANCES(MSIREN_RAGGED_COND_ROW)
+#undef MSIREN_RAGGED_COND_ROW
 };
 
 // Launch of kernel `k` with `lds` bytes of dynamic LDS on stream `s` of the handle.  The kernel's LDS limit is raised once per handle.
@@ -433,6 +450,69 @@ int launch_trunk_f32_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, co
 int launch_trunk_f32_jet_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev, float* grad_dev, float gscale) {
     if (!grad_dev) return fail(MSIREN_E_INVALID, "null gradient output");
     return launch_ragged(h, c, r, mods_dev, out_dev, grad_dev, gscale);
+}
+
+// The handle's own trunk arithmetic over per-patch sets (siren_trunk_f16x3n_ragged.hip.h), beside launch_ragged: the item table in chunks of
+// 32, the trunk over the bound reps * (ceil(T / 32) + NP) of units with the stream's pass counter -- how many of them are passes only the
+// device knows (first[NP]), so the counter is reset behind the launch as behind a plan launch -- then the exact-fp32 ragged trunk as the
+// conditional launch of the domain guard, with the flag word and number launch_trunk_f32_cond uses: a flagged call holds the exact path's
+// bits, on the synchronous and the _dev forms alike.  Named in the profile report like the other ragged kernels; not msiren_last_trunk_kernel.
+int launch_trunk_ragged_native(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev) {
+    const msiren::RaggedNativePick pk = msiren::ragged_native_pick(h->dh);
+    if (!pk.native) return launch_trunk_f32_ragged(h, c, r, mods_dev, out_dev);
+    int rc = ragged_check(r, 32);
+    if (rc) return rc;
+    if (r.T == 0 || r.NP == 0) return 0;
+    if (!out_dev) return fail(MSIREN_E_INVALID, "null output");
+    if (r.rows < 1 || r.rows > 0x7fffffffLL) return fail(MSIREN_E_INVALID, "per-patch coordinate sets: %lld modulation rows", (long long)r.rows);
+    const int act = h->cfg.activation == MSIREN_ACT_MORLET ? 1 : 0;
+    const F16RaggedInstance* fi = std::begin(kF16RaggedInstances);
+    while (fi != std::end(kF16RaggedInstances) && (fi->act != act || fi->ring != pk.ring || fi->lfix != pk.lfix)) ++fi;
+    if (fi == std::end(kF16RaggedInstances)) return fail(MSIREN_E_INVALID, "no split-fp16 ragged trunk for num_layers=%d", h->L);
+    msiren::TrunkF16RaggedParams p{};
+    p.t.l0 = h->d_l0;
+    p.t.wp = (const _Float16*)h->d_wp16n;
+    p.t.bias = h->d_bias16;
+    p.t.wout = h->d_wout16;
+    p.t.mods = mods_dev;
+    p.t.out = out_dev;
+    for (int i = 0; i < 16; ++i) p.t.winv[i] = h->mscale16[i];
+    p.t.bout = h->bout;
+    p.t.cg0 = h->cg0;
+    p.t.cg = h->cg;
+    p.t.B = (int)r.rows;
+    p.t.L = h->L;
+    p.r = {r.coords, r.offsets, r.items, r.pos, (int)r.NP, (int)r.T, (int)r.reps};
+    const int64_t bound = r.reps * ((r.T + 31) / 32 + r.NP), passes = (bound + 3) / 4;  // (< 2^31: ragged_check)
+    hipStream_t st = h->sc[c.stream].s;
+    hipLaunchKernelGGL(msiren::ragged_items_kernel<32>, dim3(1), dim3(256), 0, st, r.offsets, (int)r.NP, (int)r.T, r.items);
+    HIPCHK(hipGetLastError());
+    if (++h->range_epoch == 0) h->range_epoch = 1;  // this launch's number (never 0: the flag word's rest state)
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1)) || (rc = queue_for_launch(h, c.stream, passes, &p.t.pass_counter, &p.t.pass_base))) return rc;
+    p.t.status = p.t.pass_counter + 16;
+    p.t.status_val = (int)h->range_epoch;
+    const int lds = pk.ring == 4 ? msiren::F16Lds<4>::total(h->L) : msiren::F16Lds<3>::total(h->L);
+    const int grid = (int)std::min<int64_t>(h->num_cus, passes);
+    if ((rc = queue_launched(h, c.stream, launch_kernel(h, c.stream, fi->k, grid, lds, p)))) return rc;
+    if ((rc = queue_reset_after_plan_launch(h, c.stream, false)) || (rc = profile_end(h, c.stream, e1, r.reps * r.T, fi->name))) return rc;
+    // the conditional launch: the exact-fp32 value kernel over the same sets (items of 64: its own prefix, behind the native trunk on the stream)
+    msiren::TrunkRaggedParams q{};
+    Call plain = c;
+    plain.cs = CoordSet{};
+    plain.plan = nullptr;
+    q.t = make_trunk_params(h, plain, mods_dev, h->H, r.rows, out_dev);  // (H = 256 = HP: no padding of the rows)
+    q.t.grid = r.coords;
+    q.t.cond = p.t.status;
+    q.t.cond_val = p.t.status_val;
+    q.t.host_flag = h->status_dev;
+    q.offsets = r.offsets, q.first = r.items, q.pos = r.pos, q.gscale = 1.f;
+    q.NP = (int)r.NP, q.T = (int)r.T, q.reps = (int)r.reps;
+    q.bound = (int)((r.T + 63) / 64 + r.NP);
+    hipLaunchKernelGGL(msiren::ragged_items_kernel<64>, dim3(1), dim3(256), 0, st, r.offsets, q.NP, q.T, r.items);
+    HIPCHK(hipGetLastError());
+    if ((rc = profile_begin(h, c.stream, &e1)) || (rc = launch_kernel(h, c.stream, kRaggedCondInstances[act].k, r.reps * q.bound, 256 * 256 + 256 * 16, q))) return rc;
+    return profile_end(h, c.stream, e1, 0, kRaggedCondInstances[act].name);
 }
 
 // Behind every split-fp16 trunk launch, on the same stream: the exact-fp32 trunk over the same batch as a conditional launch
@@ -893,7 +973,8 @@ int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, 
 }
 
 // The reconstruction at arbitrary points (kernels: resample.hip.h): the slice prologue, then on the same stream
-// bin the points by covering tile -> ragged exact-fp32 trunk, replicated over the slices, patch s NP + t on the plan's row -> blend.
+// bin the points by covering tile -> ragged exact-fp32 trunk (`native`: the handle's own, launch_trunk_ragged_native), replicated over the
+// slices, patch s NP + t on the plan's row -> blend.
 // `grad`: value (out_dev may be null) and the two gradient planes grad_dev (2, n, M), per reconstruction pixel.
 int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad) {
     int rc;
@@ -913,7 +994,7 @@ int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int6
 }
 
 int resample_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M,
-                    float* out_dev, float* grad_dev, bool grad) {
+                    float* out_dev, float* grad_dev, bool grad, bool native) {
     int rc = resample_check(h, n, height, width, M, grad);
     if (rc) return rc;
     if (n > 0 && M > 0 && (!images_dev || !points_dev || (grad ? !grad_dev : !out_dev))) return fail(MSIREN_E_INVALID, "null argument");
@@ -954,7 +1035,7 @@ int resample_slices(msiren_handle h, const Call& c, const float* images_dev, int
     const RaggedSet r{rp.coords, rp.offsets, T, NPt, n, plan + 2 + NP, NP, items};
     const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
     if (grad) rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, out_dev ? rec : nullptr, rec + (size_t)n * T, gscale);
-    else rc = launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
+    else rc = native ? launch_trunk_ragged_native(h, pc, r, (const float*)sc.mods.p, rec) : launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
     if (rc || (rc = profile_begin(h, c.stream, &e1))) return rc;
     const unsigned gb = (unsigned)((n * M + 255) / 256);
     if (out_dev) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, out_dev, (int)n, (int)M, K, (int)NPt, (int)T, 1);

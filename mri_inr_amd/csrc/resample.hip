@@ -1,6 +1,7 @@
 // One coordinate set per patch (include/msiren.h): msiren_sample_ragged_* -- SirenNet.forward, and its spatial
-// gradient, with patch b evaluated at coords[offsets[b] : offsets[b + 1]].  Always the exact-fp32 trunks, on handles of every precision
+// gradient, with patch b evaluated at coords[offsets[b] : offsets[b + 1]].  The exact-fp32 trunks, on handles of every precision
 // (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
+// The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
 #include "host_buffers.h"
 #include "host_ctx.h"
 
@@ -21,7 +22,8 @@ int check_ragged_args(msiren_ctx* h, const float* coords, const int32_t* offsets
     return 0;
 }
 
-int ragged_dev(msiren_ctx* h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B, int64_t T, float* out_dev, float* grad_dev, bool grad) {
+int ragged_dev(msiren_ctx* h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B, int64_t T, float* out_dev, float* grad_dev, bool grad,
+               bool native = false) {
     RaggedSet r;
     int rc = check_ragged_args(h, coords_dev, offsets_dev, mods_dev, B, T, out_dev, grad_dev, grad, &r);
     if (rc || B == 0 || T == 0) return rc;
@@ -31,12 +33,13 @@ int ragged_dev(msiren_ctx* h, const float* coords_dev, const int32_t* offsets_de
     auto& sc = h->sc[c.stream];
     if ((rc = ensure(h, sc.ragged, (size_t)(B + 1) * sizeof(int)))) return rc;
     r.items = (int*)sc.ragged.p;
-    return grad ? launch_trunk_f32_jet_ragged(h, c, r, mods_dev, out_dev, grad_dev, 1.0f) : launch_trunk_f32_ragged(h, c, r, mods_dev, out_dev);
+    if (grad) return launch_trunk_f32_jet_ragged(h, c, r, mods_dev, out_dev, grad_dev, 1.0f);
+    return native ? launch_trunk_ragged_native(h, c, r, mods_dev, out_dev) : launch_trunk_f32_ragged(h, c, r, mods_dev, out_dev);
 }
 
 // one synchronous one-chunk call on host pointers, as the sampling calls: coords + offsets + mods -> [out], [grad]
 int ragged_host(msiren_ctx* h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B, int64_t T, float* out_host, float* grad_host,
-                bool grad) {
+                bool grad, bool native = false) {
     RaggedSet r;
     int rc = check_ragged_args(h, coords_host, offsets_host, mods_host, B, T, out_host, grad_host, grad, &r);
     if (rc || B == 0 || T == 0) return rc;
@@ -55,14 +58,17 @@ int ragged_host(msiren_ctx* h, const float* coords_host, const int32_t* offsets_
     const int o_out = io.out(out_host, no, HOST_IN_PLACE), o_grad = io.out(grad ? grad_host : nullptr, 2 * no, HOST_IN_PLACE);
     if ((rc = io.begin())) return rc;
     r.coords = io.src<float>(i_c), r.offsets = io.src<int>(i_off), r.items = d_off + (B + 1);
-    rc = grad ? launch_trunk_f32_jet_ragged(h, c, r, io.src<float>(i_m), io.dst<float>(o_out), io.dst<float>(o_grad), 1.0f)
-              : launch_trunk_f32_ragged(h, c, r, io.src<float>(i_m), io.dst<float>(o_out));
-    return rc ? rc : io.finish();
+    if (grad) rc = launch_trunk_f32_jet_ragged(h, c, r, io.src<float>(i_m), io.dst<float>(o_out), io.dst<float>(o_grad), 1.0f);
+    else if (native) rc = launch_trunk_ragged_native(h, c, r, io.src<float>(i_m), io.dst<float>(o_out));
+    else rc = launch_trunk_f32_ragged(h, c, r, io.src<float>(i_m), io.dst<float>(o_out));
+    if (rc || (rc = io.finish())) return rc;
+    if (native) (void)take_range_flag(h);  // informational: a flagged call holds the exact-fp32 trunk's bits already
+    return 0;
 }
 
 // the reconstruction at points, one synchronous one-chunk call on host pointers: images + points -> [out], [grad]
 int resample_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
-                  float* grad_host, bool grad) {
+                  float* grad_host, bool grad, bool native = false) {
     int rc = check(h);
     if (rc || (rc = resample_check(h, n, height, width, M, grad))) return rc;
     if (n == 0 || M == 0) return 0;
@@ -76,8 +82,10 @@ int resample_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t he
     const int i_img = io.in(images_host, ni, HOST_COPY), i_p = io.in(points_host, np, HOST_COPY, sc.coords.p);
     const int o_out = io.out(out_host, no, HOST_IN_PLACE), o_grad = io.out(grad ? grad_host : nullptr, 2 * no, HOST_IN_PLACE);
     if ((rc = io.begin())) return rc;
-    if ((rc = resample_slices(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_p), M, io.dst<float>(o_out), io.dst<float>(o_grad), grad))) return rc;
-    return io.finish();
+    if ((rc = resample_slices(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_p), M, io.dst<float>(o_out), io.dst<float>(o_grad), grad, native))) return rc;
+    if ((rc = io.finish())) return rc;
+    if (native) (void)take_range_flag(h);  // informational, as above
+    return 0;
 }
 
 }  // namespace
@@ -87,6 +95,15 @@ extern "C" {
 int msiren_resample_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");
     return resample_host(h, images_host, n, height, width, points_host, M, out_host, nullptr, false);
+}
+int msiren_resample_slices_native(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return resample_host(h, images_host, n, height, width, points_host, M, out_host, nullptr, false, true);
+}
+int msiren_resample_slices_native_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    return resample_slices(h, dev_call(h), images_dev, n, height, width, points_dev, M, out_dev, nullptr, false, true);
 }
 int msiren_resample_slices_grad(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
                                 float* grad_host) {
@@ -112,6 +129,14 @@ int msiren_sample_ragged_mods(msiren_handle h, const float* coords_host, const i
 int msiren_sample_ragged_mods_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B, int64_t T, float* out_dev) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");
     return ragged_dev(h, coords_dev, offsets_dev, mods_dev, B, T, out_dev, nullptr, false);
+}
+int msiren_sample_ragged_mods_native(msiren_handle h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B, int64_t T, float* out_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return ragged_host(h, coords_host, offsets_host, mods_host, B, T, out_host, nullptr, false, true);
+}
+int msiren_sample_ragged_mods_native_dev(msiren_handle h, const float* coords_dev, const int32_t* offsets_dev, const float* mods_dev, int64_t B, int64_t T, float* out_dev) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return ragged_dev(h, coords_dev, offsets_dev, mods_dev, B, T, out_dev, nullptr, false, true);
 }
 int msiren_sample_ragged_grad_mods(msiren_handle h, const float* coords_host, const int32_t* offsets_host, const float* mods_host, int64_t B, int64_t T, float* out_host,
                                    float* grad_host) {

@@ -97,6 +97,19 @@ __global__ __launch_bounds__(256, (HP <= 256 ? 2 : 1)) void siren_trunk_f32_ragg
     siren_trunk_f32_body<HP, ACT, RES, 0>(pr.t, sp, 0);
 }
 
+// The value kernel (H = 256, no residual) as the CONDITIONAL launch behind siren_trunk_f16x3n_ragged_kernel on the same stream: every
+// workgroup leaves unless that launch wrote its number to *cond (a scaled modulation beyond fp16: siren_trunk_f32_kernel's rule), so a
+// flagged call holds the exact path's bits.  pr.t.cond / cond_val / host_flag as launch_trunk_f32_cond sets them.
+template <int ACT>
+__global__ __launch_bounds__(256, 2) void siren_trunk_f32_ragged_cond_kernel(TrunkRaggedParams pr) {
+    ItemSpan sp;
+    size_t o;
+    if (__builtin_amdgcn_readfirstlane(*pr.t.cond) != pr.t.cond_val) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && pr.t.host_flag) *pr.t.host_flag = 1;  // (before the span test: workgroup 0's item may be a dropped patch)
+    if (!ragged_span<64>(pr, sp, o)) return;  // before any barrier
+    siren_trunk_f32_body<256, ACT, 0, 0>(pr.t, sp, 0);
+}
+
 template <int HP, int ACT>
 __global__ __launch_bounds__(256, 1) void siren_trunk_f32_jet_ragged_kernel(TrunkRaggedParams pr) {
     ItemSpan sp;

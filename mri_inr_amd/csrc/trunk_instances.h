@@ -41,6 +41,15 @@
     X(f32_ragged, 512,0,0) X(f32_ragged, 512,0,1) X(f32_ragged, 512,1,0) X(f32_ragged, 512,1,1)
 #define MSIREN_F32_JET_RAGGED_INSTANCES(X) X(f32_jet_ragged, 128,0) X(f32_jet_ragged, 128,1) X(f32_jet_ragged, 256,0) X(f32_jet_ragged, 256,1)
 
+// The split-fp16 trunk over one coordinate set per patch (siren_trunk_f16x3n_ragged_kernel<ACT,R,LFIX>: siren_trunk_f16x3n_ragged.hip.h,
+// layer 0 computed in the kernel), what the *_native ragged / resample calls run where ragged_native_pick (dispatch.h) says so: L = 5,
+// L = 2..4 (ring of 4), L = 6..11 (ring of 3).  Behind each of its launches: the exact-fp32 ragged trunk as a conditional launch
+// (siren_trunk_f32_ragged_cond_kernel<ACT>; H = 256, no residual).  Lists of their own as well.
+#define MSIREN_F16X3N_RAGGED_INSTANCES(X)                                                         \
+    X(f16x3n_ragged, 0,3,5) X(f16x3n_ragged, 0,4,0) X(f16x3n_ragged, 0,3,0)                       \
+    X(f16x3n_ragged, 1,3,5) X(f16x3n_ragged, 1,4,0) X(f16x3n_ragged, 1,3,0)
+#define MSIREN_F32_RAGGED_COND_INSTANCES(X) X(f32_ragged_cond, 0) X(f32_ragged_cond, 1)
+
 // the one-launch prologue (<family>_f16x3_kernel: encoder_modulator_f16x3.hip.h); latent_mods<NPH,NPZ,DEPTH,MODE>
 #define MSIREN_PROLOGUE_INSTANCES(X)                                                              \
     X(latent_mods, 2,2,2,3) X(latent_mods, 2,2,4,3) X(latent_mods, 2,2,8,3)                       \
@@ -54,6 +63,8 @@
 #define MSIREN_PARAMS_f32_jet (TrunkJetParams)
 #define MSIREN_PARAMS_f32_ragged (TrunkRaggedParams)
 #define MSIREN_PARAMS_f32_jet_ragged (TrunkRaggedParams)
+#define MSIREN_PARAMS_f32_ragged_cond (TrunkRaggedParams)
+#define MSIREN_PARAMS_f16x3n_ragged (TrunkF16RaggedParams)
 #define MSIREN_PARAMS_f16x3n (TrunkF16Params)
 #define MSIREN_PARAMS_f16x3h (TrunkF16Params)
 #define MSIREN_PARAMS_f16x3w (TrunkWsParams)

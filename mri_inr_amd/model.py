@@ -665,7 +665,7 @@ class ModulatedSiren:
         return self._sample(self._lib.msiren_sample_grad_mods, self._lib.msiren_sample_grad_mods_dev, mods, coords,
                             (self.num_layers, None, self.dim_hidden), 1, grad=True)
 
-    # ---- one coordinate set per patch: always the exact-fp32 trunks ----
+    # ---- one coordinate set per patch: the exact-fp32 trunks; exact=False: the handle's own arithmetic ----
     def _sample_ragged(self, host_fn, dev_fn, mods, coords, offsets, grad):
         """Marshalling of sample_mods_ragged(_grad): ``mods`` and ``coords`` as in _sample (numpy / torch / DeviceArray), ``offsets``
         (B + 1) integers on the host (numpy, torch, a sequence) -- checked here and uploaded -- or an int32 device tensor.  Any device
@@ -757,18 +757,23 @@ class ModulatedSiren:
                 outs = [torch.from_numpy(o) for o in outs]
         return tuple(outs) if grad else outs[0]
 
-    def sample_mods_ragged(self, mods, coords, offsets):
+    def sample_mods_ragged(self, mods, coords, offsets, *, exact=True):
         """mods (L, B, H), coords (T, 2), offsets (B + 1) -> (T,): ``SirenNet.forward`` with patch b evaluated at its OWN coordinate
-        set ``coords[offsets[b]:offsets[b + 1]]`` (msiren_sample_ragged_mods).  Always the exact-fp32 trunk, whatever the model's
-        precision: out[offsets[b] + i] is the bits of an fp32 model's ``sample_mods(mods[:, b:b + 1], coords_b)[0, i]``."""
-        return self._sample_ragged(self._lib.msiren_sample_ragged_mods, self._lib.msiren_sample_ragged_mods_dev, mods, coords, offsets, False)
+        set ``coords[offsets[b]:offsets[b + 1]]`` (msiren_sample_ragged_mods).  The exact-fp32 trunk, whatever the model's
+        precision: out[offsets[b] + i] is the bits of an fp32 model's ``sample_mods(mods[:, b:b + 1], coords_b)[0, i]``.
+        ``exact=False``: the model's own trunk arithmetic (msiren_sample_ragged_mods_native) -- on a split-fp16 model the split-fp16
+        trunk with layer 0 computed in the kernel, inside the norm of the reference, the trunk step 3.4 x faster on the call measured in
+        LAB_NOTES.md section 19; the same call, the same bits, on every other model."""
+        if exact:
+            return self._sample_ragged(self._lib.msiren_sample_ragged_mods, self._lib.msiren_sample_ragged_mods_dev, mods, coords, offsets, False)
+        return self._sample_ragged(self._lib.msiren_sample_ragged_mods_native, self._lib.msiren_sample_ragged_mods_native_dev, mods, coords, offsets, False)
 
     def sample_mods_ragged_grad(self, mods, coords, offsets):
         """As sample_mods_ragged -> (values (T,), grad (2, T)): value and ``d SirenNet.forward / d coords`` per coordinate, grad[0] along
         ``coords[:, 0]`` (rows) -- the bits of ``sample_mods_grad`` patch by patch (msiren_sample_ragged_grad_mods)."""
         return self._sample_ragged(self._lib.msiren_sample_ragged_grad_mods, self._lib.msiren_sample_ragged_grad_mods_dev, mods, coords, offsets, True)
 
-    def _resample(self, images, points, grad):
+    def _resample(self, images, points, grad, exact=True):
         self._ensure_committed()
         a = images.detach().cpu().numpy() if _is_torch(images) else np.asarray(images)
         a = np.ascontiguousarray(a, dtype=np.float32)
@@ -783,7 +788,7 @@ class ModulatedSiren:
         n, Hh, Ww = a.shape
         M = p.shape[0]
         outs = [np.empty(shape, dtype=np.float32) for shape in (((n, M), (2, n, M)) if grad else ((n, M),))]
-        fn = self._lib.msiren_resample_slices_grad if grad else self._lib.msiren_resample_slices
+        fn = self._lib.msiren_resample_slices_grad if grad else self._lib.msiren_resample_slices if exact else self._lib.msiren_resample_slices_native
         _lib.check(fn(self._h, a.ctypes.data, n, Hh, Ww, p.ctypes.data, M, *[o.ctypes.data for o in outs]))
         if single:
             outs = [outs[0][0]] + [o[:, 0] for o in outs[1:]]
@@ -793,12 +798,13 @@ class ModulatedSiren:
             outs = [torch.from_numpy(o) for o in outs]
         return tuple(outs) if grad else outs[0]
 
-    def resample(self, images, points):
+    def resample(self, images, points, *, exact=True):
         """images (n, Hh, Ww) or (Hh, Ww), points (M, 2) -> (n, M) or (M,): the reconstruction of ``reconstruct(images)`` read at real
         positions ``points[m] = (Y, X)`` in reconstruction pixel coordinates (integer (Y, X): the centre of ``recon[Y, X]``), one point
         set for all slices -- every covering tile's network evaluated at the point, blended with the fold's weights (build-defined,
-        DESIGN.md section 5.8; msiren_resample_slices).  Always the exact-fp32 trunk.  NaN where no tile covers the point."""
-        return self._resample(images, points, False)
+        DESIGN.md section 5.8; msiren_resample_slices).  The exact-fp32 trunk; ``exact=False``: the model's own trunk arithmetic
+        (msiren_resample_slices_native; sample_mods_ragged has the details).  NaN where no tile covers the point."""
+        return self._resample(images, points, False, exact)
 
     def resample_with_gradient(self, images, points):
         """As resample -> (values (n, M), grad (2, n, M)): grad per reconstruction pixel, grad[0] along the rows -- the weight-averaged
