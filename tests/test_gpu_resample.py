@@ -24,10 +24,10 @@ LO, HI = float(-PAD), float(NV * I - 1 + PAD)  # the cover of the whole slice: [
 NORM_MAX, NORM_RMS = 1e-4, 1e-5
 
 
-def build(sd, prec="fp32"):
-    m = ModulatedSiren(dim_in=2, dim_hidden=256, dim_out=1, num_layers=5, latent_dim=256, w0=1.0, w0_initial=30.0, use_bias=True,
+def build(sd, prec="fp32", act="sine", L=5):
+    m = ModulatedSiren(dim_in=2, dim_hidden=256, dim_out=1, num_layers=L, latent_dim=256, w0=1.0, w0_initial=30.0, use_bias=True,
                        dropout=0.1, modulate=True, encoder_type="custom", encoder_path=None, outer_patch_size=O, inner_patch_size=I,
-                       siren_patch_size=S, device="cuda", activation="sine", precision=prec)
+                       siren_patch_size=S, device="cuda", activation=act, precision=prec)
     m.load_state_dict(sd, strict=True)
     m.to("cuda")
     m.eval()
@@ -35,13 +35,14 @@ def build(sd, prec="fp32"):
 
 
 @functools.lru_cache(maxsize=None)
-def full_sd():
-    return syn.make_state_dict(seed=7, trained_like=True)
+def full_sd(L=5):
+    return syn.make_state_dict(seed=7, num_layers=L, trained_like=True)
 
 
 @functools.lru_cache(maxsize=None)
-def model(prec="fp32"):
-    return build(full_sd(), prec)
+def model(prec="fp32", act="sine", L=5):
+    """(tests/test_gpu_coordset_cases.py runs the same slices on a second model: Morlet, L = 3)"""
+    return build(full_sd(L), prec, act, L)
 
 
 @functools.lru_cache(maxsize=None)
@@ -73,30 +74,30 @@ def make_points(draw):
     return pts, dict(window=slice(0, len(window)), outside=slice(len(pts) - len(outside), len(pts)))
 
 
-def prologue(sd, tiles, dtype):
+def prologue(sd, tiles, dtype, L=5):
     z = orc.encoder_forward(sd, tiles, dtype=dtype)
-    return orc.modulator_forward(sd, z, num_layers=5, dtype=dtype)
+    return orc.modulator_forward(sd, z, num_layers=L, dtype=dtype)
 
 
-def reference_slice(img, pts, dtype, **kw):
-    sd = full_sd()
+def reference_slice(img, pts, dtype, act="sine", L=5, **kw):
+    sd = full_sd(L)
     patches, info = orc.image_to_patches(img, O, I)
     kept, black, _ = orc.filter_and_remember_black_patches(patches)
     assert info == (NV, NH)
-    mods = np.zeros((5, NV * NH, 256), dtype)
-    mods[:, [t for t in range(NV * NH) if t not in black]] = prologue(sd, kept, dtype)
-    val, grad = rr.resample(sd, mods, black, pts, NV, NH, S, I, num_layers=5, dtype=dtype, **kw)
+    mods = np.zeros((L, NV * NH, 256), dtype)
+    mods[:, [t for t in range(NV * NH) if t not in black]] = prologue(sd, kept, dtype, L)
+    val, grad = rr.resample(sd, mods, black, pts, NV, NH, S, I, num_layers=L, activation=act, dtype=dtype, **kw)
     return val, grad, black
 
 
 @functools.lru_cache(maxsize=None)
-def data():
+def data(act="sine", L=5):
     """The points (the first draw at which the reference's gradient ALONE sits inside the caps, as grad_reference.case_data draws), the
     fp64 reference of both slices and the gradient gate: 4 x the distance of the same chain in perturbed fp32, capped at the norm."""
     for draw in range(16):
         pts, parts = make_points(draw)
-        ref = [reference_slice(img, pts, np.float64) for img in images()]
-        f32 = [reference_slice(img, pts, np.float32, perturbed=True) for img in images()]
+        ref = [reference_slice(img, pts, np.float64, act, L) for img in images()]
+        f32 = [reference_slice(img, pts, np.float32, act, L, perturbed=True) for img in images()]
         val, grad = np.stack([r[0] for r in ref]), np.stack([r[1] for r in ref], axis=1)
         g32 = np.stack([r[1] for r in f32], axis=1)
         ok = np.isfinite(val[0])
