@@ -33,7 +33,8 @@
 extern "C" {
 #endif
 
-/* 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
+/* 9: msiren_resample_volume* (a stack of slices read as a volume at points (Z, Y, X), value, native value and gradient forms) added.
+ * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
  * arbitrary points) added.
@@ -44,7 +45,7 @@ extern "C" {
  * caller buffers (MSIREN_HOST_REGISTER) left the library.  2 (round 5): msiren_chain_* gone, msiren_profile_read_kernel /
  * msiren_last_trunk_kernel / msiren_device_pci added; sync no longer returns MSIREN_E_RANGE.  A library of another number refuses
  * msiren_create. */
-#define MSIREN_ABI_VERSION 8
+#define MSIREN_ABI_VERSION 9
 
 #if defined(__GNUC__)
 #define MSIREN_API __attribute__((visibility("default")))
@@ -363,6 +364,43 @@ MSIREN_API int msiren_resample_slices_grad(msiren_handle h, const float* images_
                                            const float* points_host, int64_t M, float* out_host /* or NULL */, float* grad_host);
 MSIREN_API int msiren_resample_slices_grad_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
                                                const float* points_dev, int64_t M, float* out_dev /* or NULL */, float* grad_dev);
+
+/* Build-defined: the n slices of a call read as a VOLUME, a stack along Z, at points (M, 3) = (Z, Y, X) float32.
+ * (Y, X) are reconstruction pixel coordinates exactly as above; Z is in slice units, an integer Z being slice Z of the call.  out (M);
+ * grad PLANAR (3, M): plane 0 per slice of Z, planes 1 and 2 per reconstruction pixel along rows and columns.
+ * With R_s(Y, X), G_s(Y, X) what msiren_resample_slices / _grad define for slice s (same cover rule, local coordinate, weights and fp32
+ * num / den over the covering tiles, a black tile 0 with its weight):
+ *     valid iff 0 <= Z <= n - 1 (the fp32 Z against the integers; false for a NaN);  z0 = floorf(Z),  f = Z - z0 (exact),  a0 = 1.0f - f
+ *     value forms:     out[m] = R_z0 if f == 0 (one slice; n = 1 is allowed), else fmaf(f, R_{z0+1}, a0 R_z0).  A slice of weight 0 is not
+ *                      evaluated.
+ *     gradient forms:  n >= 2 (MSIREN_E_INVALID otherwise), always two slices: z0' = min(z0, n - 2), f' = Z - z0' in [0, 1],
+ *                      R0, R1, G0, G1 of slices z0', z0' + 1;  select(A0, A1) = A0 if f' == 0, A1 if f' == 1, else fmaf(f', A1, (1.0f - f') A0)
+ *                      out[m] = select(R0, R1) -- the bits of the exact value form;  grad[0] = R1 - R0 (one fp32 subtraction: the slope of
+ *                      the segment that contains Z, at an interior integer the one to its right);  grad[1], grad[2] = select over G0, G1.
+ *                      The derivative of the fold weights is not part of grad.
+ * An invalid Z, a non-finite (Y, X) and a point no tile covers give NaN at that m in every plane and touch nothing else.  At integer Z = s
+ * value and in-plane gradient are the bits of msiren_resample_slices / _grad of slice s at (Y, X); a permutation of the points permutes
+ * the outputs; the call on slices a .. b - 1 with Z - a gives the bits of the whole stack for points inside [a, b - 1] (grad[0] at
+ * Z = b - 1 excepted: the whole stack's segment there is the next one).
+ * The pipeline, on the call's stream: msiren_resample_slices' prologue -> the points binned by (slice, tile) -> the ragged trunk over those
+ * n nV nH bins, at most 2 M K entries (K = ceil(S / I)^2), whatever n is -> blend.  The plain and _grad forms run the exact-fp32 trunks on
+ * handles of every precision (the _grad forms take what the gradient calls take); the _native forms the handle's own trunk arithmetic as
+ * msiren_sample_ragged_mods_native does: same kernel, domain guard and fallback.  32 M K + 8 M and 16 n nV nH must stay below 2^30
+ * (MSIREN_E_INVALID beyond, naming the product); ceil(S / I) <= 4.  n = 0 or M = 0 does nothing.  Host-pointer forms: synchronous one-chunk
+ * calls; the _dev forms enqueue on the stream rotation.  Under msiren_profile_enable: "resample_volume_bin_kernels", the ragged trunk under
+ * its name, "resample_volume_blend_kernel". */
+MSIREN_API int msiren_resample_volume(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                      const float* points_host /* (M, 3) */, int64_t M, float* out_host /* (M) */);
+MSIREN_API int msiren_resample_volume_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                          const float* points_dev, int64_t M, float* out_dev);
+MSIREN_API int msiren_resample_volume_native(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                             const float* points_host, int64_t M, float* out_host);
+MSIREN_API int msiren_resample_volume_native_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                                 const float* points_dev, int64_t M, float* out_dev);
+MSIREN_API int msiren_resample_volume_grad(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                           const float* points_host, int64_t M, float* out_host /* (M) or NULL */, float* grad_host /* (3, M) */);
+MSIREN_API int msiren_resample_volume_grad_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                               const float* points_dev, int64_t M, float* out_dev /* (M) or NULL */, float* grad_dev /* (3, M) */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

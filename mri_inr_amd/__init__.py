@@ -7,6 +7,7 @@ Public surface mirrors the reference's: ``ModulatedSiren`` (src/networks/modulat
 
 from .configuration import load_configuration, model_kwargs  # noqa: F401
 from .model import ModulatedSiren  # noqa: F401
+from .volume import plane_points  # noqa: F401
 
-__all__ = ["ModulatedSiren", "load_configuration", "model_kwargs"]
+__all__ = ["ModulatedSiren", "load_configuration", "model_kwargs", "plane_points"]
 __version__ = "0.1.0"

@@ -14,7 +14,8 @@
 //                          gradient calls (msiren_sample_grad_*, msiren_reconstruct_slices_grad: siren_trunk_f32_jet.hip.h)
 //     resample.hip         one coordinate set per patch: msiren_sample_ragged_* (kernels: siren_trunk_f32_ragged.hip.h; the *_native
 //                          forms: siren_trunk_f16x3n_ragged.hip.h), and the
-//                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h)
+//                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h) and
+//                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -243,6 +244,10 @@ int launch_trunk_ragged_native(msiren_ctx* h, const Call& c, const RaggedSet& r,
 // the reconstruction of n slices at M points shared by them (resample.hip.h); grad: out_dev may be null, grad_dev (2, n, M)
 int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad);  // 0, or MSIREN_E_INVALID: the model, or too many points
 int resample_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
+                    float* grad_dev, bool grad, bool native = false);  // native (values only): launch_trunk_ragged_native
+// a stack of n slices read as a volume at M points (Z, Y, X) (resample_volume.hip.h): out_dev (M); grad: out_dev may be null, grad_dev (3, M), n >= 2
+int resample_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad);  // 0, or MSIREN_E_INVALID, naming what is too large
+int resample_volume(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
                     float* grad_dev, bool grad, bool native = false);  // native (values only): launch_trunk_ragged_native
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);

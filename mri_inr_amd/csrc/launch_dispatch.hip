@@ -19,6 +19,7 @@
 #include "siren_trunk_x1w.hip.h"
 #include "tiling.hip.h"
 #include "resample.hip.h"
+#include "resample_volume.hip.h"
 #include "launch_dispatch.h"
 
 namespace msiren {  // the trunk / prologue kernels are compiled in their own translation units (k_*.hip)
@@ -1042,6 +1043,83 @@ int resample_slices(msiren_handle h, const Call& c, const float* images_dev, int
     if (grad) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec + (size_t)n * T, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, grad_dev, (int)n, (int)M, K, (int)NPt, (int)T, 2);
     HIPCHK(hipGetLastError());
     return profile_end(h, c.stream, e1, n * M, "resample_blend_kernel");
+}
+
+// A stack of slices read as a volume at points (Z, Y, X) (kernels: resample_volume.hip.h): the slice prologue, then on
+// the same stream bin the points by (slice, tile) -> the ragged trunk over those n nV nH bins as its patches, one replica, on the plan's rows
+// (`native`: launch_trunk_ragged_native) -> blend across tiles and the pair of slices.  Scratch grows with 2 M K, not with n.
+// `grad`: value (out_dev may be null) and the three gradient planes grad_dev (3, M): per slice of Z, per reconstruction pixel rows, columns.
+int resample_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad) {
+    int rc;
+    if (grad ? (rc = jet_supported(h)) : 0) return rc;
+    if (n < 0 || M < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, M=%lld)", (long long)n, (long long)M);
+    if (grad && n == 1) return fail(MSIREN_E_INVALID, "the volume's gradient needs two slices at least (n=1)");
+    if ((rc = check_tile_size(h, false))) return rc;
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    if (KA > msiren::RESAMPLE_MAX_KA)
+        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
+    int32_t nV, nH;
+    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
+    // every buffer of the call below 2^31 bytes, every index in 32 bits.  The stream's bin scratch holds 32 M K + 8 M bytes over the points
+    // (2 M K entries: slot and 8 bytes of coordinates; tile and weight per M K; pair and fraction per M) and 16 n nV nH over the bins: each
+    // half below 2^30.  The trunk's three planes are 24 M K bytes.  n is compared as an fp32 integer.
+    if (M > 0x0fffffffLL || 32 * M * K + 8 * M > 0x3fffffffLL)
+        return fail(MSIREN_E_INVALID, "too many points for one call: %lld points x %d covering tiles (32 M K + 8 M must stay below 2^30)", (long long)M, K);
+    if (n > 0x00ffffffLL || 16 * n * nV * nH > 0x3fffffffLL)
+        return fail(MSIREN_E_INVALID, "too many slices for one call: %lld slices x %d x %d tiles (16 n nV nH must stay below 2^30)", (long long)n, nV, nH);
+    return 0;
+}
+
+int resample_volume(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M,
+                    float* out_dev, float* grad_dev, bool grad, bool native) {
+    int rc = resample_volume_check(h, n, height, width, M, grad);
+    if (rc) return rc;
+    if (n > 0 && M > 0 && (!images_dev || !points_dev || (grad ? !grad_dev : !out_dev))) return fail(MSIREN_E_INVALID, "null argument");
+    if (n == 0 || M == 0) return 0;
+    if ((uintptr_t)points_dev % 4) return fail(MSIREN_E_INVALID, "device points must be 4-byte aligned");
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    int32_t nV, nH;
+    (void)msiren_recon_shape(h, height, width, &nV, &nH);
+    const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, MK = M * K, T = 2 * MK;
+    if ((rc = check_reflect_padding(h, height, width))) return rc;
+    auto& sc = h->sc[c.stream];
+    // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile M K][pair M][coords 2 T, 8-byte aligned][w M K][f M]
+    const size_t nint = (size_t)(4 * NP + 2 + T + MK + M + 1) & ~(size_t)1;
+    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, (nint + 2 * (size_t)T + MK + M) * 4)) ||
+        (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * (grad ? 3 : 1))))
+        return rc;
+    Call pc;
+    bool fused;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &pc, &fused))) return rc;
+    hipStream_t st = sc.s;
+    int* const ib = (int*)sc.ragged.p;
+    msiren::ResampleVolumeParams vp{points_dev, (int)M, (int)n, nV, nH, h->S, h->I, (h->S - h->I) / 2, KA, grad ? 1 : 0};
+    vp.counts = ib, vp.cursors = ib + NP, vp.offsets = ib + 2 * NP;
+    int* const items = vp.offsets + NP + 1;
+    vp.ent = items + NP + 1, vp.tile = vp.ent + T, vp.pair = vp.tile + MK;
+    vp.coords = (float*)(ib + nint), vp.w = vp.coords + 2 * T, vp.f = vp.w + MK;
+    const unsigned gm = (unsigned)((M + 255) / 256);
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+    HIPCHK(hipMemsetAsync(ib, 0, (size_t)2 * NP * sizeof(int), st));
+    hipLaunchKernelGGL(msiren::resample_volume_count_kernel, dim3(gm), dim3(256), 0, st, vp);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, vp.counts, (int)NP, vp.offsets);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::resample_volume_fill_kernel, dim3(gm), dim3(256), 0, st, vp);
+    HIPCHK(hipGetLastError());
+    if ((rc = profile_end(h, c.stream, e1, M, "resample_volume_bin_kernels"))) return rc;
+    float* const rec = (float*)sc.rec.p;  // [value (T)][d/d row][d/d column]
+    const int* plan = (const int*)sc.plan.p;
+    const RaggedSet r{vp.coords, vp.offsets, T, NP, 1, plan + 2 + NP, NP, items};
+    const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
+    if (grad) rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale);  // (grad[0] needs the values)
+    else rc = native ? launch_trunk_ragged_native(h, pc, r, (const float*)sc.mods.p, rec) : launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
+    if (rc || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    hipLaunchKernelGGL(msiren::resample_volume_blend_kernel, dim3(gm), dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, (const int*)sc.keep.p, vp.pair, vp.f,
+                       out_dev, grad ? grad_dev : nullptr, (int)M, K, (int)NPt, (int)T, grad ? 3 : 1, grad ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, M, "resample_volume_blend_kernel");
 }
 
 // msiren_weighted_fold_dev with the output side of another stride (kernel S', stride I', padding pad'): complete tiles, no black flags

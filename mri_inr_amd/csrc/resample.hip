@@ -2,6 +2,7 @@
 // gradient, with patch b evaluated at coords[offsets[b] : offsets[b + 1]].  The exact-fp32 trunks, on handles of every precision
 // (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
 // The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
+// msiren_resample_slices* and msiren_resample_volume* (DESIGN.md sections 5.8, 5.9) are built on these trunks: launch_dispatch.hip.
 #include "host_buffers.h"
 #include "host_ctx.h"
 
@@ -88,9 +89,61 @@ int resample_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t he
     return 0;
 }
 
+// a stack read as a volume at points (Z, Y, X), one synchronous one-chunk call on host pointers: images + points -> [out (M)], [grad (3, M)]
+int volume_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
+                float* grad_host, bool grad, bool native = false) {
+    int rc = check(h);
+    if (rc || (rc = resample_volume_check(h, n, height, width, M, grad))) return rc;
+    if (n == 0 || M == 0) return 0;
+    if (!images_host || !points_host || (grad ? !grad_host : !out_host)) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    Call c = make_call(h, true);
+    auto& sc = h->sc[c.stream];
+    const size_t ni = (size_t)n * height * width * sizeof(float), np = (size_t)M * 3 * sizeof(float), no = (size_t)M * sizeof(float);
+    if ((rc = ensure(h, sc.coords, np))) return rc;
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_p = io.in(points_host, np, HOST_COPY, sc.coords.p);
+    const int o_out = io.out(out_host, no, HOST_IN_PLACE), o_grad = io.out(grad ? grad_host : nullptr, 3 * no, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = resample_volume(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_p), M, io.dst<float>(o_out), io.dst<float>(o_grad), grad, native))) return rc;
+    if ((rc = io.finish())) return rc;
+    if (native) (void)take_range_flag(h);  // informational, as above
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+int msiren_resample_volume(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return volume_host(h, images_host, n, height, width, points_host, M, out_host, nullptr, false);
+}
+int msiren_resample_volume_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    return resample_volume(h, dev_call(h), images_dev, n, height, width, points_dev, M, out_dev, nullptr, false);
+}
+int msiren_resample_volume_native(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return volume_host(h, images_host, n, height, width, points_host, M, out_host, nullptr, false, true);
+}
+int msiren_resample_volume_native_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    return resample_volume(h, dev_call(h), images_dev, n, height, width, points_dev, M, out_dev, nullptr, false, true);
+}
+int msiren_resample_volume_grad(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
+                                float* grad_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return volume_host(h, images_host, n, height, width, points_host, M, out_host, grad_host, true);
+}
+int msiren_resample_volume_grad_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
+                                    float* grad_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    return resample_volume(h, dev_call(h), images_dev, n, height, width, points_dev, M, out_dev, grad_dev, true);
+}
 
 int msiren_resample_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host) {
     if (!h) return fail(MSIREN_E_INVALID, "null handle");

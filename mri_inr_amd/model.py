@@ -811,6 +811,55 @@ class ModulatedSiren:
         analytic gradients of the covering tiles, as ``reconstruct_with_gradient`` defines it (msiren_resample_slices_grad)."""
         return self._resample(images, points, True)
 
+    def _resample_volume(self, images, points, grad, exact=True):
+        self._ensure_committed()
+        a = images.detach().cpu().numpy() if _is_torch(images) else np.asarray(images)
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.ndim != 3:
+            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
+        p = np.ascontiguousarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float32)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError(f"expected points of shape (M, 3), got {p.shape}")
+        n, Hh, Ww = a.shape
+        M = p.shape[0]
+        outs = [np.full(shape, np.nan, dtype=np.float32) for shape in (((M,), (3, M)) if grad else ((M,),))]  # (n = 0: no Z is valid, no call's work)
+        fn = self._lib.msiren_resample_volume_grad if grad else self._lib.msiren_resample_volume if exact else self._lib.msiren_resample_volume_native
+        _lib.check(fn(self._h, a.ctypes.data, n, Hh, Ww, p.ctypes.data, M, *[o.ctypes.data for o in outs]))
+        if _is_torch(images):
+            import torch
+
+            outs = [torch.from_numpy(o) for o in outs]
+        return tuple(outs) if grad else outs[0]
+
+    def resample_volume(self, images, points, *, exact=True):
+        """images (n, Hh, Ww), points (M, 3) -> (M,): the stack read as a volume at ``points[m] = (Z, Y, X)`` -- (Y, X) as in ``resample``,
+        Z in slice units (integer Z: slice Z), valid for 0 <= Z <= n - 1.  ``resample`` of the two slices either side of Z, blended
+        linearly in fp32; at an integer Z the bits of ``resample(images[Z], ...)`` (build-defined, DESIGN.md section 5.9;
+        msiren_resample_volume).  Two trunk evaluations per point and covering tile, whatever n is.  The exact-fp32 trunk;
+        ``exact=False``: the model's own trunk arithmetic (msiren_resample_volume_native).  NaN for an invalid Z, a non-finite (Y, X) or
+        a point no tile covers."""
+        return self._resample_volume(images, points, False, exact)
+
+    def resample_volume_with_gradient(self, images, points):
+        """As resample_volume -> (values (M,), grad (3, M)); n >= 2.  grad[0] per slice of Z: the fp32 difference of the two slices of
+        the segment that contains Z (at an interior integer the segment to its right); grad[1], grad[2] per reconstruction pixel along
+        rows and columns, ``resample_with_gradient``'s planes blended like the value (msiren_resample_volume_grad)."""
+        return self._resample_volume(images, points, True)
+
+    def resample_each(self, images, points, *, exact=True):
+        """images (n, Hh, Ww), points (n, M, 2) -> (n, M): every slice at its OWN point set in one call -- the volume call at integer Z,
+        so out[s] is the bits of ``resample(images[s], points[s], exact=exact)``."""
+        p = np.asarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float32)
+        n = len(images)
+        if p.ndim != 3 or p.shape[0] != n or p.shape[2] != 2:
+            raise ValueError(f"expected points of shape ({n}, M, 2), got {p.shape}")
+        M = p.shape[1]
+        zyx = np.empty((n, M, 3), np.float32)
+        zyx[:, :, 0] = np.arange(n, dtype=np.float32)[:, None]
+        zyx[:, :, 1:] = p
+        out = self._resample_volume(images, zyx.reshape(n * M, 3), False, exact)
+        return out.reshape(n, M)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
