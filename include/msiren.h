@@ -34,6 +34,8 @@ extern "C" {
 #endif
 
 /* 9: msiren_resample_volume* (a stack of slices read as a volume at points (Z, Y, X), value, native value and gradient forms) added.
+ * Under the same number, as pure additions (no existing symbol or struct changed): msiren_align_slices(_dev) (slices scored under affine maps
+ * against targets: cost, gradient, JtJ).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -401,6 +403,41 @@ MSIREN_API int msiren_resample_volume_grad(msiren_handle h, const float* images_
                                            const float* points_host, int64_t M, float* out_host /* (M) or NULL */, float* grad_host /* (3, M) */);
 MSIREN_API int msiren_resample_volume_grad_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
                                                const float* points_dev, int64_t M, float* out_dev /* (M) or NULL */, float* grad_dev /* (3, M) */);
+
+/* Build-defined: the n slices of a call scored against n targets under one 2 x 3 affine map each -- per slice the
+ * sum of squared differences, its gradient over the six map parameters and the Gauss-Newton matrix JtJ, all summed on the device.
+ *     images (n, height, width) float32;  targets (n, th, tw) float32;  maps (n, 6) float32 = (a00, a01, t0, a10, a11, t1)
+ * Target pixel (i, j) of slice s, 0 <= i < th, 0 <= j < tw, is read at
+ *     Y = ((a00 i) + (a01 j)) + t0        X = ((a10 i) + (a11 j)) + t1
+ * in fp32, i and j converted exactly, every operation rounded on its own (NO fused multiply-add: float32 arithmetic in numpy gives the same
+ * bits).  (Y, X) are reconstruction pixel coordinates exactly as in msiren_resample_slices.  R, gY, gX are THE BITS of
+ * msiren_resample_slices_grad of slice s at that point (value, plane 0, plane 1): the same cover rule, fp64-then-rounded local coordinate
+ * and weight, fp32 num / den over the covering tiles in (v, h) order, a black tile 0 with its weight; the derivative of the fold weights is
+ * not included.  The trunk is always the exact-fp32 jet ragged trunk, on handles of every precision; the model limits are the gradient
+ * calls' (dim_hidden <= 256, no residual: MSIREN_E_INVALID otherwise, nothing launched).
+ * A pixel is VALID iff targets[s, i, j], R, gY and gX are all finite: a point under black tiles only is valid (R = 0); an uncovered or
+ * non-finite point and a NaN target (a cheap mask) are not.  An invalid pixel contributes to nothing and touches nothing else.  Per valid
+ * pixel, in fp64 from the fp32 numbers, no fused multiply-add:
+ *     r = (double)R - (double)T        J = (gY i, gY j, gY, gX i, gX j, gX)       (parameter order a00, a01, t0, a10, a11, t1)
+ *     count += 1;  cost += r r;  dcost[a] += (2 r) J[a];  jtj[a, b] += J[a] J[b]  for a <= b
+ * sums (n, 29) float64 = [count, cost, dcost[0..5], jtj: the upper triangle packed row-major (21)].
+ * warped (n, th, tw) = R and wgrad (2, n, th, tw) = gY, gX are optional (NULL: not written); at invalid pixels they carry what
+ * msiren_resample_slices_grad gives (NaN where no tile covers the point).
+ * Every sum has one order: pixel p = i tw + j; chunks of 1024 consecutive pixels of a slice; inside a chunk thread t of 256 adds
+ * p = lo + t, lo + t + 256, ... in that order; the 256 totals are combined by a butterfly inside each wave of 64 (xor 32, 16, .. 1), then the
+ * four waves in order; a slice's chunks in index order.  So sums are the same bits run to run, a slice alone gives its row of any batch, and
+ * passing or omitting warped / wgrad changes no bit.
+ * The pipeline, on the call's stream: msiren_resample_slices' prologue -> the pixels binned by (slice, tile) -> the jet ragged trunk over
+ * those n nV nH bins, at most T = n th tw K entries (K = ceil(S / I)^2) -> per chunk blend and partial sums -> per slice the total.  20 T and
+ * 16 n nV nH must stay below 2^30 (MSIREN_E_INVALID beyond, naming the product); ceil(S / I) <= 4.  n = 0 or th tw = 0 does nothing.  The
+ * host-pointer form is a synchronous one-chunk call; the _dev form enqueues on the stream rotation.  Under msiren_profile_enable:
+ * "align_bin_kernels", the jet ragged trunk under its name, "align_reduce_kernels". */
+MSIREN_API int msiren_align_slices(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                   const float* targets_host, int32_t th, int32_t tw, const float* maps_host /* (n, 6) */,
+                                   double* sums_host /* (n, 29) */, float* warped_host /* or NULL */, float* wgrad_host /* or NULL */);
+MSIREN_API int msiren_align_slices_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                       const float* targets_dev, int32_t th, int32_t tw, const float* maps_dev /* (n, 6) */,
+                                       double* sums_dev /* (n, 29) */, float* warped_dev /* or NULL */, float* wgrad_dev /* or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

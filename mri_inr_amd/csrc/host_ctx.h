@@ -15,7 +15,8 @@
 //     resample.hip         one coordinate set per patch: msiren_sample_ragged_* (kernels: siren_trunk_f32_ragged.hip.h; the *_native
 //                          forms: siren_trunk_f16x3n_ragged.hip.h), and the
 //                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h) and
-//                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h)
+//                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h), msiren_align_slices* (slices scored
+//                          under affine maps against targets; align.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -249,6 +250,12 @@ int resample_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64
 int resample_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad);  // 0, or MSIREN_E_INVALID, naming what is too large
 int resample_volume(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
                     float* grad_dev, bool grad, bool native = false);  // native (values only): launch_trunk_ragged_native
+// n slices scored under one 2 x 3 affine map each against targets (th, tw) (align.hip.h): sums_dev (n, 29) doubles; warped_dev (n, th, tw) and
+// wgrad_dev (2, n, th, tw) may be null
+constexpr int kAlignSums = 29;  // doubles per slice: count, cost, dcost[6], jtj[21] (align.hip.h: ALIGN_SUMS)
+int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw);  // 0, or MSIREN_E_INVALID: the model, or naming what is too large
+int align_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev);
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 

@@ -20,6 +20,7 @@
 #include "tiling.hip.h"
 #include "resample.hip.h"
 #include "resample_volume.hip.h"
+#include "align.hip.h"
 #include "launch_dispatch.h"
 
 namespace msiren {  // the trunk / prologue kernels are compiled in their own translation units (k_*.hip)
@@ -1120,6 +1121,87 @@ int resample_volume(msiren_handle h, const Call& c, const float* images_dev, int
                        out_dev, grad ? grad_dev : nullptr, (int)M, K, (int)NPt, (int)T, grad ? 3 : 1, grad ? 1 : 0);
     HIPCHK(hipGetLastError());
     return profile_end(h, c.stream, e1, M, "resample_volume_blend_kernel");
+}
+
+// Slices scored under one affine map each against targets (kernels: align.hip.h): the slice prologue, then on the same
+// stream the pixels of every target lattice, placed by their slice's map in the kernel, binned by (slice, tile) -> the exact-fp32 jet ragged
+// trunk over those n nV nH bins, one replica, on the plan's rows -> per (slice, chunk) the blend of the three planes and the 29 fp64 sums ->
+// per slice the chunks in index order.  sums_dev (n, 29) doubles; warped_dev (n, th, tw) and wgrad_dev (2, n, th, tw) may be null.
+static_assert(kAlignSums == msiren::ALIGN_SUMS, "host and kernels disagree about a slice's record");
+int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
+    int rc;
+    if ((rc = jet_supported(h))) return rc;
+    if (n < 0 || th < 0 || tw < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, th=%d, tw=%d)", (long long)n, th, tw);
+    if ((rc = check_tile_size(h, false))) return rc;
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    if (KA > msiren::RESAMPLE_MAX_KA)
+        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
+    int32_t nV, nH;
+    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
+    // every buffer of the call below 2^31 bytes, every index in 32 bits.  Over the T = n th tw K entries the stream's bin scratch holds 20 T
+    // bytes (slot, tile, weight, 8 bytes of coordinates) and 232 bytes per chunk of 1024 pixels, 16 n nV nH over the bins: each half below
+    // 2^30.  The trunk's three planes are 12 T bytes.
+    const int64_t M = (int64_t)th * tw;
+    if (n > 0x00ffffffLL || M > 0x0fffffffLL || n * M > 0x0fffffffLL || 20 * n * M * K + 232 * n * ((M + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK) > 0x3fffffffLL)
+        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices x %d x %d target pixels x %d covering tiles (20 n th tw K must stay below 2^30)",
+                    (long long)n, th, tw, K);
+    if (16 * n * nV * nH > 0x3fffffffLL)
+        return fail(MSIREN_E_INVALID, "too many slices for one call: %lld slices x %d x %d tiles (16 n nV nH must stay below 2^30)", (long long)n, nV, nH);
+    return 0;
+}
+
+int align_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = align_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    const int64_t M = (int64_t)th * tw;
+    if (n > 0 && M > 0 && (!images_dev || !targets_dev || !maps_dev || !sums_dev)) return fail(MSIREN_E_INVALID, "null argument");
+    if (n == 0 || M == 0) return 0;
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_dev % 4 || (uintptr_t)sums_dev % 8) return fail(MSIREN_E_INVALID, "device targets and maps must be 4-byte aligned, sums 8-byte aligned");
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    int32_t nV, nH;
+    (void)msiren_recon_shape(h, height, width, &nV, &nH);
+    const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, T = n * M * K, chunks = (M + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK;
+    if ((rc = check_reflect_padding(h, height, width))) return rc;
+    auto& sc = h->sc[c.stream];
+    // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T][partials n chunks 29 doubles, 8-byte aligned]
+    const size_t nint = (size_t)(4 * NP + 2 + 2 * T + 1) & ~(size_t)1, nflt = (size_t)(3 * T + 1) & ~(size_t)1;
+    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) ||
+        (rc = ensure(h, sc.ragged, (nint + nflt) * 4 + (size_t)n * chunks * msiren::ALIGN_SUMS * sizeof(double))) || (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * 3)))
+        return rc;
+    Call pc;
+    bool fused;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &pc, &fused))) return rc;
+    hipStream_t st = sc.s;
+    int* const ib = (int*)sc.ragged.p;
+    msiren::AlignParams ap{maps_dev, (int)n, th, tw, (int)M, nV, nH, h->S, h->I, (h->S - h->I) / 2, KA};
+    ap.counts = ib, ap.cursors = ib + NP, ap.offsets = ib + 2 * NP;
+    int* const items = ap.offsets + NP + 1;
+    ap.ent = items + NP + 1, ap.tile = ap.ent + T;
+    ap.coords = (float*)(ib + nint), ap.w = ap.coords + 2 * T;
+    double* const partials = (double*)(ap.coords + nflt);
+    const unsigned gm = (unsigned)((n * M + 255) / 256);
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+    HIPCHK(hipMemsetAsync(ib, 0, (size_t)2 * NP * sizeof(int), st));
+    hipLaunchKernelGGL(msiren::align_count_kernel, dim3(gm), dim3(256), 0, st, ap);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, ap.counts, (int)NP, ap.offsets);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::align_fill_kernel, dim3(gm), dim3(256), 0, st, ap);
+    HIPCHK(hipGetLastError());
+    if ((rc = profile_end(h, c.stream, e1, n * M, "align_bin_kernels"))) return rc;
+    float* const rec = (float*)sc.rec.p;  // [value (T)][d/d row][d/d column]
+    const int* plan = (const int*)sc.plan.p;
+    const RaggedSet r{ap.coords, ap.offsets, T, NP, 1, plan + 2 + NP, NP, items};
+    const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
+    if ((rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale)) || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    hipLaunchKernelGGL(msiren::align_partial_kernel, dim3((unsigned)(n * chunks)), dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, (const int*)sc.keep.p, targets_dev,
+                       warped_dev, wgrad_dev, partials, (int)n, (int)M, tw, K, (int)NPt, (int)T, (int)chunks);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::align_combine_kernel, dim3((unsigned)n), dim3(256), 0, st, partials, sums_dev, (int)chunks);
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, n * M, "align_reduce_kernels");
 }
 
 // msiren_weighted_fold_dev with the output side of another stride (kernel S', stride I', padding pad'): complete tiles, no black flags

@@ -111,6 +111,28 @@ int volume_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t heig
     return 0;
 }
 
+// slices scored under affine maps against targets, one synchronous one-chunk call on host pointers: images + targets + maps -> sums, [warped], [wgrad]
+int align_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
+               const float* maps_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    int rc = check(h);
+    if (rc || (rc = align_check(h, n, height, width, th, tw))) return rc;
+    const int64_t M = (int64_t)th * tw;
+    if (n == 0 || M == 0) return 0;
+    if (!images_host || !targets_host || !maps_host || !sums_host) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)n * M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)n * 6 * sizeof(float), HOST_COPY);
+    const int o_s = io.out(sums_host, (size_t)n * kAlignSums * sizeof(double), HOST_IN_PLACE);
+    const int o_w = io.out(warped_host, nt, HOST_IN_PLACE), o_g = io.out(wgrad_host, 2 * nt, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_slices(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), th, tw, io.src<float>(i_m), io.dst<double>(o_s), io.dst<float>(o_w),
+                           io.dst<float>(o_g))))
+        return rc;
+    return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -143,6 +165,18 @@ int msiren_resample_volume_grad_dev(msiren_handle h, const float* images_dev, in
     int rc = check(h);
     if (rc) return rc;
     return resample_volume(h, dev_call(h), images_dev, n, height, width, points_dev, M, out_dev, grad_dev, true);
+}
+
+int msiren_align_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
+                        const float* maps_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_host(h, images_host, n, height, width, targets_host, th, tw, maps_host, sums_host, warped_host, wgrad_host);
+}
+int msiren_align_slices_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                            const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    return align_slices(h, dev_call(h), images_dev, n, height, width, targets_dev, th, tw, maps_dev, sums_dev, warped_dev, wgrad_dev);
 }
 
 int msiren_resample_slices(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host) {

@@ -860,6 +860,34 @@ class ModulatedSiren:
         out = self._resample_volume(images, zyx.reshape(n * M, 3), False, exact)
         return out.reshape(n, M)
 
+    def align_cost(self, images, targets, maps, *, warped=False, gradient=False):
+        """images (n, Hh, Ww), targets (n, th, tw), maps (n, 6) -> ``align.AlignResult``: every slice read on its target's lattice under its
+        own affine map (``align.map_points``: pixel (i, j) at Y = a00 i + a01 j + t0, X = a10 i + a11 j + t1 in reconstruction pixels) and
+        scored against the target on the device -- ``count`` valid pixels, ``cost`` = sum (R - T)^2, ``grad`` = d cost / d map (n, 6),
+        ``jtj`` (n, 6, 6) the Gauss-Newton matrix; R and its gradient are the bits of ``resample_with_gradient`` (build-defined, DESIGN.md
+        section 5.10; msiren_align_slices).  A NaN target pixel, an uncovered or non-finite point is left out.  fp64 sums in a fixed order:
+        the same bits run to run, alone or in a batch.  ``warped`` / ``gradient``: also return R (n, th, tw) / (gY, gX) (2, n, th, tw)."""
+        from . import align
+
+        self._ensure_committed()
+        a = np.ascontiguousarray(images.detach().cpu().numpy() if _is_torch(images) else images, dtype=np.float32)
+        t = np.ascontiguousarray(targets.detach().cpu().numpy() if _is_torch(targets) else targets, dtype=np.float32)
+        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        if a.ndim != 3:
+            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
+        n, Hh, Ww = a.shape
+        if t.ndim != 3 or t.shape[0] != n:
+            raise ValueError(f"expected targets of shape ({n}, th, tw), got {t.shape}")
+        if m.shape != (n, 6):
+            raise ValueError(f"expected maps of shape ({n}, 6), got {m.shape}")
+        th, tw = t.shape[1:]
+        sums = np.zeros((n, align.SUMS), np.float64)
+        w = np.full((n, th, tw), np.nan, np.float32) if warped else None
+        g = np.full((2, n, th, tw), np.nan, np.float32) if gradient else None
+        _lib.check(self._lib.msiren_align_slices(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, m.ctypes.data, sums.ctypes.data,
+                                                 w.ctypes.data if warped else None, g.ctypes.data if gradient else None))
+        return align.unpack(sums, w, g)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
