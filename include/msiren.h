@@ -35,7 +35,7 @@ extern "C" {
 
 /* 9: msiren_resample_volume* (a stack of slices read as a volume at points (Z, Y, X), value, native value and gradient forms) added.
  * Under the same number, as pure additions (no existing symbol or struct changed): msiren_align_slices(_dev) (slices scored under affine maps
- * against targets: cost, gradient, JtJ).
+ * against targets: cost, gradient, JtJ); msiren_align_solve(_dev) and msiren_align_solve_opts (the damped Gauss-Newton loop around it, on the device).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -438,6 +438,53 @@ MSIREN_API int msiren_align_slices(msiren_handle h, const float* images_host, in
 MSIREN_API int msiren_align_slices_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
                                        const float* targets_dev, int32_t th, int32_t tw, const float* maps_dev /* (n, 6) */,
                                        double* sums_dev /* (n, 29) */, float* warped_dev /* or NULL */, float* wgrad_dev /* or NULL */);
+
+/* Build-defined: slices aligned to their targets on the device -- msiren_align_slices' prologue once, then
+ * `iterations` x (its evaluation at the trial maps -> one step kernel), all on the call's stream, no host synchronisation in between.
+ * Levenberg-Marquardt with per-slice accept / reject over the six affine parameters (mode 0) or over rotation and in-plane shift about
+ * (centre_y, centre_x) (mode 1).  After evaluation k = 0 .. iterations - 1 with sums (count, cost, g[6], H[6][6]) at the trial map:
+ *     mean = cost / count if count >= 6 else +inf
+ *     k == 0:            accept (best := trial, sums_best := sums, mean_best = mean_first = mean); lam unchanged
+ *     mean < mean_best:  accept; accepted += 1; lam = max(lam down, lam_min)
+ *     otherwise:         reject (a NaN mean included); lam = min(lam up, lam_max)
+ *     then propose from best (also behind the last evaluation), with g, H of sums_best:
+ *     affine  A = H, A[a][a] = H[a][a] + lam H[a][a];  d = ldl_solve(A, -g / 2);  trial[a] = (float)((double)best[a] + d[a])
+ *     rigid   state (c, s, uY, uX):  B (6 x 3) = d map / d (angle, uY, uX),  g3 = B^T g,  H3 = B^T (H B),  A = H3 damped as above,
+ *             d = ldl_solve(A, -g3 / 2);  u = d[0] / 2, cd = (1 - u u) / (1 + u u), sd = 2 u / (1 + u u) (Cayley: an exact rotation);
+ *             c' = c cd - s sd, s' = s cd + c sd, uY' = uY + d[1], uX' = uX + d[2];
+ *             trial = (float)(c', -s', cy - (c' cy - s' cx) + uY', s', c', cx - (s' cy + c' cx) + uX')
+ * ldl_solve: A = L D L^T without pivoting; a pivot that is not positive and finite gives a zero step (flag SINGULAR).  fp64 + - * / one
+ * at a time, no fused multiply-add, every sum in one order: mri_inr_amd/align.py: lm_step restates it in Python floats and gives the
+ * same bits, so the call equals the same loop on the host around msiren_align_slices bit for bit (DESIGN.md section 5.11 has every order).
+ * Affine mode reads maps_in (n, 6); rigid mode reads rigid_in (n, 4) = (cos, sin, uY, uX) and forms the first map from it.
+ * maps_out (n, 6): the best map.  rigid_out (n, 4) or NULL: the best rigid state (zeros in affine mode).
+ * report (n, 6) float64: accepted, mean_first, mean_best, count at the best map, lam, flags (bit 0 SINGULAR: the last proposal was zero;
+ * bit 1 NO_OVERLAP: mean_first is +inf).  trace (iterations, n, 8) float64 or NULL: per evaluation the trial map as six doubles, cost, count.
+ * A slice with fewer than six valid pixels at every evaluation, and a black slice (H = 0: SINGULAR), keep their input map.  Every slice's
+ * trajectory depends on that slice only: the same bits alone or in any batch, with or without trace.
+ * MSIREN_E_INVALID with a message, before any launch: what msiren_align_slices refuses; struct_size != sizeof(msiren_align_solve_opts);
+ * mode not 0 or 1; iterations outside 1 .. 256; anything outside 0 < lam_min <= damping <= lam_max < inf, 0 < down <= 1, 1 <= up < inf; a
+ * non-finite centre in rigid mode; a missing input of the mode, a null maps_out or report; device pointers not aligned to 4 (floats) / 8
+ * (doubles) bytes.  n = 0 or th tw = 0 does nothing.  The host-pointer form is one synchronous call: images and targets go up once.
+ * Under msiren_profile_enable: the prologue's entries once per call; "align_bin_kernels", the jet ragged trunk, "align_reduce_kernels" and
+ * "align_step_kernel" `iterations` times. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(msiren_align_solve_opts) */
+    int32_t mode;             /* 0 affine, 1 rigid */
+    int32_t iterations;       /* evaluations, 1 .. 256 */
+    int32_t reserved;
+    double damping, down, up, lam_min, lam_max, centre_y, centre_x;
+} msiren_align_solve_opts;
+MSIREN_API int msiren_align_solve(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                  const float* targets_host, int32_t th, int32_t tw, const msiren_align_solve_opts* opts,
+                                  const float* maps_in /* (n, 6), affine */, const double* rigid_in /* (n, 4), rigid */,
+                                  float* maps_out /* (n, 6) */, double* rigid_out /* (n, 4) or NULL */, double* report /* (n, 6) */,
+                                  double* trace /* (iterations, n, 8) or NULL */);
+MSIREN_API int msiren_align_solve_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                      const float* targets_dev, int32_t th, int32_t tw, const msiren_align_solve_opts* opts,
+                                      const float* maps_in_dev /* (n, 6), affine */, const double* rigid_in_dev /* (n, 4), rigid */,
+                                      float* maps_out_dev /* (n, 6) */, double* rigid_out_dev /* (n, 4) or NULL */,
+                                      double* report_dev /* (n, 6) */, double* trace_dev /* (iterations, n, 8) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

@@ -8,7 +8,7 @@ Public surface mirrors the reference's: ``ModulatedSiren`` (src/networks/modulat
 from .configuration import load_configuration, model_kwargs  # noqa: F401
 from .model import ModulatedSiren  # noqa: F401
 from .volume import plane_points  # noqa: F401
-from . import align  # noqa: F401
+from . import align  # noqa: F401  (map helpers, and the step rule of ModulatedSiren.align_solve: lm_step, solve_on_host)
 
-__all__ = ["ModulatedSiren", "load_configuration", "model_kwargs", "plane_points"]
+__all__ = ["ModulatedSiren", "load_configuration", "model_kwargs", "plane_points", "align"]
 __version__ = "0.1.0"

@@ -1,5 +1,6 @@
-"""Helpers for ``ModulatedSiren.align_cost``: the affine maps slices are read under, the call's packed sums, and a
-Gauss-Newton step on them.  Pure numpy.
+"""Helpers for ``ModulatedSiren.align_cost`` and ``align_solve`` (section 5.11): the affine maps slices are read
+under, the call's packed sums, a Gauss-Newton step on them, and the Levenberg-Marquardt rule of msiren_align_solve restated operation by
+operation (``lm_step``, ``solve_on_host``).  Pure numpy; the step rule in plain Python floats.
 
 A map is six float32 numbers (a00, a01, t0, a10, a11, t1): pixel (i, j) of the target lattice is read at
     Y = ((a00 i) + (a01 j)) + t0        X = ((a10 i) + (a11 j)) + t1
@@ -34,9 +35,10 @@ def map_points(maps_row, shape):
     return np.stack([Y, X], axis=-1).reshape(th * tw, 2)
 
 
-def rigid_maps(angle, shift, centre):
+def rigid_maps(angle, shift, centre, dtype=np.float32):
     """Rotations by ``angle`` (n,) radians about ``centre`` (2,) = (Y, X) followed by ``shift`` (n, 2) -> maps (n, 6) float32:
-    p' = R (p - centre) + centre + shift, R = [[cos, -sin], [sin, cos]] on (row, column).  Formed in fp64 and rounded once."""
+    p' = R (p - centre) + centre + shift, R = [[cos, -sin], [sin, cos]] on (row, column).  Formed in fp64 and rounded once
+    (``dtype=np.float64``: not rounded)."""
     angle = np.atleast_1d(np.asarray(angle, dtype=np.float64))
     shift = np.broadcast_to(np.asarray(shift, dtype=np.float64), (len(angle), 2))
     cy, cx = np.asarray(centre, dtype=np.float64)
@@ -44,7 +46,7 @@ def rigid_maps(angle, shift, centre):
     maps = np.empty((len(angle), 6), np.float64)
     maps[:, 0], maps[:, 1], maps[:, 2] = c, -s, cy - (c * cy - s * cx) + shift[:, 0]
     maps[:, 3], maps[:, 4], maps[:, 5] = s, c, cx - (s * cy + c * cx) + shift[:, 1]
-    return maps.astype(np.float32)
+    return maps.astype(dtype)
 
 
 def unpack(sums, warped=None, wgrad=None):
@@ -73,3 +75,192 @@ def gauss_newton_step(result, damping=0.0):
         except np.linalg.LinAlgError:
             pass
     return step
+
+
+# ---- msiren_align_solve's step rule, one slice, in Python floats: fp64 + - * / one at a time, no fused operation, every
+# sum in the order written -- what align_step_kernel computes, bit for bit.  No numpy arithmetic below: its summation order is not defined.
+AFFINE, RIGID = 0, 1
+SINGULAR, NO_OVERLAP = 1, 2
+INF = float("inf")
+
+SolveOptions = collections.namedtuple("SolveOptions", "mode iterations damping down up lam_min lam_max centre", defaults=(AFFINE, 12, 1e-3, 0.1, 10.0, 1e-9, 1e9, (0.0, 0.0)))
+SolveResult = collections.namedtuple("SolveResult", "maps angle shift accepted mean_first mean_best count damping flags trace")
+SolveResult.__doc__ = """maps (n, 6) float32 the best map of every slice; angle (n,) = atan2(s, c) and shift (n, 2) of the best rigid state (None in
+affine mode); accepted (n,) int64 steps accepted after the first evaluation; mean_first / mean_best (n,) cost / count at the input and at the best
+map (+inf: fewer than six valid pixels); count (n,) int64 valid pixels at the best map; damping (n,) the final lambda; flags (n,) int64
+(SINGULAR: the last proposal was zero, NO_OVERLAP: mean_first is +inf); trace (iterations, n, 8) or None: per evaluation the trial map, cost, count."""
+
+
+def _f32(x):
+    """a Python float rounded to float32 (nearest even; beyond the range: inf), back as a Python float"""
+    with np.errstate(over="ignore", invalid="ignore"):
+        return float(np.float32(x))
+
+
+def _finite(x):
+    return x - x == 0.0  # (false for inf and NaN)
+
+
+def ldl_solve(A, b, m):
+    """A (m x m, its lower triangle and diagonal are read), b (m) -> (x, ok): A = L D L^T without pivoting, then the three substitutions.  A pivot
+    that is not positive and finite: (zeros, False)."""
+    L = [[0.0] * m for _ in range(m)]
+    D = [0.0] * m
+    for j in range(m):
+        dj = A[j][j]
+        for k in range(j):
+            dj = dj - (L[j][k] * L[j][k]) * D[k]
+        if not (dj > 0.0) or not _finite(dj):
+            return [0.0] * m, False
+        D[j] = dj
+        for i in range(j + 1, m):
+            v = A[i][j]
+            for k in range(j):
+                v = v - (L[i][k] * L[j][k]) * D[k]
+            L[i][j] = v / dj
+    y = [float(x) for x in b]
+    for i in range(m):
+        for k in range(i):
+            y[i] = y[i] - L[i][k] * y[k]
+    for i in range(m):
+        y[i] = y[i] / D[i]
+    for i in range(m - 1, -1, -1):
+        for k in range(i + 1, m):
+            y[i] = y[i] - L[k][i] * y[k]
+    return y, True
+
+
+def rigid_jacobian(c, s, cy, cx):
+    """B (6 x 3): d map / d (angle, uY, uX) at the rigid state (c, s, ., .) about (cy, cx)"""
+    B = [[0.0] * 3 for _ in range(6)]
+    B[0][0], B[1][0], B[2][0] = -s, -c, s * cy + c * cx
+    B[3][0], B[4][0], B[5][0] = c, -s, -(c * cy - s * cx)
+    B[2][1] = 1.0
+    B[5][2] = 1.0
+    return B
+
+
+def cayley(u):
+    """(cos, sin) of the rotation by 2 atan(u): an exact rotation up to rounding, no trigonometry"""
+    uu = u * u
+    return (1.0 - uu) / (1.0 + uu), (2.0 * u) / (1.0 + uu)
+
+
+def rigid_map(c, s, uY, uX, cy, cx):
+    """rigid_maps' formula for one state, in Python floats -> the six float32 entries (as floats)"""
+    return [_f32(c), _f32(-s), _f32(cy - (c * cy - s * cx) + uY), _f32(s), _f32(c), _f32(cx - (s * cy + c * cx) + uX)]
+
+
+def lm_decide(k, mean, mean_best, lam, o):
+    """-> (accept, counted, lam): the first evaluation is accepted and changes nothing else; a lower mean is accepted and lowers lam; everything
+    else (a NaN included) is rejected and raises it"""
+    if k == 0:
+        return True, False, lam
+    if mean < mean_best:
+        x = lam * o.down
+        return True, True, (x if x > o.lam_min else o.lam_min)
+    x = lam * o.up
+    return False, False, (x if x < o.lam_max else o.lam_max)
+
+
+def lm_init(o, map_in=None, rigid_in=None):
+    """the state of one slice before its first evaluation: a dict (trial, best, rigid_trial, rigid_best, sums, mean_best, mean_first, lam,
+    accepted, flags).  Affine: map_in (6); rigid: rigid_in (c, s, uY, uX), the trial map formed from it."""
+    st = dict(sums=[0.0] * SUMS, mean_best=INF, mean_first=INF, lam=float(o.damping), accepted=0, flags=0)
+    if o.mode == RIGID:
+        r = [float(x) for x in rigid_in]
+        st["rigid_trial"], st["rigid_best"] = r, list(r)
+        st["trial"] = rigid_map(r[0], r[1], r[2], r[3], float(o.centre[0]), float(o.centre[1]))
+    else:
+        st["rigid_trial"] = st["rigid_best"] = [0.0] * 4
+        st["trial"] = [_f32(x) for x in map_in]
+    st["best"] = list(st["trial"])
+    return st
+
+
+def lm_step(st, sums, k, o):
+    """One slice after evaluation k: ``sums`` (29) are msiren_align_slices' at st["trial"].  Accept or reject, then propose the next trial from
+    the best map.  ``st`` is updated in place and returned."""
+    sums = [float(x) for x in sums]
+    mean = sums[1] / sums[0] if sums[0] >= 6.0 else INF
+    accept, counted, st["lam"] = lm_decide(k, mean, st["mean_best"], st["lam"], o)
+    if accept:
+        st["best"], st["rigid_best"], st["sums"], st["mean_best"] = list(st["trial"]), list(st["rigid_trial"]), sums, mean
+        if k == 0:
+            st["mean_first"] = mean
+        if counted:
+            st["accepted"] += 1
+    lam, bs = st["lam"], st["sums"]
+    g = bs[2:8]
+    H = [[0.0] * 6 for _ in range(6)]
+    q = 8
+    for a in range(6):
+        for b in range(a, 6):
+            H[a][b] = H[b][a] = bs[q]
+            q += 1
+    if o.mode == AFFINE:
+        A = [row[:] for row in H]
+        for a in range(6):
+            A[a][a] = H[a][a] + lam * H[a][a]
+        d, ok = ldl_solve(A, [-0.5 * g[a] for a in range(6)], 6)
+        st["trial"] = [_f32(st["best"][a] + d[a]) for a in range(6)]
+    else:
+        c, s, uY, uX = st["rigid_best"]
+        cy, cx = float(o.centre[0]), float(o.centre[1])
+        B = rigid_jacobian(c, s, cy, cx)
+        g3 = [0.0] * 3
+        for p in range(3):
+            t = 0.0
+            for a in range(6):
+                t = t + B[a][p] * g[a]
+            g3[p] = t
+        T = [[0.0] * 3 for _ in range(6)]
+        for a in range(6):
+            for p in range(3):
+                t = 0.0
+                for b in range(6):
+                    t = t + H[a][b] * B[b][p]
+                T[a][p] = t
+        A = [[0.0] * 3 for _ in range(3)]
+        for p in range(3):
+            for r in range(3):
+                t = 0.0
+                for a in range(6):
+                    t = t + B[a][p] * T[a][r]
+                A[p][r] = t
+        for p in range(3):
+            A[p][p] = A[p][p] + lam * A[p][p]
+        d, ok = ldl_solve(A, [-0.5 * g3[p] for p in range(3)], 3)
+        cd, sd = cayley(d[0] / 2.0)
+        c2, s2 = c * cd - s * sd, s * cd + c * sd
+        st["rigid_trial"] = [c2, s2, uY + d[1], uX + d[2]]
+        st["trial"] = rigid_map(c2, s2, uY + d[1], uX + d[2], cy, cx)
+    st["flags"] = (0 if ok else SINGULAR) | (NO_OVERLAP if st["mean_first"] == INF else 0)
+    return st
+
+
+def solve_on_host(cost_fn, n, *, maps=None, rigid=None, options=SolveOptions(), trace=False):
+    """msiren_align_solve's loop around any ``cost_fn(maps (n, 6) float32) -> sums (n, 29)``: ``options.iterations`` evaluations, ``lm_step``
+    per slice after each.  Affine: ``maps`` (n, 6); rigid: ``rigid`` (n, 4) = (c, s, uY, uX).  -> (SolveResult, rigid (n, 4) float64 best states)"""
+    o = options
+    st = [lm_init(o, None if maps is None else maps[s], None if rigid is None else rigid[s]) for s in range(n)]
+    tr = np.zeros((o.iterations, n, 8), np.float64) if trace else None
+    for k in range(o.iterations):
+        trial = np.array([x["trial"] for x in st], np.float32).reshape(n, 6)
+        sums = np.asarray(cost_fn(trial), np.float64).reshape(n, SUMS)
+        if trace:
+            tr[k, :, :6], tr[k, :, 6], tr[k, :, 7] = trial, sums[:, 1], sums[:, 0]
+        for s in range(n):
+            lm_step(st[s], sums[s], k, o)
+    rb = np.array([x["rigid_best"] for x in st], np.float64).reshape(n, 4)
+    return solve_result(np.array([x["best"] for x in st], np.float32).reshape(n, 6), rb if o.mode == RIGID else None,
+                        np.array([[x["accepted"], x["mean_first"], x["mean_best"], x["sums"][0], x["lam"], x["flags"]] for x in st], np.float64).reshape(n, 6), tr), rb
+
+
+def solve_result(maps, rigid, report, trace):
+    """what msiren_align_solve writes -> SolveResult"""
+    angle = shift = None
+    if rigid is not None:
+        angle, shift = np.arctan2(rigid[:, 1], rigid[:, 0]), rigid[:, 2:4].copy()
+    return SolveResult(maps, angle, shift, report[:, 0].astype(np.int64), report[:, 1].copy(), report[:, 2].copy(), report[:, 3].astype(np.int64),
+                       report[:, 4].copy(), report[:, 5].astype(np.int64), trace)

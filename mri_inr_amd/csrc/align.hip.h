@@ -176,4 +176,262 @@ __global__ __launch_bounds__(256) void align_combine_kernel(const double* __rest
     }
 }
 
+// ---- msiren_align_solve* (DESIGN.md section 5.11): the damped Gauss-Newton loop around the pipeline above -----------------------------------
+// One thread per slice between two evaluations.  State per slice, in the stream's scratch behind the partials:
+//     trial, best (6 fp32 each)   the map the next evaluation reads / the best map so far
+//     rigid_trial, rigid_best     (c, s, uY, uX) fp64 each (rigid mode)
+//     sums_best (29 fp64)         the sums at the best map;  scal = (mean_best, mean_first, lam);  cnt = (accepted, flags)
+// The rule is DESIGN.md section 5.11's, restated by mri_inr_amd/align.py: lm_step -- fp64 + - * / one at a time (contraction off), every sum
+// in the order written there, so the two give the same bits.  Every loop below has constant bounds and is unrolled: the matrices live in
+// registers, nothing is indexed at run time.  Plain stores, no atomics: a slice's trajectory depends on that slice only.
+constexpr int ALIGN_SINGULAR = 1, ALIGN_NO_OVERLAP = 2;
+
+struct AlignSolveParams {
+    const double* sums;                  // (n, 29) of the evaluation at `trial`
+    float *trial, *best;                 // (n, 6)
+    double *rigid_trial, *rigid_best;    // (n, 4)
+    double* sums_best;                   // (n, 29)
+    double* scal;                        // (n, 3)
+    int* cnt;                            // (n, 2)
+    double* trace;                       // (iterations, n, 8) or null
+    float* maps_out;                     // (n, 6)      written behind the last evaluation
+    double* rigid_out;                   // (n, 4) or null
+    double* report;                      // (n, 6)
+    int n, mode, k, last;                // mode 0 affine, 1 rigid; k: the evaluation just done; last: k == iterations - 1
+    double down, up, lam_min, lam_max, cy, cx;
+};
+
+// rigid_maps' formula (mri_inr_amd/align.py) for one state: fp64, rounded once per entry
+__device__ __forceinline__ void align_rigid_map(double c, double s, double uY, double uX, double cy, double cx, float* m) {
+#pragma clang fp contract(off)
+    const double ccy = c * cy, scx = s * cx, scy = s * cy, ccx = c * cx;
+    const double ry = ccy - scx, rx = scy + ccx;
+    const double ty = (cy - ry) + uY, tx = (cx - rx) + uX;
+    m[0] = (float)c, m[1] = (float)(-s), m[2] = (float)ty, m[3] = (float)s, m[4] = (float)c, m[5] = (float)tx;
+}
+
+// A = L D L^T without pivoting (the lower triangle and the diagonal of A are read), then the three substitutions.  A pivot that is not
+// positive and finite: x = 0, false.
+template <int M>
+__device__ __forceinline__ bool align_ldl_solve(const double (&A)[M][M], const double (&b)[M], double (&x)[M]) {
+#pragma clang fp contract(off)
+    double L[M][M], D[M], y[M];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+        double dj = A[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) {
+            const double ll = L[j][k] * L[j][k];
+            dj = dj - ll * D[k];
+        }
+        ok = ok && dj > 0.0 && dj < __builtin_inf();  // (false for a NaN)
+        D[j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < M; ++i) {
+            double v = A[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) {
+                const double ll = L[i][k] * L[j][k];
+                v = v - ll * D[k];
+            }
+            L[i][j] = v / dj;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+        y[i] = b[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) y[i] = y[i] - L[i][k] * y[k];
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) y[i] = y[i] / D[i];
+#pragma unroll
+    for (int i = M - 1; i >= 0; --i) {
+#pragma unroll
+        for (int k = i + 1; k < M; ++k) y[i] = y[i] - L[k][i] * y[k];
+    }
+#pragma unroll
+    for (int i = 0; i < M; ++i) x[i] = ok ? y[i] : 0.0;
+    return ok;
+}
+
+// before the first evaluation: trial := best := the input (rigid: the map of the input state), lam := damping, nothing accepted
+__global__ __launch_bounds__(256) void align_solve_init_kernel(AlignSolveParams p, const float* __restrict__ maps_in, const double* __restrict__ rigid_in,
+                                                               double damping) {
+#pragma clang fp contract(off)
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= p.n) return;
+    float m[6];
+    double r[4] = {0.0, 0.0, 0.0, 0.0};
+    if (p.mode == 1) {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) r[a] = rigid_in[(size_t)s * 4 + a];
+        align_rigid_map(r[0], r[1], r[2], r[3], p.cy, p.cx, m);
+    } else {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) m[a] = maps_in[(size_t)s * 6 + a];
+    }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) p.trial[(size_t)s * 6 + a] = m[a], p.best[(size_t)s * 6 + a] = m[a];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) p.rigid_trial[(size_t)s * 4 + a] = r[a], p.rigid_best[(size_t)s * 4 + a] = r[a];
+#pragma unroll
+    for (int a = 0; a < ALIGN_SUMS; ++a) p.sums_best[(size_t)s * ALIGN_SUMS + a] = 0.0;
+    p.scal[(size_t)s * 3] = __builtin_inf(), p.scal[(size_t)s * 3 + 1] = __builtin_inf(), p.scal[(size_t)s * 3 + 2] = damping;
+    p.cnt[(size_t)s * 2] = 0, p.cnt[(size_t)s * 2 + 1] = 0;
+}
+
+// behind evaluation k: accept or reject the trial, then propose the next one from the best map.  grid: ceil(n / 256) workgroups of 256
+__global__ __launch_bounds__(256) void align_step_kernel(AlignSolveParams p) {
+#pragma clang fp contract(off)
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= p.n) return;
+    const double inf = __builtin_inf();
+    float trial[6], best[6];
+    double rt[4], rb[4], bs[ALIGN_SUMS];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) trial[a] = p.trial[(size_t)s * 6 + a], best[a] = p.best[(size_t)s * 6 + a];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) rt[a] = p.rigid_trial[(size_t)s * 4 + a], rb[a] = p.rigid_best[(size_t)s * 4 + a];
+    double mean_best = p.scal[(size_t)s * 3], mean_first = p.scal[(size_t)s * 3 + 1], lam = p.scal[(size_t)s * 3 + 2];
+    int accepted = p.cnt[(size_t)s * 2];
+    const double* ev = p.sums + (size_t)s * ALIGN_SUMS;
+    const double count = ev[0], cost = ev[1];
+    if (p.trace) {
+        double* tr = p.trace + ((size_t)p.k * p.n + s) * 8;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) tr[a] = (double)trial[a];
+        tr[6] = cost, tr[7] = count;
+    }
+    const double mean = count >= 6.0 ? cost / count : inf;
+    bool accept;
+    if (p.k == 0) {
+        accept = true;
+        mean_first = mean;
+    } else if (mean < mean_best) {  // (false for a NaN)
+        accept = true;
+        accepted += 1;
+        const double x = lam * p.down;
+        lam = x > p.lam_min ? x : p.lam_min;
+    } else {
+        accept = false;
+        const double x = lam * p.up;
+        lam = x < p.lam_max ? x : p.lam_max;
+    }
+#pragma unroll
+    for (int a = 0; a < ALIGN_SUMS; ++a) bs[a] = accept ? ev[a] : p.sums_best[(size_t)s * ALIGN_SUMS + a];
+    if (accept) {
+        mean_best = mean;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) best[a] = trial[a];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) rb[a] = rt[a];
+#pragma unroll
+        for (int a = 0; a < ALIGN_SUMS; ++a) p.sums_best[(size_t)s * ALIGN_SUMS + a] = bs[a];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) p.best[(size_t)s * 6 + a] = best[a];
+#pragma unroll
+        for (int a = 0; a < 4; ++a) p.rigid_best[(size_t)s * 4 + a] = rb[a];
+    }
+    double H[6][6];
+    {
+        int q = 8;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b, ++q) H[a][b] = bs[q], H[b][a] = bs[q];
+    }
+    bool ok;
+    if (p.mode == 0) {
+        double A[6][6], rhs[6], d[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+#pragma unroll
+            for (int b = 0; b < 6; ++b) A[a][b] = H[a][b];
+            const double lh = lam * H[a][a];
+            A[a][a] = H[a][a] + lh;
+            rhs[a] = -0.5 * bs[2 + a];
+        }
+        ok = align_ldl_solve<6>(A, rhs, d);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) trial[a] = (float)((double)best[a] + d[a]);
+    } else {
+        const double c = rb[0], sn = rb[1], uY = rb[2], uX = rb[3], cy = p.cy, cx = p.cx;
+        double B[6][3];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) B[a][0] = 0.0, B[a][1] = 0.0, B[a][2] = 0.0;
+        {
+            const double scy = sn * cy, ccx = c * cx, ccy = c * cy, scx = sn * cx;
+            B[0][0] = -sn, B[1][0] = -c, B[2][0] = scy + ccx;
+            B[3][0] = c, B[4][0] = -sn, B[5][0] = -(ccy - scx);
+            B[2][1] = 1.0, B[5][2] = 1.0;
+        }
+        double g3[3], T[6][3], A[3][3], rhs[3], d[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            double t = 0.0;
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                const double bg = B[a][q] * bs[2 + a];
+                t = t + bg;
+            }
+            g3[q] = t;
+        }
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                double t = 0.0;
+#pragma unroll
+                for (int b = 0; b < 6; ++b) {
+                    const double hb = H[a][b] * B[b][q];
+                    t = t + hb;
+                }
+                T[a][q] = t;
+            }
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                double t = 0.0;
+#pragma unroll
+                for (int a = 0; a < 6; ++a) {
+                    const double bt = B[a][q] * T[a][r];
+                    t = t + bt;
+                }
+                A[q][r] = t;
+            }
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const double lh = lam * A[q][q];
+            A[q][q] = A[q][q] + lh;
+            rhs[q] = -0.5 * g3[q];
+        }
+        ok = align_ldl_solve<3>(A, rhs, d);
+        const double u = d[0] / 2.0, uu = u * u, den = 1.0 + uu;
+        const double cd = (1.0 - uu) / den, sd = (2.0 * u) / den;
+        const double ccd = c * cd, ssd = sn * sd, scd = sn * cd, csd = c * sd;
+        rt[0] = ccd - ssd, rt[1] = scd + csd, rt[2] = uY + d[1], rt[3] = uX + d[2];
+        align_rigid_map(rt[0], rt[1], rt[2], rt[3], cy, cx, trial);
+#pragma unroll
+        for (int a = 0; a < 4; ++a) p.rigid_trial[(size_t)s * 4 + a] = rt[a];
+    }
+    const int flags = (ok ? 0 : ALIGN_SINGULAR) | (mean_first == inf ? ALIGN_NO_OVERLAP : 0);
+#pragma unroll
+    for (int a = 0; a < 6; ++a) p.trial[(size_t)s * 6 + a] = trial[a];
+    p.scal[(size_t)s * 3] = mean_best, p.scal[(size_t)s * 3 + 1] = mean_first, p.scal[(size_t)s * 3 + 2] = lam;
+    p.cnt[(size_t)s * 2] = accepted, p.cnt[(size_t)s * 2 + 1] = flags;
+    if (p.last) {
+#pragma unroll
+        for (int a = 0; a < 6; ++a) p.maps_out[(size_t)s * 6 + a] = best[a];
+        if (p.rigid_out) {
+#pragma unroll
+            for (int a = 0; a < 4; ++a) p.rigid_out[(size_t)s * 4 + a] = rb[a];
+        }
+        double* rp = p.report + (size_t)s * 6;
+        rp[0] = (double)accepted, rp[1] = mean_first, rp[2] = mean_best, rp[3] = bs[0], rp[4] = lam, rp[5] = (double)flags;
+    }
+}
+
 }  // namespace msiren

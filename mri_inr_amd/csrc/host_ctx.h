@@ -16,7 +16,7 @@
 //                          forms: siren_trunk_f16x3n_ragged.hip.h), and the
 //                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h) and
 //                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h), msiren_align_slices* (slices scored
-//                          under affine maps against targets; align.hip.h)
+//                          under affine maps against targets; align.hip.h), msiren_align_solve* (the damped Gauss-Newton loop around it)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -256,6 +256,12 @@ constexpr int kAlignSums = 29;  // doubles per slice: count, cost, dcost[6], jtj
 int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw);  // 0, or MSIREN_E_INVALID: the model, or naming what is too large
 int align_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
                  const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev);
+// msiren_align_solve* (align.hip.h): the prologue once, then opts->iterations x (evaluation at the trial maps -> align_step_kernel) on the call's
+// stream.  align_solve_check: every refusal that needs no device pointer (the host-pointer form asks it before it stages anything).
+int align_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_opts* o, const void* maps_in,
+                      const void* rigid_in, const void* maps_out, const void* report);
+int align_solve(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                const msiren_align_solve_opts* o, const float* maps_in, const double* rigid_in, float* maps_out, double* rigid_out, double* report, double* trace);
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 

@@ -1150,8 +1150,21 @@ int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t
     return 0;
 }
 
-int align_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
-                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+// What align_prepare leaves for align_evaluate: the call's geometry and the trunk's call state.  Nothing of it lives on the handle.
+struct AlignPlan {
+    int64_t n = 0, M = 0, NPt = 0, NP = 0, T = 0, chunks = 0;
+    int32_t th = 0, tw = 0, nV = 0, nH = 0;
+    int KA = 0, K = 0;
+    size_t nint = 0, nflt = 0, bytes = 0;  // words of the integer / float part of the bins, bytes of bins + partials (what follows is the caller's)
+    const float* targets = nullptr;
+    Call pc;
+};
+
+// the checks, every workspace of the call (`extra` bytes more behind the partials in the stream's scratch: msiren_align_solve's state) and the
+// slice prologue.  *todo = false: nothing to do (n = 0 or th tw = 0).  No workspace moves after this.
+static int align_prepare(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                         const void* maps_dev, const void* sums_dev, size_t extra, AlignPlan* a, bool* todo) {
+    *todo = false;
     int rc = align_check(h, n, height, width, th, tw);
     if (rc) return rc;
     const int64_t M = (int64_t)th * tw;
@@ -1166,20 +1179,29 @@ int align_slices(msiren_handle h, const Call& c, const float* images_dev, int64_
     auto& sc = h->sc[c.stream];
     // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T][partials n chunks 29 doubles, 8-byte aligned]
     const size_t nint = (size_t)(4 * NP + 2 + 2 * T + 1) & ~(size_t)1, nflt = (size_t)(3 * T + 1) & ~(size_t)1;
-    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) ||
-        (rc = ensure(h, sc.ragged, (nint + nflt) * 4 + (size_t)n * chunks * msiren::ALIGN_SUMS * sizeof(double))) || (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * 3)))
+    const size_t bytes = (nint + nflt) * 4 + (size_t)n * chunks * msiren::ALIGN_SUMS * sizeof(double);
+    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, bytes + extra)) || (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * 3)))
         return rc;
-    Call pc;
+    *a = AlignPlan{n, M, NPt, NP, T, chunks, th, tw, nV, nH, KA, K, nint, nflt, bytes, targets_dev, Call()};
     bool fused;
-    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &pc, &fused))) return rc;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &a->pc, &fused))) return rc;
+    *todo = true;
+    return 0;
+}
+
+// one evaluation behind align_prepare, on the same stream: the memset, count, scan, fill, the trunk, partial and combine
+static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc;
+    auto& sc = h->sc[c.stream];
+    const int64_t n = a.n, M = a.M, NP = a.NP, T = a.T;
     hipStream_t st = sc.s;
     int* const ib = (int*)sc.ragged.p;
-    msiren::AlignParams ap{maps_dev, (int)n, th, tw, (int)M, nV, nH, h->S, h->I, (h->S - h->I) / 2, KA};
+    msiren::AlignParams ap{maps_dev, (int)n, a.th, a.tw, (int)M, a.nV, a.nH, h->S, h->I, (h->S - h->I) / 2, a.KA};
     ap.counts = ib, ap.cursors = ib + NP, ap.offsets = ib + 2 * NP;
     int* const items = ap.offsets + NP + 1;
     ap.ent = items + NP + 1, ap.tile = ap.ent + T;
-    ap.coords = (float*)(ib + nint), ap.w = ap.coords + 2 * T;
-    double* const partials = (double*)(ap.coords + nflt);
+    ap.coords = (float*)(ib + a.nint), ap.w = ap.coords + 2 * T;
+    double* const partials = (double*)(ap.coords + a.nflt);
     const unsigned gm = (unsigned)((n * M + 255) / 256);
     hipEvent_t e1 = nullptr;
     if ((rc = profile_begin(h, c.stream, &e1))) return rc;
@@ -1195,13 +1217,82 @@ int align_slices(msiren_handle h, const Call& c, const float* images_dev, int64_
     const int* plan = (const int*)sc.plan.p;
     const RaggedSet r{ap.coords, ap.offsets, T, NP, 1, plan + 2 + NP, NP, items};
     const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
-    if ((rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale)) || (rc = profile_begin(h, c.stream, &e1))) return rc;
-    hipLaunchKernelGGL(msiren::align_partial_kernel, dim3((unsigned)(n * chunks)), dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, (const int*)sc.keep.p, targets_dev,
-                       warped_dev, wgrad_dev, partials, (int)n, (int)M, tw, K, (int)NPt, (int)T, (int)chunks);
+    if ((rc = launch_trunk_f32_jet_ragged(h, a.pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale)) || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    hipLaunchKernelGGL(msiren::align_partial_kernel, dim3((unsigned)(n * a.chunks)), dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, (const int*)sc.keep.p, a.targets,
+                       warped_dev, wgrad_dev, partials, (int)n, (int)M, a.tw, a.K, (int)a.NPt, (int)T, (int)a.chunks);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::align_combine_kernel, dim3((unsigned)n), dim3(256), 0, st, partials, sums_dev, (int)chunks);
+    hipLaunchKernelGGL(msiren::align_combine_kernel, dim3((unsigned)n), dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
     HIPCHK(hipGetLastError());
     return profile_end(h, c.stream, e1, n * M, "align_reduce_kernels");
+}
+
+int align_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    AlignPlan a;
+    bool todo;
+    const int rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_dev, sums_dev, 0, &a, &todo);
+    if (rc || !todo) return rc;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+// msiren_align_solve* (kernels: align.hip.h): align_prepare once, then `iterations` x (align_evaluate at the trial maps ->
+// align_step_kernel), all on the call's stream, no host sync in between.  State and the per-evaluation sums: the stream's scratch behind
+// the partials, ensured before the prologue.
+int align_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_opts* o, const void* maps_in,
+                      const void* rigid_in, const void* maps_out, const void* report) {
+    int rc = align_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_solve_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_solve_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_solve_opts));
+    if (o->mode != 0 && o->mode != 1) return fail(MSIREN_E_INVALID, "mode = %d (0: affine, 1: rigid)", o->mode);
+    if (o->iterations < 1 || o->iterations > 256) return fail(MSIREN_E_INVALID, "iterations = %d outside 1 .. 256", o->iterations);
+    const double inf = __builtin_inf();
+    if (!(0.0 < o->lam_min && o->lam_min <= o->damping && o->damping <= o->lam_max && o->lam_max < inf))
+        return fail(MSIREN_E_INVALID, "damping: 0 < lam_min <= damping <= lam_max < inf is required (lam_min=%g, damping=%g, lam_max=%g)", o->lam_min, o->damping, o->lam_max);
+    if (!(0.0 < o->down && o->down <= 1.0) || !(1.0 <= o->up && o->up < inf)) return fail(MSIREN_E_INVALID, "0 < down <= 1 <= up < inf is required (down=%g, up=%g)", o->down, o->up);
+    if (o->mode == 1 && !(o->centre_y - o->centre_y == 0.0 && o->centre_x - o->centre_x == 0.0)) return fail(MSIREN_E_INVALID, "rigid mode: the centre must be finite");
+    if (n > 0 && (int64_t)th * tw > 0 && (!(o->mode == 1 ? rigid_in : maps_in) || !maps_out || !report))
+        return fail(MSIREN_E_INVALID, "null argument (%s)", !maps_out ? "maps_out" : !report ? "report" : o->mode == 1 ? "rigid_in: rigid mode" : "maps_in: affine mode");
+    return 0;
+}
+
+int align_solve(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                const msiren_align_solve_opts* o, const float* maps_in, const double* rigid_in, float* maps_out, double* rigid_out, double* report, double* trace) {
+    int rc = align_solve_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, report);
+    if (rc || n == 0 || (int64_t)th * tw == 0) return rc;
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)trace % 8)
+        return fail(MSIREN_E_INVALID, "device maps must be 4-byte aligned, rigid states, report and trace 8-byte aligned");
+    // state in the stream's scratch, behind the partials: [sums n 29][sums_best n 29][rigid_trial n 4][rigid_best n 4][scal n 3][trial n 6][best n 6][cnt n 2]
+    const size_t nd = (size_t)n * (2 * msiren::ALIGN_SUMS + 4 + 4 + 3), extra = nd * sizeof(double) + (size_t)n * (6 + 6 + 2) * 4;
+    AlignPlan a;
+    bool todo;
+    if ((rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_out, report, extra, &a, &todo)) || !todo) return rc;
+    auto& sc = h->sc[c.stream];
+    double* const d0 = (double*)((char*)sc.ragged.p + a.bytes);  // (a.bytes is a multiple of 8)
+    msiren::AlignSolveParams sp{};
+    double* const sums = d0;
+    sp.sums = sums, sp.sums_best = d0 + n * msiren::ALIGN_SUMS, sp.rigid_trial = sp.sums_best + n * msiren::ALIGN_SUMS, sp.rigid_best = sp.rigid_trial + n * 4;
+    sp.scal = sp.rigid_best + n * 4;
+    sp.trial = (float*)(d0 + nd), sp.best = sp.trial + n * 6, sp.cnt = (int*)(sp.best + n * 6);
+    sp.trace = trace, sp.maps_out = maps_out, sp.rigid_out = rigid_out, sp.report = report;
+    sp.n = (int)n, sp.mode = o->mode;
+    sp.down = o->down, sp.up = o->up, sp.lam_min = o->lam_min, sp.lam_max = o->lam_max, sp.cy = o->centre_y, sp.cx = o->centre_x;
+    hipStream_t st = sc.s;
+    const unsigned gs = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(msiren::align_solve_init_kernel, dim3(gs), dim3(256), 0, st, sp, maps_in, rigid_in, o->damping);
+    HIPCHK(hipGetLastError());
+    for (int k = 0; k < o->iterations; ++k) {
+        if ((rc = align_evaluate(h, c, a, sp.trial, sums, nullptr, nullptr))) return rc;
+        hipEvent_t e1 = nullptr;
+        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+        sp.k = k, sp.last = k == o->iterations - 1;
+        hipLaunchKernelGGL(msiren::align_step_kernel, dim3(gs), dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        if ((rc = profile_end(h, c.stream, e1, n, "align_step_kernel"))) return rc;
+    }
+    return 0;
 }
 
 // msiren_weighted_fold_dev with the output side of another stride (kernel S', stride I', padding pad'): complete tiles, no black flags

@@ -888,6 +888,57 @@ class ModulatedSiren:
                                                  w.ctypes.data if warped else None, g.ctypes.data if gradient else None))
         return align.unpack(sums, w, g)
 
+    def _align_solve(self, images, targets, mode, maps, rigid, centre, iterations, damping, down, up, lam_min, lam_max, trace):
+        from . import align
+
+        self._ensure_committed()
+        a = np.ascontiguousarray(images.detach().cpu().numpy() if _is_torch(images) else images, dtype=np.float32)
+        t = np.ascontiguousarray(targets.detach().cpu().numpy() if _is_torch(targets) else targets, dtype=np.float32)
+        if a.ndim != 3:
+            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
+        n, Hh, Ww = a.shape
+        if t.ndim != 3 or t.shape[0] != n:
+            raise ValueError(f"expected targets of shape ({n}, th, tw), got {t.shape}")
+        if mode == align.AFFINE and maps.shape != (n, 6):
+            raise ValueError(f"expected maps of shape ({n}, 6), got {maps.shape}")
+        if mode == align.RIGID and rigid.shape != (n, 4):
+            raise ValueError(f"expected {n} angles and shifts of shape ({n}, 2), got a state of shape {rigid.shape}")
+        th, tw = t.shape[1:]
+        o = _lib.AlignSolveOpts(C.sizeof(_lib.AlignSolveOpts), mode, int(iterations), 0, float(damping), float(down), float(up), float(lam_min), float(lam_max),
+                                float(centre[0]), float(centre[1]))
+        out = np.zeros((n, 6), np.float32) if mode == align.RIGID else maps.copy()
+        rout = rigid.copy() if mode == align.RIGID else None
+        report = np.zeros((n, 6), np.float64)
+        tr = np.zeros((max(int(iterations), 0), n, 8), np.float64) if trace else None
+        _lib.check(self._lib.msiren_align_solve(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, C.byref(o), maps.ctypes.data if mode == align.AFFINE else None,
+                                                rigid.ctypes.data if mode == align.RIGID else None, out.ctypes.data, rout.ctypes.data if mode == align.RIGID else None,
+                                                report.ctypes.data, tr.ctypes.data if trace else None))
+        return align.solve_result(out, rout, report, tr)
+
+    def align_solve(self, images, targets, maps, *, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
+        """images (n, Hh, Ww), targets (n, th, tw), maps (n, 6) -> ``align.SolveResult``: every slice aligned to its target over the six
+        affine parameters, on the device -- ``align_cost``'s prologue once, then ``iterations`` evaluations with a Levenberg-Marquardt step
+        behind each (per slice: accept a lower mean cost and lower the damping by ``down``, reject and raise it by ``up``), no host
+        synchronisation in between (build-defined; msiren_align_solve).  ``maps`` of the result is the best map of
+        every slice; bit for bit what ``align.solve_on_host`` gives around ``align_cost``.  ``trace``: also the trial map, cost and count
+        of every evaluation (iterations, n, 8)."""
+        from . import align
+
+        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        return self._align_solve(images, targets, align.AFFINE, m, None, (0.0, 0.0), iterations, damping, down, up, lam_min, lam_max, trace)
+
+    def align_solve_rigid(self, images, targets, angle, shift, centre, *, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9,
+                          trace=False):
+        """As ``align_solve`` over rotation and in-plane shift: slice s starts at ``align.rigid_maps(angle, shift, centre)[s]`` (angle (n,)
+        radians, shift (n, 2), centre (2,) = (Y, X); cos, sin and shift are formed in fp64 here) and every trial is a rigid map about
+        ``centre`` (msiren_align_solve, mode 1).  ``angle`` and ``shift`` of the result are the best state's."""
+        from . import align
+
+        ang = np.atleast_1d(np.asarray(angle, dtype=np.float64))
+        sh = np.broadcast_to(np.asarray(shift, dtype=np.float64), (len(ang), 2))
+        rigid = np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang), sh[:, 0], sh[:, 1]], axis=1))
+        return self._align_solve(images, targets, align.RIGID, None, rigid, centre, iterations, damping, down, up, lam_min, lam_max, trace)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
