@@ -35,7 +35,8 @@ extern "C" {
 
 /* 9: msiren_resample_volume* (a stack of slices read as a volume at points (Z, Y, X), value, native value and gradient forms) added.
  * Under the same number, as pure additions (no existing symbol or struct changed): msiren_align_slices(_dev) (slices scored under affine maps
- * against targets: cost, gradient, JtJ); msiren_align_solve(_dev) and msiren_align_solve_opts (the damped Gauss-Newton loop around it, on the device).
+ * against targets: cost, gradient, JtJ); msiren_align_solve(_dev) and msiren_align_solve_opts (the damped Gauss-Newton loop around it, on the device);
+ * msiren_align_slices_w(_dev), msiren_align_solve_w(_dev) and msiren_align_solve_w_opts (the same two with a per-pixel weight and a per-slice gain and bias).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -485,6 +486,79 @@ MSIREN_API int msiren_align_solve_dev(msiren_handle h, const float* images_dev, 
                                       const float* maps_in_dev /* (n, 6), affine */, const double* rigid_in_dev /* (n, 4), rigid */,
                                       float* maps_out_dev /* (n, 6) */, double* rigid_out_dev /* (n, 4) or NULL */,
                                       double* report_dev /* (n, 6) */, double* trace_dev /* (iterations, n, 8) or NULL */);
+
+/* Build-defined: msiren_align_slices with a per-pixel weight and a per-slice gain and bias.  Everything of
+ * msiren_align_slices is unchanged (images, targets, maps, the point rule, R, gY, gX the bits of msiren_resample_slices_grad, the pipeline, the
+ * limits); two inputs are added:
+ *     weights (n, th, tw) float32 or NULL (every weight 1);   intensity (n, 2) float32 = (g, b) per slice or NULL ((1, 0))
+ * A pixel is VALID iff msiren_align_slices' condition holds (target, R, gY, gX all finite) and its weight w is finite and w > 0: a zero,
+ * negative, NaN or infinite weight masks the pixel.  An invalid pixel contributes to nothing.  Per valid pixel, in fp64 from the fp32 numbers, no
+ * fused multiply-add, each operation rounded on its own, in exactly this association:
+ *     m  = ((double)g (double)R) + (double)b          r = m - (double)T
+ *     gy = (double)g (double)gY                       gx = (double)g (double)gX
+ *     J  = (gy i, gy j, gy, gx i, gx j, gx, (double)R, 1.0)         (parameter order a00, a01, t0, a10, a11, t1, g, b)
+ *     wr = w r
+ *     count += 1;  wsum += w;  cost += wr r;  dcost[a] += (2 wr) J[a];  jtj[a, b] += (w J[a]) J[b]  for a <= b
+ * sums (n, 47) float64 = [count, wsum, cost, dcost[0..7], jtj: the upper triangle of the 8 x 8 matrix packed row-major (36)].
+ * warped / wgrad are what msiren_align_slices writes: R, gY, gX BEFORE gain and bias, the bits of msiren_resample_slices_grad.
+ * Every sum has msiren_align_slices' one order (chunks of 1024 pixels, thread t adds lo + t, lo + t + 256, ..., the butterfly inside each wave,
+ * the four waves in order, the chunks in index order; no floating-point atomics).  So, bit for bit: with g = 1, b = 0, w = 1 every shared
+ * entry (count, cost, dcost[0..5], the leading 6 x 6 block of jtj) is msiren_align_slices' and wsum == count; weights in {0, 1} give what
+ * msiren_align_slices gives on targets with NaN where the weight is 0; a weight that is a power of two scales wsum, cost, dcost and jtj
+ * exactly.  MSIREN_E_INVALID before any launch: what msiren_align_slices refuses (the partial records are 376 bytes per chunk in the
+ * 2^30 limit); device weights or intensity not 4-byte aligned.  Under msiren_profile_enable: "align_bin_kernels", the jet ragged trunk,
+ * "align_reduce_w_kernels". */
+MSIREN_API int msiren_align_slices_w(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                     const float* targets_host, int32_t th, int32_t tw, const float* maps_host /* (n, 6) */,
+                                     const float* weights_host /* (n, th, tw) or NULL */, const float* intensity_host /* (n, 2) or NULL */,
+                                     double* sums_host /* (n, 47) */, float* warped_host /* or NULL */, float* wgrad_host /* or NULL */);
+MSIREN_API int msiren_align_slices_w_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                         const float* targets_dev, int32_t th, int32_t tw, const float* maps_dev /* (n, 6) */,
+                                         const float* weights_dev /* (n, th, tw) or NULL */, const float* intensity_dev /* (n, 2) or NULL */,
+                                         double* sums_dev /* (n, 47) */, float* warped_dev /* or NULL */, float* wgrad_dev /* or NULL */);
+
+/* Build-defined: msiren_align_solve's loop around msiren_align_slices_w -- the prologue once, then `iterations` x
+ * (bin -> jet ragged trunk -> the 47-sum reduce -> one step kernel), no host synchronisation.  intensity_mode 0 (fixed): (g, b) stay at their
+ * inputs and the solve is over 6 parameters (affine) or 3 (rigid); 1 (estimate): (g, b) are solved for with the map, over 8 (affine) or 5
+ * (rigid).  With P the number of solved parameters and sums (count, wsum, cost, g[8], H[8][8]) at the trial (map, g, b):
+ *     mean = cost / wsum if count >= P else +inf;       accept / reject, lam and the flags: msiren_align_solve's
+ *     affine, fixed     msiren_align_solve's 6 x 6 system on the leading block of g, H
+ *     affine, estimate  the same expressions with 8 in place of 6;  trial[a] = (float)((double)best[a] + d[a]) for a < 6,
+ *                       g' = (float)((double)g_best + d[6]),  b' = (float)((double)b_best + d[7])
+ *     rigid, fixed      msiren_align_solve's 3 x 3 system on the leading 6 x 6 block
+ *     rigid, estimate   B (8 x 5): msiren_align_solve's 6 x 3 block, then B[6][3] = B[7][4] = 1, every other entry 0;  g5 = B^T g,
+ *                       H5 = B^T (H B), every sum ascending from 0.0, zero entries included;  the Cayley update on d[0..2];
+ *                       g' = (float)((double)g_best + d[3]),  b' = (float)((double)b_best + d[4])
+ * fp64 + - * / one at a time; mri_inr_amd/align.py: lm_step_w restates it in Python floats and gives the same bits.  With unit weights
+ * wsum == count, so with intensity_mode 0, no weights and no intensity the call returns msiren_align_solve's maps, report and trace columns.
+ * weights (n, th, tw) or NULL; intensity_in (n, 2) or NULL ((1, 0)).  maps_out (n, 6), intensity_out (n, 2): the best map and (g, b);
+ * rigid_out (n, 4) or NULL.  report (n, 7) float64: accepted, mean_first, mean_best, count at the best map, wsum at the best map, lam, flags.
+ * trace (iterations, n, 11) float64 or NULL: per evaluation the trial map (6), the trial g, b, then cost, count, wsum.
+ * A black slice (R = 0 everywhere: SINGULAR) and a slice whose weights mask every pixel (NO_OVERLAP) keep their inputs.
+ * MSIREN_E_INVALID with a message, before any launch: everything msiren_align_solve refuses; struct_size != sizeof(msiren_align_solve_w_opts);
+ * intensity_mode not 0 or 1; a null intensity_out or report; device weights or intensities not 4-byte aligned.
+ * Under msiren_profile_enable: the prologue's entries once per call; "align_bin_kernels", the jet ragged trunk, "align_reduce_w_kernels" and
+ * "align_step_w_kernel" `iterations` times. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(msiren_align_solve_w_opts) */
+    int32_t mode;             /* 0 affine, 1 rigid */
+    int32_t iterations;       /* evaluations, 1 .. 256 */
+    int32_t intensity_mode;   /* 0 fixed, 1 estimate */
+    double damping, down, up, lam_min, lam_max, centre_y, centre_x;
+} msiren_align_solve_w_opts;
+MSIREN_API int msiren_align_solve_w(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                    const float* targets_host, int32_t th, int32_t tw, const msiren_align_solve_w_opts* opts,
+                                    const float* maps_in /* (n, 6), affine */, const double* rigid_in /* (n, 4), rigid */,
+                                    const float* weights /* (n, th, tw) or NULL */, const float* intensity_in /* (n, 2) or NULL */,
+                                    float* maps_out /* (n, 6) */, float* intensity_out /* (n, 2) */, double* rigid_out /* (n, 4) or NULL */,
+                                    double* report /* (n, 7) */, double* trace /* (iterations, n, 11) or NULL */);
+MSIREN_API int msiren_align_solve_w_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                        const float* targets_dev, int32_t th, int32_t tw, const msiren_align_solve_w_opts* opts,
+                                        const float* maps_in_dev /* (n, 6), affine */, const double* rigid_in_dev /* (n, 4), rigid */,
+                                        const float* weights_dev /* (n, th, tw) or NULL */, const float* intensity_in_dev /* (n, 2) or NULL */,
+                                        float* maps_out_dev /* (n, 6) */, float* intensity_out_dev /* (n, 2) */,
+                                        double* rigid_out_dev /* (n, 4) or NULL */, double* report_dev /* (n, 7) */,
+                                        double* trace_dev /* (iterations, n, 11) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

@@ -63,6 +63,23 @@ class AlignSolveOpts(C.Structure):
     ]
 
 
+class AlignSolveWOpts(C.Structure):
+    """msiren_align_solve_w_opts"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_int32),
+        ("iterations", C.c_int32),
+        ("intensity_mode", C.c_int32),
+        ("damping", C.c_double),
+        ("down", C.c_double),
+        ("up", C.c_double),
+        ("lam_min", C.c_double),
+        ("lam_max", C.c_double),
+        ("centre_y", C.c_double),
+        ("centre_x", C.c_double),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -133,6 +150,10 @@ PROTOTYPES = {
     "msiren_align_slices_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
     "msiren_align_solve": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.POINTER(AlignSolveOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_align_solve_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.POINTER(AlignSolveOpts), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_slices_w": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_slices_w_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_solve_w": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.POINTER(AlignSolveWOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_solve_w_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, C.POINTER(AlignSolveWOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

@@ -16,7 +16,8 @@
 //                          forms: siren_trunk_f16x3n_ragged.hip.h), and the
 //                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h) and
 //                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h), msiren_align_slices* (slices scored
-//                          under affine maps against targets; align.hip.h), msiren_align_solve* (the damped Gauss-Newton loop around it)
+//                          under affine maps against targets; align.hip.h), msiren_align_solve* (the damped Gauss-Newton loop around it),
+//                          msiren_align_slices_w* / msiren_align_solve_w* (the two with a per-pixel weight and a per-slice gain and bias; align_w.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -262,6 +263,18 @@ int align_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, i
                       const void* rigid_in, const void* maps_out, const void* report);
 int align_solve(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
                 const msiren_align_solve_opts* o, const float* maps_in, const double* rigid_in, float* maps_out, double* rigid_out, double* report, double* trace);
+// msiren_align_slices_w* and msiren_align_solve_w* (align_w.hip.h): the same pipeline with a per-pixel weight and a per-slice
+// (gain, bias); weights_dev (n, th, tw) and intensity (n, 2) may be null; sums_dev (n, 47) doubles.  The checks as above; align_w_check also sizes
+// the larger partial records.
+constexpr int kAlignSumsW = 47;  // doubles per slice: count, wsum, cost, dcost[8], jtj[36] (align_w.hip.h: ALIGN_SUMS_W)
+int align_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw);
+int align_slices_w(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                   const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev);
+int align_solve_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_w_opts* o, const void* maps_in,
+                        const void* rigid_in, const void* maps_out, const void* intensity_out, const void* report);
+int align_solve_w(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                  const msiren_align_solve_w_opts* o, const float* maps_in, const double* rigid_in, const float* weights_dev, const float* intensity_in, float* maps_out,
+                  float* intensity_out, double* rigid_out, double* report, double* trace);
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 

@@ -21,6 +21,7 @@
 #include "resample.hip.h"
 #include "resample_volume.hip.h"
 #include "align.hip.h"
+#include "align_w.hip.h"
 #include "launch_dispatch.h"
 
 namespace msiren {  // the trunk / prologue kernels are compiled in their own translation units (k_*.hip)
@@ -1158,12 +1159,15 @@ struct AlignPlan {
     size_t nint = 0, nflt = 0, bytes = 0;  // words of the integer / float part of the bins, bytes of bins + partials (what follows is the caller's)
     const float* targets = nullptr;
     Call pc;
+    // msiren_align_slices_w* / msiren_align_solve_w* (DESIGN.md section 5.12): the 47-sum reduce; weights (n, th, tw) and intensity (n, 2) may be null
+    bool weighted = false;
+    const float *weights = nullptr, *intensity = nullptr;
 };
 
 // the checks, every workspace of the call (`extra` bytes more behind the partials in the stream's scratch: msiren_align_solve's state) and the
 // slice prologue.  *todo = false: nothing to do (n = 0 or th tw = 0).  No workspace moves after this.
 static int align_prepare(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
-                         const void* maps_dev, const void* sums_dev, size_t extra, AlignPlan* a, bool* todo) {
+                         const void* maps_dev, const void* sums_dev, size_t extra, AlignPlan* a, bool* todo, int nsums = msiren::ALIGN_SUMS) {
     *todo = false;
     int rc = align_check(h, n, height, width, th, tw);
     if (rc) return rc;
@@ -1177,9 +1181,9 @@ static int align_prepare(msiren_handle h, const Call& c, const float* images_dev
     const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, T = n * M * K, chunks = (M + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK;
     if ((rc = check_reflect_padding(h, height, width))) return rc;
     auto& sc = h->sc[c.stream];
-    // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T][partials n chunks 29 doubles, 8-byte aligned]
+    // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T][partials n chunks nsums doubles, 8-byte aligned]
     const size_t nint = (size_t)(4 * NP + 2 + 2 * T + 1) & ~(size_t)1, nflt = (size_t)(3 * T + 1) & ~(size_t)1;
-    const size_t bytes = (nint + nflt) * 4 + (size_t)n * chunks * msiren::ALIGN_SUMS * sizeof(double);
+    const size_t bytes = (nint + nflt) * 4 + (size_t)n * chunks * nsums * sizeof(double);
     if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, bytes + extra)) || (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * 3)))
         return rc;
     *a = AlignPlan{n, M, NPt, NP, T, chunks, th, tw, nV, nH, KA, K, nint, nflt, bytes, targets_dev, Call()};
@@ -1218,6 +1222,14 @@ static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, co
     const RaggedSet r{ap.coords, ap.offsets, T, NP, 1, plan + 2 + NP, NP, items};
     const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
     if ((rc = launch_trunk_f32_jet_ragged(h, a.pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale)) || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    if (a.weighted) {  // the 47-sum pair of align_w.hip.h: sums_dev (n, 47)
+        hipLaunchKernelGGL(msiren::align_partial_w_kernel, dim3((unsigned)(n * a.chunks)), dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, (const int*)sc.keep.p, a.targets,
+                           a.weights, a.intensity, warped_dev, wgrad_dev, partials, (int)n, (int)M, a.tw, a.K, (int)a.NPt, (int)T, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(msiren::align_combine_w_kernel, dim3((unsigned)n), dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        return profile_end(h, c.stream, e1, n * M, "align_reduce_w_kernels");
+    }
     hipLaunchKernelGGL(msiren::align_partial_kernel, dim3((unsigned)(n * a.chunks)), dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, (const int*)sc.keep.p, a.targets,
                        warped_dev, wgrad_dev, partials, (int)n, (int)M, a.tw, a.K, (int)a.NPt, (int)T, (int)a.chunks);
     HIPCHK(hipGetLastError());
@@ -1291,6 +1303,89 @@ int align_solve(msiren_handle h, const Call& c, const float* images_dev, int64_t
         hipLaunchKernelGGL(msiren::align_step_kernel, dim3(gs), dim3(256), 0, st, sp);
         HIPCHK(hipGetLastError());
         if ((rc = profile_end(h, c.stream, e1, n, "align_step_kernel"))) return rc;
+    }
+    return 0;
+}
+
+// msiren_align_slices_w* / msiren_align_solve_w* (kernels: align_w.hip.h): align_prepare and align_evaluate with the 47-sum
+// reduce.  Partial records are 376 bytes per chunk of 1024 pixels: the bin scratch and they stay below 2^30 together.
+static_assert(kAlignSumsW == msiren::ALIGN_SUMS_W, "host and kernels disagree about a slice's weighted record");
+int align_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
+    int rc = align_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    const int64_t M = (int64_t)th * tw;
+    if (20 * n * M * K + 8 * msiren::ALIGN_SUMS_W * n * ((M + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK) > 0x3fffffffLL)
+        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices x %d x %d target pixels x %d covering tiles (20 n th tw K must stay below 2^30)",
+                    (long long)n, th, tw, K);
+    return 0;
+}
+
+int align_slices_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                   const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = align_w_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    if ((uintptr_t)weights_dev % 4 || (uintptr_t)intensity_dev % 4) return fail(MSIREN_E_INVALID, "device weights and intensity must be 4-byte aligned");
+    AlignPlan a;
+    bool todo;
+    rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_dev, sums_dev, 0, &a, &todo, msiren::ALIGN_SUMS_W);
+    if (rc || !todo) return rc;
+    a.weighted = true, a.weights = weights_dev, a.intensity = intensity_dev;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+int align_solve_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_w_opts* o, const void* maps_in,
+                        const void* rigid_in, const void* maps_out, const void* intensity_out, const void* report) {
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_solve_w_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_solve_w_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_solve_w_opts));
+    if (o->intensity_mode != 0 && o->intensity_mode != 1) return fail(MSIREN_E_INVALID, "intensity_mode = %d (0: fixed, 1: estimate)", o->intensity_mode);
+    const msiren_align_solve_opts base{(uint32_t)sizeof(msiren_align_solve_opts), o->mode, o->iterations, 0, o->damping, o->down, o->up, o->lam_min, o->lam_max,
+                                       o->centre_y, o->centre_x};
+    int rc = align_solve_check(h, n, height, width, th, tw, &base, maps_in, rigid_in, maps_out, report);  // (everything msiren_align_solve refuses)
+    if (rc || (rc = align_w_check(h, n, height, width, th, tw))) return rc;
+    if (n > 0 && (int64_t)th * tw > 0 && !intensity_out) return fail(MSIREN_E_INVALID, "null argument (intensity_out)");
+    return 0;
+}
+
+int align_solve_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                  const msiren_align_solve_w_opts* o, const float* maps_in, const double* rigid_in, const float* weights_dev, const float* intensity_in, float* maps_out,
+                  float* intensity_out, double* rigid_out, double* report, double* trace) {
+    int rc = align_solve_w_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, intensity_out, report);
+    if (rc || n == 0 || (int64_t)th * tw == 0) return rc;
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_in % 4 ||
+        (uintptr_t)intensity_out % 4 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)trace % 8)
+        return fail(MSIREN_E_INVALID, "device maps, weights and intensity must be 4-byte aligned, rigid states, report and trace 8-byte aligned");
+    // state in the stream's scratch, behind the partials:
+    // [sums n 47][sums_best n 47][rigid_trial n 4][rigid_best n 4][scal n 3][trial n 6][best n 6][gb_trial n 2][gb_best n 2][cnt n 2]
+    const size_t nd = (size_t)n * (2 * msiren::ALIGN_SUMS_W + 4 + 4 + 3), extra = nd * sizeof(double) + (size_t)n * (6 + 6 + 2 + 2 + 2) * 4;
+    AlignPlan a;
+    bool todo;
+    if ((rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_out, report, extra, &a, &todo, msiren::ALIGN_SUMS_W)) || !todo) return rc;
+    auto& sc = h->sc[c.stream];
+    double* const d0 = (double*)((char*)sc.ragged.p + a.bytes);  // (a.bytes is a multiple of 8)
+    msiren::AlignSolveWParams sp{};
+    double* const sums = d0;
+    sp.sums = sums, sp.sums_best = d0 + n * msiren::ALIGN_SUMS_W, sp.rigid_trial = sp.sums_best + n * msiren::ALIGN_SUMS_W, sp.rigid_best = sp.rigid_trial + n * 4;
+    sp.scal = sp.rigid_best + n * 4;
+    sp.trial = (float*)(d0 + nd), sp.best = sp.trial + n * 6, sp.gb_trial = sp.best + n * 6, sp.gb_best = sp.gb_trial + n * 2, sp.cnt = (int*)(sp.gb_best + n * 2);
+    sp.trace = trace, sp.maps_out = maps_out, sp.intensity_out = intensity_out, sp.rigid_out = rigid_out, sp.report = report;
+    sp.n = (int)n, sp.mode = o->mode, sp.estimate = o->intensity_mode;
+    sp.down = o->down, sp.up = o->up, sp.lam_min = o->lam_min, sp.lam_max = o->lam_max, sp.cy = o->centre_y, sp.cx = o->centre_x;
+    a.weighted = true, a.weights = weights_dev, a.intensity = sp.gb_trial;
+    hipStream_t st = sc.s;
+    const unsigned gs = (unsigned)((n + 255) / 256);
+    hipLaunchKernelGGL(msiren::align_solve_init_w_kernel, dim3(gs), dim3(256), 0, st, sp, maps_in, rigid_in, intensity_in, o->damping);
+    HIPCHK(hipGetLastError());
+    for (int k = 0; k < o->iterations; ++k) {
+        if ((rc = align_evaluate(h, c, a, sp.trial, sums, nullptr, nullptr))) return rc;
+        hipEvent_t e1 = nullptr;
+        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+        sp.k = k, sp.last = k == o->iterations - 1;
+        hipLaunchKernelGGL(msiren::align_step_w_kernel, dim3(gs), dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        if ((rc = profile_end(h, c.stream, e1, n, "align_step_w_kernel"))) return rc;
     }
     return 0;
 }

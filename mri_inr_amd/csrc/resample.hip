@@ -2,8 +2,8 @@
 // gradient, with patch b evaluated at coords[offsets[b] : offsets[b + 1]].  The exact-fp32 trunks, on handles of every precision
 // (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
 // The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
-// msiren_resample_slices*, msiren_resample_volume*, msiren_align_slices* and msiren_align_solve* (DESIGN.md sections 5.8 - 5.11) are built on
-// these trunks: launch_dispatch.hip.
+// msiren_resample_slices*, msiren_resample_volume*, msiren_align_slices*, msiren_align_solve* and their weighted forms msiren_align_slices_w*,
+// msiren_align_solve_w* (DESIGN.md sections 5.8 - 5.12) are built on these trunks: launch_dispatch.hip.
 #include "host_buffers.h"
 #include "host_ctx.h"
 
@@ -159,9 +159,87 @@ int align_solve_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t
     return io.finish();
 }
 
+// the weighted forms: as the two above; the weights and the intensities go up once per call
+int align_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
+                 const float* maps_host, const float* weights_host, const float* intensity_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    int rc = check(h);
+    if (rc || (rc = align_w_check(h, n, height, width, th, tw))) return rc;
+    const int64_t M = (int64_t)th * tw;
+    if (n == 0 || M == 0) return 0;
+    if (!images_host || !targets_host || !maps_host || !sums_host) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)n * M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)n * 6 * sizeof(float), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_host, (size_t)n * 2 * sizeof(float), HOST_COPY);
+    const int o_s = io.out(sums_host, (size_t)n * kAlignSumsW * sizeof(double), HOST_IN_PLACE);
+    const int o_w = io.out(warped_host, nt, HOST_IN_PLACE), o_g = io.out(wgrad_host, 2 * nt, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_slices_w(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), th, tw, io.src<float>(i_m), io.src<float>(i_w), io.src<float>(i_gb),
+                             io.dst<double>(o_s), io.dst<float>(o_w), io.dst<float>(o_g))))
+        return rc;
+    return io.finish();
+}
+
+int align_solve_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
+                       const msiren_align_solve_w_opts* o, const float* maps_in, const double* rigid_in, const float* weights_host, const float* intensity_in,
+                       float* maps_out, float* intensity_out, double* rigid_out, double* report, double* trace) {
+    int rc = check(h);
+    if (rc || (rc = align_solve_w_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, intensity_out, report))) return rc;
+    const int64_t M = (int64_t)th * tw;
+    if (n == 0 || M == 0) return 0;
+    if (!images_host || !targets_host) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)n * M * sizeof(float);
+    const bool rigid = o->mode == 1;
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY);
+    const int i_m = io.in(rigid ? nullptr : maps_in, (size_t)n * 6 * sizeof(float), HOST_COPY), i_r = io.in(rigid ? rigid_in : nullptr, (size_t)n * 4 * sizeof(double), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_in, (size_t)n * 2 * sizeof(float), HOST_COPY);
+    const int o_m = io.out(maps_out, (size_t)n * 6 * sizeof(float), HOST_COPY), o_gb = io.out(intensity_out, (size_t)n * 2 * sizeof(float), HOST_COPY);
+    const int o_r = io.out(rigid_out, (size_t)n * 4 * sizeof(double), HOST_COPY);
+    const int o_rep = io.out(report, (size_t)n * 7 * sizeof(double), HOST_COPY), o_tr = io.out(trace, (size_t)o->iterations * n * 11 * sizeof(double), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_solve_w(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), th, tw, o, io.src<float>(i_m), io.src<double>(i_r), io.src<float>(i_w),
+                            io.src<float>(i_gb), io.dst<float>(o_m), io.dst<float>(o_gb), io.dst<double>(o_r), io.dst<double>(o_rep), io.dst<double>(o_tr))))
+        return rc;
+    return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
+
+int msiren_align_slices_w(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
+                          const float* maps_host, const float* weights_host, const float* intensity_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_w_host(h, images_host, n, height, width, targets_host, th, tw, maps_host, weights_host, intensity_host, sums_host, warped_host, wgrad_host);
+}
+int msiren_align_slices_w_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                              const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_w_check(h, n, height, width, th, tw))) return rc;  // (before the stream rotates)
+    return align_slices_w(h, dev_call(h), images_dev, n, height, width, targets_dev, th, tw, maps_dev, weights_dev, intensity_dev, sums_dev, warped_dev, wgrad_dev);
+}
+int msiren_align_solve_w(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
+                         const msiren_align_solve_w_opts* opts, const float* maps_in, const double* rigid_in, const float* weights_host, const float* intensity_in,
+                         float* maps_out, float* intensity_out, double* rigid_out, double* report, double* trace) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_solve_w_host(h, images_host, n, height, width, targets_host, th, tw, opts, maps_in, rigid_in, weights_host, intensity_in, maps_out, intensity_out, rigid_out,
+                              report, trace);
+}
+int msiren_align_solve_w_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                             const msiren_align_solve_w_opts* opts, const float* maps_in_dev, const double* rigid_in_dev, const float* weights_dev,
+                             const float* intensity_in_dev, float* maps_out_dev, float* intensity_out_dev, double* rigid_out_dev, double* report_dev, double* trace_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_solve_w_check(h, n, height, width, th, tw, opts, maps_in_dev, rigid_in_dev, maps_out_dev, intensity_out_dev, report_dev))) return rc;  // (before the stream rotates)
+    return align_solve_w(h, dev_call(h), images_dev, n, height, width, targets_dev, th, tw, opts, maps_in_dev, rigid_in_dev, weights_dev, intensity_in_dev, maps_out_dev,
+                         intensity_out_dev, rigid_out_dev, report_dev, trace_dev);
+}
 
 int msiren_align_solve(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
                        const msiren_align_solve_opts* opts, const float* maps_in, const double* rigid_in, float* maps_out, double* rigid_out, double* report,

@@ -939,6 +939,96 @@ class ModulatedSiren:
         rigid = np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang), sh[:, 0], sh[:, 1]], axis=1))
         return self._align_solve(images, targets, align.RIGID, None, rigid, centre, iterations, damping, down, up, lam_min, lam_max, trace)
 
+    @staticmethod
+    def _align_w_inputs(images, targets, weights, intensity):
+        """-> (images, targets, weights or None, intensity or None) as contiguous float32, shapes checked"""
+        def f32(x):
+            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+
+        a, t = f32(images), f32(targets)
+        if a.ndim != 3:
+            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
+        n = a.shape[0]
+        if t.ndim != 3 or t.shape[0] != n:
+            raise ValueError(f"expected targets of shape ({n}, th, tw), got {t.shape}")
+        w = None if weights is None else f32(weights)
+        if w is not None and w.shape != t.shape:
+            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
+        gb = None if intensity is None else f32(intensity)
+        if gb is not None and gb.shape != (n, 2):
+            raise ValueError(f"expected intensity of shape ({n}, 2), got {gb.shape}")
+        return a, t, w, gb
+
+    def align_cost_w(self, images, targets, maps, *, weights=None, intensity=None, warped=False, gradient=False):
+        """``align_cost`` with a per-pixel weight and a per-slice gain and bias -> ``align.AlignResultW``: ``weights`` (n, th, tw) or None (all
+        1; a weight that is zero, negative or not finite masks its pixel), ``intensity`` (n, 2) = (g, b) or None ((1, 0)); ``cost`` = sum w (g R
+        + b - T)^2 over the valid pixels, ``wsum`` their weights, ``grad`` (n, 8) and ``jtj`` (n, 8, 8) over (a00, a01, t0, a10, a11, t1, g, b)
+        (build-defined; msiren_align_slices_w).  Without weights and intensity the shared entries are ``align_cost``'s
+        bits.  ``warped`` / ``gradient`` return R and (gY, gX) before gain and bias."""
+        from . import align
+
+        self._ensure_committed()
+        a, t, w, gb = self._align_w_inputs(images, targets, weights, intensity)
+        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        n, Hh, Ww = a.shape
+        if m.shape != (n, 6):
+            raise ValueError(f"expected maps of shape ({n}, 6), got {m.shape}")
+        th, tw = t.shape[1:]
+        sums = np.zeros((n, align.SUMS_W), np.float64)
+        wp = np.full((n, th, tw), np.nan, np.float32) if warped else None
+        g = np.full((2, n, th, tw), np.nan, np.float32) if gradient else None
+        _lib.check(self._lib.msiren_align_slices_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, m.ctypes.data, None if w is None else w.ctypes.data,
+                                                   None if gb is None else gb.ctypes.data, sums.ctypes.data, wp.ctypes.data if warped else None,
+                                                   g.ctypes.data if gradient else None))
+        return align.unpack_w(sums, wp, g)
+
+    def _align_solve_w(self, images, targets, mode, maps, rigid, centre, weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min, lam_max, trace):
+        from . import align
+
+        self._ensure_committed()
+        a, t, w, gb = self._align_w_inputs(images, targets, weights, intensity)
+        n, Hh, Ww = a.shape
+        if mode == align.AFFINE and maps.shape != (n, 6):
+            raise ValueError(f"expected maps of shape ({n}, 6), got {maps.shape}")
+        if mode == align.RIGID and rigid.shape != (n, 4):
+            raise ValueError(f"expected {n} angles and shifts of shape ({n}, 2), got a state of shape {rigid.shape}")
+        th, tw = t.shape[1:]
+        o = _lib.AlignSolveWOpts(C.sizeof(_lib.AlignSolveWOpts), mode, int(iterations), align.ESTIMATE if estimate_intensity else align.FIXED, float(damping), float(down),
+                                 float(up), float(lam_min), float(lam_max), float(centre[0]), float(centre[1]))
+        out = np.zeros((n, 6), np.float32) if mode == align.RIGID else maps.copy()
+        gout = np.tile(np.array([1.0, 0.0], np.float32), (n, 1)) if gb is None else gb.copy()
+        rout = rigid.copy() if mode == align.RIGID else None
+        report = np.zeros((n, 7), np.float64)
+        tr = np.zeros((max(int(iterations), 0), n, 11), np.float64) if trace else None
+        _lib.check(self._lib.msiren_align_solve_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, C.byref(o), maps.ctypes.data if mode == align.AFFINE else None,
+                                                  rigid.ctypes.data if mode == align.RIGID else None, None if w is None else w.ctypes.data,
+                                                  None if gb is None else gb.ctypes.data, out.ctypes.data, gout.ctypes.data,
+                                                  rout.ctypes.data if mode == align.RIGID else None, report.ctypes.data, tr.ctypes.data if trace else None))
+        return align.solve_result_w(out, gout, rout, report, tr)
+
+    def align_solve_w(self, images, targets, maps, *, weights=None, intensity=None, estimate_intensity=True, iterations=12, damping=1e-3, down=0.1, up=10.0,
+                      lam_min=1e-9, lam_max=1e9, trace=False):
+        """``align_solve`` on ``align_cost_w`` -> ``align.SolveResultW``: every pixel weighted by ``weights`` (n, th, tw), the target modelled as
+        g R + b per slice from ``intensity`` (n, 2) (None: (1, 0)).  ``estimate_intensity``: (g, b) are solved for together with the map (8
+        parameters); False: they stay at their inputs (6).  The accept / reject rule compares cost / wsum (build-defined, DESIGN.md section 5.12;
+        msiren_align_solve_w); bit for bit what ``align.solve_on_host_w`` gives around ``align_cost_w``.  ``trace``: (iterations, n, 11)."""
+        from . import align
+
+        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        return self._align_solve_w(images, targets, align.AFFINE, m, None, (0.0, 0.0), weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min,
+                                   lam_max, trace)
+
+    def align_solve_rigid_w(self, images, targets, angle, shift, centre, *, weights=None, intensity=None, estimate_intensity=True, iterations=12, damping=1e-3, down=0.1,
+                            up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
+        """As ``align_solve_w`` over rotation and in-plane shift (``align_solve_rigid``'s arguments): 5 parameters with the intensity, 3 without."""
+        from . import align
+
+        ang = np.atleast_1d(np.asarray(angle, dtype=np.float64))
+        sh = np.broadcast_to(np.asarray(shift, dtype=np.float64), (len(ang), 2))
+        rigid = np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang), sh[:, 0], sh[:, 1]], axis=1))
+        return self._align_solve_w(images, targets, align.RIGID, None, rigid, centre, weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min,
+                                   lam_max, trace)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
