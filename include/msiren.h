@@ -36,7 +36,9 @@ extern "C" {
 /* 9: msiren_resample_volume* (a stack of slices read as a volume at points (Z, Y, X), value, native value and gradient forms) added.
  * Under the same number, as pure additions (no existing symbol or struct changed): msiren_align_slices(_dev) (slices scored under affine maps
  * against targets: cost, gradient, JtJ); msiren_align_solve(_dev) and msiren_align_solve_opts (the damped Gauss-Newton loop around it, on the device);
- * msiren_align_slices_w(_dev), msiren_align_solve_w(_dev) and msiren_align_solve_w_opts (the same two with a per-pixel weight and a per-slice gain and bias).
+ * msiren_align_slices_w(_dev), msiren_align_solve_w(_dev) and msiren_align_solve_w_opts (the same two with a per-pixel weight and a per-slice gain and bias);
+ * msiren_align_volume(_dev), msiren_align_volume_solve(_dev) and msiren_align_volume_solve_opts (target slices scored against, and aligned to, the stack
+ * read as a volume under 3 x 3 maps).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -559,6 +561,80 @@ MSIREN_API int msiren_align_solve_w_dev(msiren_handle h, const float* images_dev
                                         float* maps_out_dev /* (n, 6) */, float* intensity_out_dev /* (n, 2) */,
                                         double* rigid_out_dev /* (n, 4) or NULL */, double* report_dev /* (n, 7) */,
                                         double* trace_dev /* (iterations, n, 11) or NULL */);
+
+/* Build-defined: m target slices scored against the stack of n slices READ AS A VOLUME (msiren_resample_volume_grad), each
+ * under its own 3 x 3 map -- per target the sum of squared differences, its gradient over the nine map parameters and the Gauss-Newton matrix JtJ.
+ *     images (n, height, width) float32, n >= 2;  targets (m, th, tw) float32, m independent of n;
+ *     maps (m, 9) float32 = (z0, z1, tz, y0, y1, ty, x0, x1, tx)
+ * Pixel (i, j) of target q is read at
+ *     Z = ((z0 i) + (z1 j)) + tz      Y = ((y0 i) + (y1 j)) + ty      X = ((x0 i) + (x1 j)) + tx
+ * in fp32, i and j converted exactly, every operation rounded on its own (NO fused multiply-add: float32 arithmetic in numpy gives the same bits).
+ * Z is in slice units, (Y, X) in reconstruction pixel coordinates.  R, gZ, gY, gX are THE BITS of msiren_resample_volume_grad at (Z, Y, X)
+ * (value, planes 0, 1, 2): the pair z0' = min(floor Z, n - 2) with f' = Z - z0', the selection R0 / R1 / fma(f', R1, (1 - f') R0), gZ = R1 - R0,
+ * NaN in every plane for a Z outside 0 .. n - 1 or where no tile covers (Y, X), a black tile 0 with its weight, no derivative of the fold weights.
+ * A pixel is VALID iff targets[q, i, j], R, gZ, gY and gX are all finite.  Per valid pixel, in fp64 from the fp32 numbers, no fused multiply-add:
+ *     r = (double)R - (double)T        J = (gZ i, gZ j, gZ, gY i, gY j, gY, gX i, gX j, gX)       (parameter order: the map's)
+ *     count += 1;  cost += r r;  dcost[a] += (2 r) J[a];  jtj[a, b] += J[a] J[b]  for a <= b
+ * sums (m, 56) float64 = [count, cost, dcost[0..8], jtj: the upper triangle packed row-major (45)].
+ * warped (m, th, tw) = R and wgrad (3, m, th, tw) = gZ, gY, gX are optional (NULL: not written); at invalid pixels they carry what
+ * msiren_resample_volume_grad gives.  Every sum has msiren_align_slices' one order (chunks of 1024 consecutive pixels of a target; thread t of 256
+ * adds p = lo + t, lo + t + 256, ...; the butterfly inside each wave, the four waves in order; the chunks in index order; no floating-point
+ * atomics): the same bits run to run, a target alone gives its row of any batch, passing or omitting warped / wgrad changes no bit.  With
+ * m = n and the Z row (0, 0, s) the entries count, cost, dcost[3..8] and the in-plane 6 x 6 block of jtj are msiren_align_slices' of slice s.
+ * The pipeline, on the call's stream: msiren_resample_volume's prologue -> the pixels binned by (slice, tile), two slices each -> the jet ragged
+ * trunk over those n nV nH bins, at most T = 2 m th tw K entries -> per chunk blend and partial sums -> per target the total.  MSIREN_E_INVALID
+ * before any launch, naming the product: n < 2; 32 M K + 8 M (M = m th tw) with 448 bytes per chunk, or 16 n nV nH, not below 2^30; M not below
+ * 2^28; the gradient calls' model limits; a null argument.  m = 0 or th tw = 0 does nothing.  The host-pointer form is a synchronous one-chunk
+ * call; the _dev form enqueues on the stream rotation.  Under msiren_profile_enable: "align_volume_bin_kernels", the jet ragged trunk under its
+ * name, "align_volume_reduce_kernels". */
+MSIREN_API int msiren_align_volume(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                   const float* targets_host, int64_t m_targets, int32_t th, int32_t tw, const float* maps_host /* (m, 9) */,
+                                   double* sums_host /* (m, 56) */, float* warped_host /* or NULL */, float* wgrad_host /* (3, m, th, tw) or NULL */);
+MSIREN_API int msiren_align_volume_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                       const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw, const float* maps_dev /* (m, 9) */,
+                                       double* sums_dev /* (m, 56) */, float* warped_dev /* or NULL */, float* wgrad_dev /* or NULL */);
+
+/* Build-defined: targets aligned to the volume on the device -- msiren_align_solve's loop around msiren_align_volume: the
+ * prologue once, then `iterations` x (bin -> jet ragged trunk -> the 56-sum reduce -> one step kernel), no host synchronisation.  Accept / reject,
+ * lam and the flags are msiren_align_solve's;  mean = cost / count if count >= P else +inf.
+ *     mode 0, affine, P = 9   msiren_align_solve's expressions with 9 in place of 6
+ *     mode 1, rigid,  P = 6   a rigid motion of the target's nominal plane in physical space, slices `spacing` pixels apart.  planes (m, 12)
+ *             float64 = (e_i, e_j, o, c): the lattice's two step vectors, its origin and the rotation centre, triples in (Z, Y, X) order in
+ *             pixel units.  State (Rot (9, row-major), u (3)) float64.  With v_i = Rot e_i, v_j = Rot e_j, v_o = Rot (o - c), t = (v_o + c) + u,
+ *             row r of the map is (float)(v_i[r], v_j[r], t[r]), the Z row (r = 0) divided by spacing before rounding.
+ *             B (9 x 6) over (w0, w1, w2, u0, u1, u2): B[3 r + col][k] = (e_k x v_col)[r] (v_col = v_i, v_j, v_o), B[3 r + 2][3 + k] = [r == k], the
+ *             rows r = 0 divided by spacing;  g6 = B^T g, H6 = B^T (H B), every sum ascending from 0.0, zero entries included;  d = ldl_solve(H6
+ *             damped, -g6 / 2);  a = d[0..2] / 2, Cay = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a) (an exact rotation, no trigonometry),
+ *             Rot' = Cay Rot, u' = u + d[3..5].
+ * fp64 + - * / one at a time, no fused multiply-add; DESIGN.md section 5.13 fixes every association and mri_inr_amd/align_volume.py: lm_step_v restates
+ * it in Python floats with the same bits, so the call equals the same loop on the host around msiren_align_volume bit for bit.
+ * Affine mode reads maps_in (m, 9); rigid mode reads planes (m, 12) and rigid_in (m, 12).  maps_out (m, 9): the best map.  rigid_out (m, 12) or
+ * NULL: the best rigid state (zeros in affine mode).  report (m, 6) float64: msiren_align_solve's (accepted, mean_first, mean_best, count at the
+ * best map, lam, flags).  trace (iterations, m, 11) float64 or NULL: per evaluation the trial map as nine doubles, cost, count.
+ * MSIREN_E_INVALID with a message, before any launch: what msiren_align_volume refuses; struct_size != sizeof(msiren_align_volume_solve_opts); mode
+ * not 0 or 1; iterations outside 1 .. 256; anything outside 0 < lam_min <= damping <= lam_max < inf, 0 < down <= 1, 1 <= up < inf; in rigid mode
+ * a spacing that is not finite and > 0; a missing input of the mode, a null maps_out or report; device pointers not aligned to 4 (floats) / 8
+ * (doubles) bytes.  Under msiren_profile_enable: the prologue's entries once per call; "align_volume_bin_kernels", the jet ragged trunk,
+ * "align_volume_reduce_kernels" and "align_volume_step_kernel" `iterations` times. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(msiren_align_volume_solve_opts) */
+    int32_t mode;             /* 0 affine, 1 rigid */
+    int32_t iterations;       /* evaluations, 1 .. 256 */
+    int32_t reserved;
+    double damping, down, up, lam_min, lam_max, spacing;
+} msiren_align_volume_solve_opts;
+MSIREN_API int msiren_align_volume_solve(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                         const float* targets_host, int64_t m_targets, int32_t th, int32_t tw,
+                                         const msiren_align_volume_solve_opts* opts, const float* maps_in /* (m, 9), affine */,
+                                         const double* planes /* (m, 12), rigid */, const double* rigid_in /* (m, 12), rigid */,
+                                         float* maps_out /* (m, 9) */, double* rigid_out /* (m, 12) or NULL */, double* report /* (m, 6) */,
+                                         double* trace /* (iterations, m, 11) or NULL */);
+MSIREN_API int msiren_align_volume_solve_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                             const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw,
+                                             const msiren_align_volume_solve_opts* opts, const float* maps_in_dev /* (m, 9), affine */,
+                                             const double* planes_dev /* (m, 12), rigid */, const double* rigid_in_dev /* (m, 12), rigid */,
+                                             float* maps_out_dev /* (m, 9) */, double* rigid_out_dev /* (m, 12) or NULL */,
+                                             double* report_dev /* (m, 6) */, double* trace_dev /* (iterations, m, 11) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

@@ -17,7 +17,8 @@
 //                          reconstruction at arbitrary points built on it: msiren_resample_slices* (bin / blend kernels: resample.hip.h) and
 //                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h), msiren_align_slices* (slices scored
 //                          under affine maps against targets; align.hip.h), msiren_align_solve* (the damped Gauss-Newton loop around it),
-//                          msiren_align_slices_w* / msiren_align_solve_w* (the two with a per-pixel weight and a per-slice gain and bias; align_w.hip.h)
+//                          msiren_align_slices_w* / msiren_align_solve_w* (the two with a per-pixel weight and a per-slice gain and bias; align_w.hip.h),
+//                          msiren_align_volume* / msiren_align_volume_solve* (target slices against the stack read as a volume, 3 x 3 maps; align_volume.hip.h)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -275,6 +276,18 @@ int align_solve_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width,
 int align_solve_w(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
                   const msiren_align_solve_w_opts* o, const float* maps_in, const double* rigid_in, const float* weights_dev, const float* intensity_in, float* maps_out,
                   float* intensity_out, double* rigid_out, double* report, double* trace);
+// msiren_align_volume* and msiren_align_volume_solve* (align_volume.hip.h): m targets (th, tw) scored against the stack of n slices
+// read as a volume, one 3 x 3 map (m, 9) each; sums_dev (m, 56) doubles; warped_dev (m, th, tw) and wgrad_dev (3, m, th, tw) may be null.  The solve:
+// the prologue once, then opts->iterations x (evaluation at the trial maps -> align_volume_step_kernel) on the call's stream.
+constexpr int kAlignVolumeSums = 56;  // doubles per target: count, cost, dcost[9], jtj[45] (align_volume.hip.h: ALIGN_VOLUME_SUMS)
+int align_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw);  // 0, or MSIREN_E_INVALID naming what is too large
+int align_volume(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev);
+int align_volume_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_opts* o,
+                             const void* maps_in, const void* planes, const void* rigid_in, const void* maps_out, const void* report);
+int align_volume_solve(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                       int32_t tw, const msiren_align_volume_solve_opts* o, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out,
+                       double* rigid_out, double* report, double* trace);
 int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
 int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 

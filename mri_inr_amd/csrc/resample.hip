@@ -3,7 +3,7 @@
 // (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
 // The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
 // msiren_resample_slices*, msiren_resample_volume*, msiren_align_slices*, msiren_align_solve* and their weighted forms msiren_align_slices_w*,
-// msiren_align_solve_w* (DESIGN.md sections 5.8 - 5.12) are built on these trunks: launch_dispatch.hip.
+// msiren_align_solve_w*, and msiren_align_volume*, msiren_align_volume_solve* (DESIGN.md sections 5.8 - 5.13) are built on these trunks: launch_dispatch.hip.
 #include "host_buffers.h"
 #include "host_ctx.h"
 
@@ -208,6 +208,54 @@ int align_solve_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32
     return io.finish();
 }
 
+// target slices scored against the stack read as a volume, one synchronous one-chunk call on host pointers
+int align_volume_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                      const float* maps_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    int rc = check(h);
+    if (rc || (rc = align_volume_check(h, n, height, width, m, th, tw))) return rc;
+    const int64_t M = m * (int64_t)th * tw;
+    if (M == 0) return 0;
+    if (!images_host || !targets_host || !maps_host || !sums_host) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)m * 9 * sizeof(float), HOST_COPY);
+    const int o_s = io.out(sums_host, (size_t)m * kAlignVolumeSums * sizeof(double), HOST_IN_PLACE);
+    const int o_w = io.out(warped_host, nt, HOST_IN_PLACE), o_g = io.out(wgrad_host, 3 * nt, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_volume(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, io.src<float>(i_m), io.dst<double>(o_s), io.dst<float>(o_w),
+                           io.dst<float>(o_g))))
+        return rc;
+    return io.finish();
+}
+
+// targets aligned to the volume, one synchronous one-chunk call on host pointers: images + targets + the start go up once, the loop runs on the device
+int align_volume_solve_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                            const msiren_align_volume_solve_opts* o, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out, double* rigid_out,
+                            double* report, double* trace) {
+    int rc = check(h);
+    if (rc || (rc = align_volume_solve_check(h, n, height, width, m, th, tw, o, maps_in, planes, rigid_in, maps_out, report))) return rc;
+    const int64_t M = m * (int64_t)th * tw;
+    if (M == 0) return 0;
+    if (!images_host || !targets_host) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    const bool rigid = o->mode == 1;
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY);
+    const int i_m = io.in(rigid ? nullptr : maps_in, (size_t)m * 9 * sizeof(float), HOST_COPY), i_p = io.in(rigid ? planes : nullptr, (size_t)m * 12 * sizeof(double), HOST_COPY);
+    const int i_r = io.in(rigid ? rigid_in : nullptr, (size_t)m * 12 * sizeof(double), HOST_COPY);
+    const int o_m = io.out(maps_out, (size_t)m * 9 * sizeof(float), HOST_COPY), o_r = io.out(rigid_out, (size_t)m * 12 * sizeof(double), HOST_COPY);
+    const int o_rep = io.out(report, (size_t)m * 6 * sizeof(double), HOST_COPY), o_tr = io.out(trace, (size_t)o->iterations * m * 11 * sizeof(double), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_volume_solve(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, o, io.src<float>(i_m), io.src<double>(i_p), io.src<double>(i_r),
+                                 io.dst<float>(o_m), io.dst<double>(o_r), io.dst<double>(o_rep), io.dst<double>(o_tr))))
+        return rc;
+    return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -239,6 +287,34 @@ int msiren_align_solve_w_dev(msiren_handle h, const float* images_dev, int64_t n
     if ((rc = align_solve_w_check(h, n, height, width, th, tw, opts, maps_in_dev, rigid_in_dev, maps_out_dev, intensity_out_dev, report_dev))) return rc;  // (before the stream rotates)
     return align_solve_w(h, dev_call(h), images_dev, n, height, width, targets_dev, th, tw, opts, maps_in_dev, rigid_in_dev, weights_dev, intensity_in_dev, maps_out_dev,
                          intensity_out_dev, rigid_out_dev, report_dev, trace_dev);
+}
+
+int msiren_align_volume(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                        const float* maps_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_volume_host(h, images_host, n, height, width, targets_host, m, th, tw, maps_host, sums_host, warped_host, wgrad_host);
+}
+int msiren_align_volume_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                            const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_volume_check(h, n, height, width, m, th, tw))) return rc;  // (before the stream rotates)
+    return align_volume(h, dev_call(h), images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+int msiren_align_volume_solve(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th,
+                              int32_t tw, const msiren_align_volume_solve_opts* opts, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out,
+                              double* rigid_out, double* report, double* trace) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_volume_solve_host(h, images_host, n, height, width, targets_host, m, th, tw, opts, maps_in, planes, rigid_in, maps_out, rigid_out, report, trace);
+}
+int msiren_align_volume_solve_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                                  int32_t tw, const msiren_align_volume_solve_opts* opts, const float* maps_in_dev, const double* planes_dev, const double* rigid_in_dev,
+                                  float* maps_out_dev, double* rigid_out_dev, double* report_dev, double* trace_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_volume_solve_check(h, n, height, width, m, th, tw, opts, maps_in_dev, planes_dev, rigid_in_dev, maps_out_dev, report_dev))) return rc;  // (before the stream rotates)
+    return align_volume_solve(h, dev_call(h), images_dev, n, height, width, targets_dev, m, th, tw, opts, maps_in_dev, planes_dev, rigid_in_dev, maps_out_dev, rigid_out_dev,
+                              report_dev, trace_dev);
 }
 
 int msiren_align_solve(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,

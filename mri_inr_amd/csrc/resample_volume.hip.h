@@ -91,6 +91,12 @@ __global__ __launch_bounds__(256) void resample_volume_count_kernel(ResampleVolu
             }
 }
 
+// The fill kernels' fp64 expressions, shared with align_volume_fill_kernel (align_volume.hip.h): a point's offset inside a tile along one axis,
+// its local coordinate there and its fold weight -- fp64 from the fp32 coordinate, rounded once
+__device__ __forceinline__ double volume_tile_offset(float Y, int v, int I, int pad) { return (double)Y - (double)(v * I - pad); }
+__device__ __forceinline__ float volume_local_coord(double t, double den) { return (float)(-1.0 + t * 2.0 / den); }
+__device__ __forceinline__ float volume_fold_weight(double ty, double tx, double c) { return (float)exp(-0.1 * sqrt((ty - c) * (ty - c) + (tx - c) * (tx - c))); }
+
 __global__ __launch_bounds__(256) void resample_volume_fill_kernel(ResampleVolumeParams p) {
     const int m = blockIdx.x * 256 + threadIdx.x;
     const bool in = m < p.M;
@@ -114,13 +120,13 @@ __global__ __launch_bounds__(256) void resample_volume_fill_kernel(ResampleVolum
                 const int place = wave_bin_add(p.cursors, bin, has);
                 if (has) {  // (m < M)
                     const int k = a * nh + b;  // the point's covering tiles in (v, h) row-major order
-                    const double ty = (double)Y - (double)((v0 + a) * p.I - p.pad), tx = (double)X - (double)((h0 + b) * p.I - p.pad);
+                    const double ty = volume_tile_offset(Y, v0 + a, p.I, p.pad), tx = volume_tile_offset(X, h0 + b, p.I, p.pad);
                     const int e = p.offsets[bin] + place;
-                    reinterpret_cast<float2*>(p.coords)[e] = make_float2((float)(-1.0 + ty * 2.0 / den), (float)(-1.0 + tx * 2.0 / den));
+                    reinterpret_cast<float2*>(p.coords)[e] = make_float2(volume_local_coord(ty, den), volume_local_coord(tx, den));
                     p.ent[((size_t)2 * m + j) * K + k] = e;
                     if (j == 0) {
                         p.tile[(size_t)m * K + k] = t;
-                        p.w[(size_t)m * K + k] = (float)exp(-0.1 * sqrt((ty - c) * (ty - c) + (tx - c) * (tx - c)));
+                        p.w[(size_t)m * K + k] = volume_fold_weight(ty, tx, c);
                     }
                 }
             }

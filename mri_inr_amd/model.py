@@ -1029,6 +1029,87 @@ class ModulatedSiren:
         return self._align_solve_w(images, targets, align.RIGID, None, rigid, centre, weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min,
                                    lam_max, trace)
 
+    @staticmethod
+    def _align_volume_inputs(images, targets):
+        """-> (images, targets) as contiguous float32, shapes checked"""
+        a = np.ascontiguousarray(images.detach().cpu().numpy() if _is_torch(images) else images, dtype=np.float32)
+        t = np.ascontiguousarray(targets.detach().cpu().numpy() if _is_torch(targets) else targets, dtype=np.float32)
+        if a.ndim != 3:
+            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
+        if t.ndim != 3:
+            raise ValueError(f"expected targets of shape (m, th, tw), got {t.shape}")
+        return a, t
+
+    def align_volume_cost(self, images, targets, maps, *, warped=False, gradient=False):
+        """images (n, Hh, Ww), n >= 2, targets (m, th, tw), maps (m, 9) -> ``align_volume.AlignResultV``: every target's lattice read in the stack
+        as a volume under its own 3 x 3 map (``align_volume.map_points3``: pixel (i, j) at Z = z0 i + z1 j + tz in slice units, Y = y0 i + y1 j + ty,
+        X = x0 i + x1 j + tx in reconstruction pixels) and scored against the target on the device -- ``count``, ``cost`` = sum (R - T)^2, ``grad``
+        (m, 9), ``jtj`` (m, 9, 9); R and its gradient are the bits of ``resample_volume_with_gradient`` (build-defined, DESIGN.md section 5.13;
+        msiren_align_volume).  m is independent of n.  ``warped`` / ``gradient``: also return R (m, th, tw) / (gZ, gY, gX) (3, m, th, tw)."""
+        from . import align_volume as av
+
+        self._ensure_committed()
+        a, t = self._align_volume_inputs(images, targets)
+        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        if mp.shape != (m, 9):
+            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
+        sums = np.zeros((m, av.SUMS_V), np.float64)
+        w = np.full((m, th, tw), np.nan, np.float32) if warped else None
+        g = np.full((3, m, th, tw), np.nan, np.float32) if gradient else None
+        _lib.check(self._lib.msiren_align_volume(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, mp.ctypes.data, sums.ctypes.data,
+                                                 w.ctypes.data if warped else None, g.ctypes.data if gradient else None))
+        return av.unpack_v(sums, w, g)
+
+    def _align_volume_solve(self, images, targets, mode, maps, planes, rigid, spacing, iterations, damping, down, up, lam_min, lam_max, trace):
+        from . import align, align_volume as av
+
+        self._ensure_committed()
+        a, t = self._align_volume_inputs(images, targets)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        if mode == align.AFFINE and maps.shape != (m, 9):
+            raise ValueError(f"expected maps of shape ({m}, 9), got {maps.shape}")
+        if mode == align.RIGID and (planes.shape != (m, 12) or rigid.shape != (m, 12)):
+            raise ValueError(f"expected planes and states of shape ({m}, 12), got {planes.shape} and {rigid.shape}")
+        o = _lib.AlignVolumeSolveOpts(C.sizeof(_lib.AlignVolumeSolveOpts), mode, int(iterations), 0, float(damping), float(down), float(up), float(lam_min),
+                                      float(lam_max), float(spacing))
+        is_rigid = mode == align.RIGID
+        out = np.zeros((m, 9), np.float32) if is_rigid else maps.copy()
+        rout = rigid.copy() if is_rigid else None
+        report = np.zeros((m, 6), np.float64)
+        tr = np.zeros((max(int(iterations), 0), m, 11), np.float64) if trace else None
+        _lib.check(self._lib.msiren_align_volume_solve(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), None if is_rigid else maps.ctypes.data,
+                                                       planes.ctypes.data if is_rigid else None, rigid.ctypes.data if is_rigid else None, out.ctypes.data,
+                                                       rout.ctypes.data if is_rigid else None, report.ctypes.data, tr.ctypes.data if trace else None))
+        return av.solve_result_v(out, rout, report, tr)
+
+    def align_volume_solve(self, images, targets, maps, *, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
+        """images (n, Hh, Ww), targets (m, th, tw), maps (m, 9) -> ``align_volume.SolveResultV``: every target aligned to the volume over the nine
+        parameters of its map, on the device -- ``align_volume_cost``'s prologue once, then ``iterations`` evaluations with ``align_solve``'s
+        Levenberg-Marquardt step behind each, no host synchronisation (build-defined; msiren_align_volume_solve).  Bit for
+        bit what ``align_volume.solve_on_host_v`` gives around ``align_volume_cost``.  ``trace``: (iterations, m, 11)."""
+        from . import align
+
+        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        return self._align_volume_solve(images, targets, align.AFFINE, mp, None, None, 1.0, iterations, damping, down, up, lam_min, lam_max, trace)
+
+    def align_volume_solve_rigid(self, images, targets, planes, spacing, *, rotation=None, shift=None, iterations=12, damping=1e-3, down=0.1, up=10.0,
+                                 lam_min=1e-9, lam_max=1e9, trace=False):
+        """As ``align_volume_solve`` over a rigid motion of every target's nominal plane in physical space (6 parameters): ``planes`` (m, 12)
+        float64 = (e_i, e_j, o, c), the lattice's two step vectors, its origin and the rotation centre as (Z, Y, X) triples in pixel units; slices are
+        ``spacing`` pixels apart.  Starts at ``rotation`` (m, 3, 3) (None: the identity) and ``shift`` (m, 3) (None: zero); every trial map is
+        ``align_volume.rigid_maps3`` of the state (msiren_align_volume_solve, mode 1).  ``rotation`` and ``shift`` of the result are the best state's."""
+        from . import align
+
+        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
+        m = len(pl)
+        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (m, 3, 3)).reshape(m, 9)
+        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (m, 3))
+        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
+        return self._align_volume_solve(images, targets, align.RIGID, None, pl, rigid, spacing, iterations, damping, down, up, lam_min, lam_max, trace)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
