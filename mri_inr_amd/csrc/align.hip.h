@@ -104,6 +104,38 @@ __global__ __launch_bounds__(256) void align_fill_kernel(AlignParams p) {
 
 __device__ __forceinline__ bool align_finite(float x) { return fabsf(x) < __builtin_inff(); }  // (false for a NaN)
 
+// The one order of a chunk's N sums over its 256 threads, score_block_sum's for all N at once: butterfly inside each wave, then the four wave
+// totals in wave order -> partials[block, 0..N).  red: the workgroup's N x 4 doubles of LDS.  Every partial kernel ends with this.
+template <int N>
+__device__ __forceinline__ void align_block_reduce(const double (&acc)[N], double (&red)[N][4], double* __restrict__ partials) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int a = 0; a < N; ++a) {
+        double v = acc[a];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if ((threadIdx.x & 63) == 0) red[a][threadIdx.x >> 6] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const int a = threadIdx.x;
+        partials[(size_t)blockIdx.x * N + a] = ((red[a][0] + red[a][1]) + red[a][2]) + red[a][3];
+    }
+}
+
+// sums[unit, a] = the unit's `chunks` partial records added in index order: the body of every combine kernel (one workgroup per unit)
+template <int N>
+__device__ __forceinline__ void align_combine(const double* __restrict__ partials, double* __restrict__ sums, int chunks) {
+#pragma clang fp contract(off)
+    const int s = blockIdx.x, a = threadIdx.x;
+    if (a < N) {
+        const double* pr = partials + (size_t)s * chunks * N + a;
+        double t = pr[0];
+        for (int c = 1; c < chunks; ++c) t += pr[(size_t)c * N];
+        sums[(size_t)s * N + a] = t;
+    }
+}
+
 // vals (3, T): the jet ragged trunk's outputs by entry.  black (n NPt).  targets (n, M).  warped (n, M) and wgrad (2, n, M) may be null.
 // partials (n chunks, ALIGN_SUMS).  grid: n * chunks workgroups (slice-major), chunks = ceil(M / ALIGN_CHUNK)
 __global__ __launch_bounds__(256) void align_partial_kernel(const float* __restrict__ vals, const int* __restrict__ ent, const int* __restrict__ tile,
@@ -149,31 +181,12 @@ __global__ __launch_bounds__(256) void align_partial_kernel(const float* __restr
             }
         }
     }
-    // score_block_sum's order for all 29 at once: butterfly inside each wave, then the four wave totals in wave order
-#pragma unroll
-    for (int a = 0; a < ALIGN_SUMS; ++a) {
-        double v = acc[a];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((threadIdx.x & 63) == 0) red[a][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < ALIGN_SUMS) {
-        const int a = threadIdx.x;
-        partials[(size_t)blockIdx.x * ALIGN_SUMS + a] = ((red[a][0] + red[a][1]) + red[a][2]) + red[a][3];
-    }
+    align_block_reduce<ALIGN_SUMS>(acc, red, partials);
 }
 
 // sums[s, a] = the slice's partial records added in index order
 __global__ __launch_bounds__(256) void align_combine_kernel(const double* __restrict__ partials, double* __restrict__ sums, int chunks) {
-#pragma clang fp contract(off)
-    const int s = blockIdx.x, a = threadIdx.x;
-    if (a < ALIGN_SUMS) {
-        const double* pr = partials + (size_t)s * chunks * ALIGN_SUMS + a;
-        double t = pr[0];
-        for (int c = 1; c < chunks; ++c) t += pr[(size_t)c * ALIGN_SUMS];
-        sums[(size_t)s * ALIGN_SUMS + a] = t;
-    }
+    align_combine<ALIGN_SUMS>(partials, sums, chunks);
 }
 
 // ---- msiren_align_solve* (DESIGN.md section 5.11): the damped Gauss-Newton loop around the pipeline above -----------------------------------
@@ -210,50 +223,164 @@ __device__ __forceinline__ void align_rigid_map(double c, double s, double uY, d
     m[0] = (float)c, m[1] = (float)(-s), m[2] = (float)ty, m[3] = (float)s, m[4] = (float)c, m[5] = (float)tx;
 }
 
-// A = L D L^T without pivoting (the lower triangle and the diagonal of A are read), then the three substitutions.  A pivot that is not
-// positive and finite: x = 0, false.
+// A = L D L^T without pivoting, in place: the lower triangle and the diagonal of A are read, L is left over the strict lower triangle and D
+// over the diagonal; then the three substitutions.  A pivot that is not positive and finite: x = 0, false.  x may not alias b.
 template <int M>
-__device__ __forceinline__ bool align_ldl_solve(const double (&A)[M][M], const double (&b)[M], double (&x)[M]) {
+__device__ __forceinline__ bool align_ldl_solve(double (&A)[M][M], const double (&b)[M], double (&x)[M]) {
 #pragma clang fp contract(off)
-    double L[M][M], D[M], y[M];
     bool ok = true;
 #pragma unroll
     for (int j = 0; j < M; ++j) {
         double dj = A[j][j];
 #pragma unroll
         for (int k = 0; k < j; ++k) {
-            const double ll = L[j][k] * L[j][k];
-            dj = dj - ll * D[k];
+            const double ll = A[j][k] * A[j][k];
+            dj = dj - ll * A[k][k];
         }
         ok = ok && dj > 0.0 && dj < __builtin_inf();  // (false for a NaN)
-        D[j] = dj;
+        A[j][j] = dj;
 #pragma unroll
         for (int i = j + 1; i < M; ++i) {
             double v = A[i][j];
 #pragma unroll
             for (int k = 0; k < j; ++k) {
-                const double ll = L[i][k] * L[j][k];
-                v = v - ll * D[k];
+                const double ll = A[i][k] * A[j][k];
+                v = v - ll * A[k][k];
             }
-            L[i][j] = v / dj;
+            A[i][j] = v / dj;
         }
     }
 #pragma unroll
     for (int i = 0; i < M; ++i) {
-        y[i] = b[i];
+        x[i] = b[i];
 #pragma unroll
-        for (int k = 0; k < i; ++k) y[i] = y[i] - L[i][k] * y[k];
+        for (int k = 0; k < i; ++k) x[i] = x[i] - A[i][k] * x[k];
     }
 #pragma unroll
-    for (int i = 0; i < M; ++i) y[i] = y[i] / D[i];
+    for (int i = 0; i < M; ++i) x[i] = x[i] / A[i][i];
 #pragma unroll
     for (int i = M - 1; i >= 0; --i) {
 #pragma unroll
-        for (int k = i + 1; k < M; ++k) y[i] = y[i] - L[k][i] * y[k];
+        for (int k = i + 1; k < M; ++k) x[i] = x[i] - A[k][i] * x[k];
     }
 #pragma unroll
-    for (int i = 0; i < M; ++i) x[i] = ok ? y[i] : 0.0;
+    for (int i = 0; i < M; ++i) x[i] = ok ? x[i] : 0.0;
     return ok;
+}
+
+// The proposals of the step kernels over the leading P of the N parameters of (gradient gr, matrix H): N = 6, or 8 with the (gain, bias) pair
+// of align_w.hip.h behind the map's six.
+// the affine proposal: d = ldl_solve(H damped, -gr / 2), zero behind the leading P
+template <int P, int N>
+__device__ __forceinline__ bool align_propose_affine(const double (&H)[N][N], const double (&gr)[N], double lam, double (&d)[N]) {
+#pragma clang fp contract(off)
+    double A[P][P], rhs[P], x[P];
+#pragma unroll
+    for (int a = 0; a < P; ++a) {
+#pragma unroll
+        for (int b = 0; b < P; ++b) A[a][b] = H[a][b];
+        const double lh = lam * H[a][a];
+        A[a][a] = H[a][a] + lh;
+        rhs[a] = -0.5 * gr[a];
+    }
+    const bool ok = align_ldl_solve<P>(A, rhs, x);
+#pragma unroll
+    for (int a = 0; a < N; ++a) d[a] = 0.0;
+#pragma unroll
+    for (int a = 0; a < P; ++a) d[a] = x[a];
+    return ok;
+}
+
+// the rigid proposal: B (P x Q) = section 5.11's 6 x 3 block [then B[6][3] = B[7][4] = 1], Q = P - 3; g_Q = B^T gr, H_Q = B^T (H B), every sum
+// ascending from 0.0, zero entries included; d = ldl_solve(H_Q damped, -g_Q / 2) = (angle, uY, uX[, g, b])
+template <int P, int N>
+__device__ __forceinline__ bool align_propose_rigid(const double (&H)[N][N], const double (&gr)[N], double lam, double c, double sn, double cy, double cx,
+                                                    double (&d)[N - 3]) {
+#pragma clang fp contract(off)
+    constexpr int Q = P - 3;
+    double B[P][Q];
+#pragma unroll
+    for (int a = 0; a < P; ++a)
+#pragma unroll
+        for (int q = 0; q < Q; ++q) B[a][q] = 0.0;
+    {
+        const double scy = sn * cy, ccx = c * cx, ccy = c * cy, scx = sn * cx;
+        B[0][0] = -sn, B[1][0] = -c, B[2][0] = scy + ccx;
+        B[3][0] = c, B[4][0] = -sn, B[5][0] = -(ccy - scx);
+        B[2][1] = 1.0, B[5][2] = 1.0;
+        if (P == 8) B[P - 2][Q - 2] = 1.0, B[P - 1][Q - 1] = 1.0;
+    }
+    double gq[Q], T[P][Q], A[Q][Q], rhs[Q], x[Q];
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        double t = 0.0;
+#pragma unroll
+        for (int a = 0; a < P; ++a) {
+            const double bg = B[a][q] * gr[a];
+            t = t + bg;
+        }
+        gq[q] = t;
+    }
+#pragma unroll
+    for (int a = 0; a < P; ++a)
+#pragma unroll
+        for (int q = 0; q < Q; ++q) {
+            double t = 0.0;
+#pragma unroll
+            for (int b = 0; b < P; ++b) {
+                const double hb = H[a][b] * B[b][q];
+                t = t + hb;
+            }
+            T[a][q] = t;
+        }
+#pragma unroll
+    for (int q = 0; q < Q; ++q)
+#pragma unroll
+        for (int r = 0; r < Q; ++r) {
+            double t = 0.0;
+#pragma unroll
+            for (int a = 0; a < P; ++a) {
+                const double bt = B[a][q] * T[a][r];
+                t = t + bt;
+            }
+            A[q][r] = t;
+        }
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const double lh = lam * A[q][q];
+        A[q][q] = A[q][q] + lh;
+        rhs[q] = -0.5 * gq[q];
+    }
+    const bool ok = align_ldl_solve<Q>(A, rhs, x);
+#pragma unroll
+    for (int q = 0; q < N - 3; ++q) d[q] = 0.0;
+#pragma unroll
+    for (int q = 0; q < Q; ++q) d[q] = x[q];
+    return ok;
+}
+
+// DESIGN.md section 5.11's accept / reject / damping rule behind evaluation k, the device twin of mri_inr_amd/align.py: lm_decide, for all
+// three step kernels.  The first evaluation is accepted and sets mean_first; a lower mean is accepted, counted, and lowers lam; everything
+// else (a NaN included) is rejected and raises it.  An accepted mean becomes mean_best.
+__device__ __forceinline__ bool align_lm_decide(int k, double mean, double* mean_best, double* mean_first, double* lam, int* accepted, double down, double up,
+                                                double lam_min, double lam_max) {
+#pragma clang fp contract(off)
+    bool accept;
+    if (k == 0) {
+        accept = true;
+        *mean_first = mean;
+    } else if (mean < *mean_best) {  // (false for a NaN)
+        accept = true;
+        *accepted += 1;
+        const double x = *lam * down;
+        *lam = x > lam_min ? x : lam_min;
+    } else {
+        accept = false;
+        const double x = *lam * up;
+        *lam = x < lam_max ? x : lam_max;
+    }
+    if (accept) *mean_best = mean;
+    return accept;
 }
 
 // before the first evaluation: trial := best := the input (rigid: the map of the input state), lam := damping, nothing accepted
@@ -305,24 +432,10 @@ __global__ __launch_bounds__(256) void align_step_kernel(AlignSolveParams p) {
         tr[6] = cost, tr[7] = count;
     }
     const double mean = count >= 6.0 ? cost / count : inf;
-    bool accept;
-    if (p.k == 0) {
-        accept = true;
-        mean_first = mean;
-    } else if (mean < mean_best) {  // (false for a NaN)
-        accept = true;
-        accepted += 1;
-        const double x = lam * p.down;
-        lam = x > p.lam_min ? x : p.lam_min;
-    } else {
-        accept = false;
-        const double x = lam * p.up;
-        lam = x < p.lam_max ? x : p.lam_max;
-    }
+    const bool accept = align_lm_decide(p.k, mean, &mean_best, &mean_first, &lam, &accepted, p.down, p.up, p.lam_min, p.lam_max);
 #pragma unroll
     for (int a = 0; a < ALIGN_SUMS; ++a) bs[a] = accept ? ev[a] : p.sums_best[(size_t)s * ALIGN_SUMS + a];
     if (accept) {
-        mean_best = mean;
 #pragma unroll
         for (int a = 0; a < 6; ++a) best[a] = trial[a];
 #pragma unroll
@@ -342,73 +455,19 @@ __global__ __launch_bounds__(256) void align_step_kernel(AlignSolveParams p) {
 #pragma unroll
             for (int b = a; b < 6; ++b, ++q) H[a][b] = bs[q], H[b][a] = bs[q];
     }
+    double gr[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) gr[a] = bs[2 + a];
     bool ok;
     if (p.mode == 0) {
-        double A[6][6], rhs[6], d[6];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int b = 0; b < 6; ++b) A[a][b] = H[a][b];
-            const double lh = lam * H[a][a];
-            A[a][a] = H[a][a] + lh;
-            rhs[a] = -0.5 * bs[2 + a];
-        }
-        ok = align_ldl_solve<6>(A, rhs, d);
+        double d[6];
+        ok = align_propose_affine<6>(H, gr, lam, d);
 #pragma unroll
         for (int a = 0; a < 6; ++a) trial[a] = (float)((double)best[a] + d[a]);
     } else {
         const double c = rb[0], sn = rb[1], uY = rb[2], uX = rb[3], cy = p.cy, cx = p.cx;
-        double B[6][3];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) B[a][0] = 0.0, B[a][1] = 0.0, B[a][2] = 0.0;
-        {
-            const double scy = sn * cy, ccx = c * cx, ccy = c * cy, scx = sn * cx;
-            B[0][0] = -sn, B[1][0] = -c, B[2][0] = scy + ccx;
-            B[3][0] = c, B[4][0] = -sn, B[5][0] = -(ccy - scx);
-            B[2][1] = 1.0, B[5][2] = 1.0;
-        }
-        double g3[3], T[6][3], A[3][3], rhs[3], d[3];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            double t = 0.0;
-#pragma unroll
-            for (int a = 0; a < 6; ++a) {
-                const double bg = B[a][q] * bs[2 + a];
-                t = t + bg;
-            }
-            g3[q] = t;
-        }
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                double t = 0.0;
-#pragma unroll
-                for (int b = 0; b < 6; ++b) {
-                    const double hb = H[a][b] * B[b][q];
-                    t = t + hb;
-                }
-                T[a][q] = t;
-            }
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                double t = 0.0;
-#pragma unroll
-                for (int a = 0; a < 6; ++a) {
-                    const double bt = B[a][q] * T[a][r];
-                    t = t + bt;
-                }
-                A[q][r] = t;
-            }
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const double lh = lam * A[q][q];
-            A[q][q] = A[q][q] + lh;
-            rhs[q] = -0.5 * g3[q];
-        }
-        ok = align_ldl_solve<3>(A, rhs, d);
+        double d[3];
+        ok = align_propose_rigid<6>(H, gr, lam, c, sn, cy, cx, d);
         const double u = d[0] / 2.0, uu = u * u, den = 1.0 + uu;
         const double cd = (1.0 - uu) / den, sd = (2.0 * u) / den;
         const double ccd = c * cd, ssd = sn * sd, scd = sn * cd, csd = c * sd;

@@ -1,0 +1,86 @@
+// Scratch layouts and size limits of the geometry calls (plain C++, no HIP: unit-tested on the CPU by tests/test_align_plan.py): the five
+// pipelines of resample.hip -- resample, resample-volume, align, align-w, align-volume -- and the state of the three solves.  Every call
+// carves one block of its stream's scratch, in this order, offsets in bytes:
+//     [counts B][cursors B][offsets B + 1][items B + 1][ent E][tile S][pair P]  ints, padded to an even count
+//     [coords 2 E][w S][f P]                                                    floats; coords are float2: 8-byte aligned
+//     [partials R records of `nsums` doubles]                                   behind the floats padded to an even count (align forms)
+//     [solve state]                                                             behind the partials (solve_layout)
+// B bins, E entries (what the ragged trunk evaluates), S slots (tile and fold weight), P points (pair of slices and fraction):
+//     resample          B = nV nH      E = S = M K             P = 0          (M points, K = KA KA covering tiles at most)
+//     resample-volume   B = n nV nH    E = 2 M K, S = M K      P = M
+//     align, align-w    B = n nV nH    E = S = n th tw K       P = 0          R = n chunks, chunks = ceil(th tw / 1024), 29 / 47 sums
+//     align-volume      B = n nV nH    E = 2 M K, S = M K      P = M = m th tw, R = m chunks, 56 sums
+// The memset in front of the count kernel covers counts and cursors: zero_bytes.  The limits keep every buffer of a call below 2^31 bytes and
+// every index in 32 bits; the bin scratch over the points and over the bins stays below 2^30 each.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace msiren {
+
+constexpr int64_t kAlignChunk = 1024;  // pixels per partial record (align.hip.h: ALIGN_CHUNK)
+inline int64_t align_chunks(int64_t Mt) { return (Mt + kAlignChunk - 1) / kAlignChunk; }
+
+struct GeomLayout {
+    size_t counts, cursors, offsets, items, ent, tile, pair, coords, w, f, partials;  // partials: where they would start, also without any
+    size_t zero_bytes;  // counts and cursors
+    size_t total;       // bins + partials: what follows is the solve's
+};
+
+inline GeomLayout geom_layout(int64_t bins, int64_t entries, int64_t slots, int64_t points, int64_t records = 0, int nsums = 0) {
+    const size_t B = (size_t)bins, E = (size_t)entries, S = (size_t)slots, P = (size_t)points;
+    const size_t nint = (4 * B + 2 + E + S + P + 1) & ~(size_t)1, nflt = 2 * E + S + P;
+    GeomLayout l{};
+    l.counts = 0, l.cursors = 4 * B, l.offsets = 4 * (2 * B), l.items = 4 * (3 * B + 1), l.ent = 4 * (4 * B + 2);
+    l.tile = l.ent + 4 * E, l.pair = l.tile + 4 * S;
+    l.coords = 4 * nint, l.w = l.coords + 4 * (2 * E), l.f = l.w + 4 * S;
+    l.partials = 4 * (nint + ((nflt + 1) & ~(size_t)1));
+    l.zero_bytes = 2 * B * sizeof(int);
+    l.total = records ? l.partials + (size_t)records * nsums * sizeof(double) : 4 * (nint + nflt);
+    return l;
+}
+inline GeomLayout resample_layout(int64_t NPt, int64_t M, int K) { return geom_layout(NPt, M * K, M * K, 0); }
+inline GeomLayout resample_volume_layout(int64_t NP, int64_t M, int K) { return geom_layout(NP, 2 * M * K, M * K, M); }
+inline GeomLayout align_layout(int64_t NP, int64_t n, int64_t Mt, int K, int nsums) {
+    return geom_layout(NP, n * Mt * K, n * Mt * K, 0, n * align_chunks(Mt), nsums);
+}
+inline GeomLayout align_volume_layout(int64_t NP, int64_t m, int64_t Mt, int K, int nsums) {
+    return geom_layout(NP, 2 * m * Mt * K, m * Mt * K, m * Mt, m * align_chunks(Mt), nsums);
+}
+
+// A solve's state per unit (slice or target) behind `base` = GeomLayout::total, a multiple of 8: the doubles, then the 4-byte words.
+//     [sums u nsums][sums_best u nsums][rigid_trial u nrigid][rigid_best u nrigid][scal u 3] [trial u nmap][best u nmap][gb_trial u 2][gb_best u 2][cnt u 2]
+// align: (29, 4, 6), align-w: (47, 4, 6) with the (gain, bias) pair, align-volume: (56, 12, 9)
+struct SolveLayout {
+    size_t sums, sums_best, rigid_trial, rigid_best, scal, trial, best, gb_trial, gb_best, cnt;  // gb_*: = cnt without the pair
+    size_t total;  // from the start of the scratch
+};
+inline SolveLayout solve_layout(size_t base, int64_t units, int nsums, int nrigid, int nmap, bool gb) {
+    const size_t u = (size_t)units;
+    SolveLayout s{};
+    s.sums = base, s.sums_best = s.sums + 8 * u * nsums, s.rigid_trial = s.sums_best + 8 * u * nsums, s.rigid_best = s.rigid_trial + 8 * u * nrigid;
+    s.scal = s.rigid_best + 8 * u * nrigid;
+    s.trial = s.scal + 8 * u * 3, s.best = s.trial + 4 * u * nmap, s.gb_trial = s.best + 4 * u * nmap, s.gb_best = s.gb_trial + (gb ? 4 * u * 2 : 0);
+    s.cnt = s.gb_best + (gb ? 4 * u * 2 : 0);
+    s.total = s.cnt + 4 * u * 2;
+    return s;
+}
+
+// The limits: true = the call fits.  NPt = nV nH tiles per slice.
+inline bool resample_fits(int64_t n, int64_t M, int K, int64_t NPt) {  // the entries' coordinates (8 bytes each), the trunk's three planes
+    return !(M > 0x0fffffffLL || n > 0x0fffffffLL || M * K * 8 > 0x7fffffffLL || n * M * K * 12 > 0x7fffffffLL || n * NPt > 0x3fffffffLL);
+}
+// 2 M K entries (slot and 8 bytes of coordinates), tile and weight per M K, pair and fraction per M: 32 M K + 8 M bytes
+inline bool volume_points_fit(int64_t M, int K) { return !(M > 0x0fffffffLL || 32 * M * K + 8 * M > 0x3fffffffLL); }
+inline bool bins_fit(int64_t n, int64_t NPt) { return !(16 * n * NPt > 0x3fffffffLL); }                       // 16 bytes per bin
+inline bool volume_slices_fit(int64_t n, int64_t NPt) { return !(n > 0x00ffffffLL) && bins_fit(n, NPt); }  // n is compared as an fp32 integer
+// 20 bytes per entry (slot, tile, weight, 8 bytes of coordinates) and one record per chunk; the trunk's three planes are 12 T bytes
+inline bool align_pixels_fit(int64_t n, int64_t Mt, int K, int nsums) {
+    return !(n > 0x00ffffffLL || Mt > 0x0fffffffLL || n * Mt > 0x0fffffffLL || 20 * n * Mt * K + 8 * nsums * n * align_chunks(Mt) > 0x3fffffffLL);
+}
+// resample-volume's bytes over M = m th tw pixels and one record per chunk; the trunk's three planes are 24 M K bytes
+inline bool align_volume_pixels_fit(int64_t m, int64_t Mt, int K, int nsums) {
+    return !(Mt > 0x0fffffffLL || m > 0x0fffffffLL || m * Mt > 0x0fffffffLL || 32 * m * Mt * K + 8 * m * Mt + 8 * nsums * m * align_chunks(Mt) > 0x3fffffffLL);
+}
+
+}  // namespace msiren

@@ -178,31 +178,12 @@ __global__ __launch_bounds__(256) void align_volume_partial_kernel(const float* 
             }
         }
     }
-    // score_block_sum's order for all 56 at once: butterfly inside each wave, then the four wave totals in wave order
-#pragma unroll
-    for (int a = 0; a < ALIGN_VOLUME_SUMS; ++a) {
-        double v = acc[a];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((threadIdx.x & 63) == 0) red[a][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < ALIGN_VOLUME_SUMS) {
-        const int a = threadIdx.x;
-        partials[(size_t)blockIdx.x * ALIGN_VOLUME_SUMS + a] = ((red[a][0] + red[a][1]) + red[a][2]) + red[a][3];
-    }
+    align_block_reduce<ALIGN_VOLUME_SUMS>(acc, red, partials);
 }
 
 // sums[q, a] = the target's partial records added in index order
 __global__ __launch_bounds__(256) void align_volume_combine_kernel(const double* __restrict__ partials, double* __restrict__ sums, int chunks) {
-#pragma clang fp contract(off)
-    const int q = blockIdx.x, a = threadIdx.x;
-    if (a < ALIGN_VOLUME_SUMS) {
-        const double* pr = partials + (size_t)q * chunks * ALIGN_VOLUME_SUMS + a;
-        double t = pr[0];
-        for (int c = 1; c < chunks; ++c) t += pr[(size_t)c * ALIGN_VOLUME_SUMS];
-        sums[(size_t)q * ALIGN_VOLUME_SUMS + a] = t;
-    }
+    align_combine<ALIGN_VOLUME_SUMS>(partials, sums, chunks);
 }
 
 // ---- msiren_align_volume_solve* (DESIGN.md section 5.13): section 5.11's damped Gauss-Newton loop around the pipeline above --------------------
@@ -211,8 +192,8 @@ __global__ __launch_bounds__(256) void align_volume_combine_kernel(const double*
 //     rigid_trial, rigid_best     (Rot 9 row-major, u 3) fp64 each (rigid mode)
 //     sums_best (56 fp64)         the sums at the best map;  scal = (mean_best, mean_first, lam);  cnt = (accepted, flags)
 // The rule is restated by mri_inr_amd/align_volume.py: lm_step_v -- fp64 + - * / one at a time (contraction off), every sum in the order written
-// there.  The step kernel is instantiated per mode, so each instantiation carries one system; the LDL^T factorisation works in place on the
-// lower triangle.  Every loop has constant bounds and is unrolled: nothing is indexed at run time.  Plain stores, no atomics.
+// there.  The step kernel is instantiated per mode, so each instantiation carries one system (align_ldl_solve factorises it in place).
+// Every loop has constant bounds and is unrolled: nothing is indexed at run time.  Plain stores, no atomics.
 constexpr int ALIGN_VOLUME_AFFINE = 0, ALIGN_VOLUME_RIGID = 1;
 
 struct AlignVolumeSolveParams {
@@ -267,50 +248,6 @@ __device__ __forceinline__ void align_rigid_map3(const double (&st)[12], const d
         if (r == 0) mp[0] = (float)(vi[0] / spacing), mp[1] = (float)(vj[0] / spacing), mp[2] = (float)(t / spacing);
         else mp[3 * r] = (float)vi[r], mp[3 * r + 1] = (float)vj[r], mp[3 * r + 2] = (float)t;
     }
-}
-
-// align_ldl_solve's operations in the same order, L over the strict lower triangle of A and D over its diagonal; x may not alias b
-template <int M>
-__device__ __forceinline__ bool align_ldl_solve_inplace(double (&A)[M][M], const double (&b)[M], double (&x)[M]) {
-#pragma clang fp contract(off)
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-        double dj = A[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) {
-            const double ll = A[j][k] * A[j][k];
-            dj = dj - ll * A[k][k];
-        }
-        ok = ok && dj > 0.0 && dj < __builtin_inf();  // (false for a NaN)
-        A[j][j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < M; ++i) {
-            double v = A[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) {
-                const double ll = A[i][k] * A[j][k];
-                v = v - ll * A[k][k];
-            }
-            A[i][j] = v / dj;
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-        x[i] = b[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) x[i] = x[i] - A[i][k] * x[k];
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) x[i] = x[i] / A[i][i];
-#pragma unroll
-    for (int i = M - 1; i >= 0; --i) {
-#pragma unroll
-        for (int k = i + 1; k < M; ++k) x[i] = x[i] - A[k][i] * x[k];
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) x[i] = ok ? x[i] : 0.0;
-    return ok;
 }
 
 // before the first evaluation: trial := best := the input (rigid: the map of the input state), lam := damping, nothing accepted
@@ -369,22 +306,8 @@ __global__ __launch_bounds__(256) void align_volume_step_kernel(AlignVolumeSolve
         }
     }
     const double mean = count >= (double)P ? cost / count : inf;
-    bool accept;
-    if (p.k == 0) {
-        accept = true;
-        mean_first = mean;
-    } else if (mean < mean_best) {  // (false for a NaN)
-        accept = true;
-        accepted += 1;
-        const double x = lam * p.down;
-        lam = x > p.lam_min ? x : p.lam_min;
-    } else {
-        accept = false;
-        const double x = lam * p.up;
-        lam = x < p.lam_max ? x : p.lam_max;
-    }
+    const bool accept = align_lm_decide(p.k, mean, &mean_best, &mean_first, &lam, &accepted, p.down, p.up, p.lam_min, p.lam_max);
     if (accept) {  // best := trial, in the state
-        mean_best = mean;
 #pragma unroll
         for (int a = 0; a < ALIGN_VOLUME_SUMS; ++a) p.sums_best[(size_t)q * ALIGN_VOLUME_SUMS + a] = ev[a];
 #pragma unroll
@@ -415,7 +338,7 @@ __global__ __launch_bounds__(256) void align_volume_step_kernel(AlignVolumeSolve
             A[a][a] = h + lh;
             rhs[a] = -0.5 * bs[2 + a];
         }
-        ok = align_ldl_solve_inplace<9>(A, rhs, d);
+        ok = align_ldl_solve<9>(A, rhs, d);
 #pragma unroll
         for (int a = 0; a < 9; ++a) trial[a] = (float)((double)p.best[(size_t)q * 9 + a] + d[a]);
     } else {
@@ -491,7 +414,7 @@ __global__ __launch_bounds__(256) void align_volume_step_kernel(AlignVolumeSolve
             const double lh = lam * A[k][k];
             A[k][k] = A[k][k] + lh;
         }
-        ok = align_ldl_solve_inplace<6>(A, rhs, d);
+        ok = align_ldl_solve<6>(A, rhs, d);
         __asm__ volatile("" ::: "memory");
         // Cayley: a = d[0:3] / 2, Cay = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a);  Rot' = Cay Rot, u' = u + d[3:6]
         const double a0 = d[0] / 2.0, a1 = d[1] / 2.0, a2 = d[2] / 2.0;

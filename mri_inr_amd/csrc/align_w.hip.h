@@ -72,31 +72,12 @@ __global__ __launch_bounds__(256) void align_partial_w_kernel(const float* __res
             }
         }
     }
-    // score_block_sum's order for all 47 at once: butterfly inside each wave, then the four wave totals in wave order
-#pragma unroll
-    for (int a = 0; a < ALIGN_SUMS_W; ++a) {
-        double v = acc[a];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-        if ((threadIdx.x & 63) == 0) red[a][threadIdx.x >> 6] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < ALIGN_SUMS_W) {
-        const int a = threadIdx.x;
-        partials[(size_t)blockIdx.x * ALIGN_SUMS_W + a] = ((red[a][0] + red[a][1]) + red[a][2]) + red[a][3];
-    }
+    align_block_reduce<ALIGN_SUMS_W>(acc, red, partials);
 }
 
 // sums[s, a] = the slice's partial records added in index order
 __global__ __launch_bounds__(256) void align_combine_w_kernel(const double* __restrict__ partials, double* __restrict__ sums, int chunks) {
-#pragma clang fp contract(off)
-    const int s = blockIdx.x, a = threadIdx.x;
-    if (a < ALIGN_SUMS_W) {
-        const double* pr = partials + (size_t)s * chunks * ALIGN_SUMS_W + a;
-        double t = pr[0];
-        for (int c = 1; c < chunks; ++c) t += pr[(size_t)c * ALIGN_SUMS_W];
-        sums[(size_t)s * ALIGN_SUMS_W + a] = t;
-    }
+    align_combine<ALIGN_SUMS_W>(partials, sums, chunks);
 }
 
 // ---- msiren_align_solve_w* (DESIGN.md section 5.12): section 5.11's loop on the 47 sums ------------------------------------------------------
@@ -148,95 +129,6 @@ __global__ __launch_bounds__(256) void align_solve_init_w_kernel(AlignSolveWPara
     p.cnt[(size_t)s * 2] = 0, p.cnt[(size_t)s * 2 + 1] = 0;
 }
 
-// the affine proposal over the leading P parameters of (gradient gr, matrix H): d = ldl_solve(H damped, -gr / 2)
-template <int P>
-__device__ __forceinline__ bool align_propose_affine(const double (&H)[8][8], const double (&gr)[8], double lam, double (&d)[8]) {
-#pragma clang fp contract(off)
-    double A[P][P], rhs[P], x[P];
-#pragma unroll
-    for (int a = 0; a < P; ++a) {
-#pragma unroll
-        for (int b = 0; b < P; ++b) A[a][b] = H[a][b];
-        const double lh = lam * H[a][a];
-        A[a][a] = H[a][a] + lh;
-        rhs[a] = -0.5 * gr[a];
-    }
-    const bool ok = align_ldl_solve<P>(A, rhs, x);
-#pragma unroll
-    for (int a = 0; a < 8; ++a) d[a] = 0.0;
-#pragma unroll
-    for (int a = 0; a < P; ++a) d[a] = x[a];
-    return ok;
-}
-
-// the rigid proposal: B (P x Q) = section 5.11's 6 x 3 block [then B[6][3] = B[7][4] = 1], Q = P - 3; g_Q = B^T gr, H_Q = B^T (H B), every sum
-// ascending from 0.0, zero entries included; d = ldl_solve(H_Q damped, -g_Q / 2) = (angle, uY, uX[, g, b])
-template <int P>
-__device__ __forceinline__ bool align_propose_rigid(const double (&H)[8][8], const double (&gr)[8], double lam, double c, double sn, double cy, double cx,
-                                                    double (&d)[5]) {
-#pragma clang fp contract(off)
-    constexpr int Q = P - 3;
-    double B[P][Q];
-#pragma unroll
-    for (int a = 0; a < P; ++a)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) B[a][q] = 0.0;
-    {
-        const double scy = sn * cy, ccx = c * cx, ccy = c * cy, scx = sn * cx;
-        B[0][0] = -sn, B[1][0] = -c, B[2][0] = scy + ccx;
-        B[3][0] = c, B[4][0] = -sn, B[5][0] = -(ccy - scx);
-        B[2][1] = 1.0, B[5][2] = 1.0;
-        if (P == 8) B[P - 2][Q - 2] = 1.0, B[P - 1][Q - 1] = 1.0;
-    }
-    double gq[Q], T[P][Q], A[Q][Q], rhs[Q], x[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        double t = 0.0;
-#pragma unroll
-        for (int a = 0; a < P; ++a) {
-            const double bg = B[a][q] * gr[a];
-            t = t + bg;
-        }
-        gq[q] = t;
-    }
-#pragma unroll
-    for (int a = 0; a < P; ++a)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            double t = 0.0;
-#pragma unroll
-            for (int b = 0; b < P; ++b) {
-                const double hb = H[a][b] * B[b][q];
-                t = t + hb;
-            }
-            T[a][q] = t;
-        }
-#pragma unroll
-    for (int q = 0; q < Q; ++q)
-#pragma unroll
-        for (int r = 0; r < Q; ++r) {
-            double t = 0.0;
-#pragma unroll
-            for (int a = 0; a < P; ++a) {
-                const double bt = B[a][q] * T[a][r];
-                t = t + bt;
-            }
-            A[q][r] = t;
-        }
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        const double lh = lam * A[q][q];
-        A[q][q] = A[q][q] + lh;
-        rhs[q] = -0.5 * gq[q];
-    }
-    const bool ok = align_ldl_solve<Q>(A, rhs, x);
-#pragma unroll
-    for (int q = 0; q < 5; ++q) d[q] = 0.0;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) d[q] = x[q];
-    return ok;
-}
-
 // behind evaluation k: accept or reject the trial, then propose the next one from the best state.  grid: ceil(n / 256) workgroups of 256
 __global__ __launch_bounds__(256) void align_step_w_kernel(AlignSolveWParams p) {
 #pragma clang fp contract(off)
@@ -263,24 +155,10 @@ __global__ __launch_bounds__(256) void align_step_w_kernel(AlignSolveWParams p) 
     }
     const double solved = (double)((p.mode == 1 ? 3 : 6) + (p.estimate ? 2 : 0));
     const double mean = count >= solved ? cost / wsum : inf;
-    bool accept;
-    if (p.k == 0) {
-        accept = true;
-        mean_first = mean;
-    } else if (mean < mean_best) {  // (false for a NaN)
-        accept = true;
-        accepted += 1;
-        const double x = lam * p.down;
-        lam = x > p.lam_min ? x : p.lam_min;
-    } else {
-        accept = false;
-        const double x = lam * p.up;
-        lam = x < p.lam_max ? x : p.lam_max;
-    }
+    const bool accept = align_lm_decide(p.k, mean, &mean_best, &mean_first, &lam, &accepted, p.down, p.up, p.lam_min, p.lam_max);
 #pragma unroll
     for (int a = 0; a < ALIGN_SUMS_W; ++a) bs[a] = accept ? ev[a] : p.sums_best[(size_t)s * ALIGN_SUMS_W + a];
     if (accept) {
-        mean_best = mean;
 #pragma unroll
         for (int a = 0; a < 6; ++a) best[a] = trial[a];
         gbb[0] = gbt[0], gbb[1] = gbt[1];

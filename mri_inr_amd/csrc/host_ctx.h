@@ -1,7 +1,8 @@
 // Shared by the host translation units of libmsiren.so (round 6: the former 3 000-line msiren.hip, cut by responsibility):
 //     msiren.hip           C ABI: lifecycle, weights, the forward / slice entry points on host pointers, memory, timing, info
 //     dispatch.h           which kernel runs for which model and call: pure functions, no HIP (tests/test_dispatch.py)
-//     launch_dispatch.hip  the launches of what dispatch.h picks: trunks, prologue, tiling / fold, the *_dev slice pipeline
+//     launch_dispatch.hip  the launches of what dispatch.h picks: trunks, prologue, tiling / fold, the *_dev slice pipeline and its
+//                          prologue (slice_prologue: what the geometry calls of resample.hip start with)
 //     trunk_instances.h    the one list of kernel instances: k_*.hip instantiate it, the host units declare it extern
 //     weights_pack.hip     state_dict -> the kernels' weight layouts (host arithmetic + uploads)
 //     host_buffers.hip     what a caller's host range is (pageable / page-locked / page-locked in part), bounce buffers, and the one
@@ -18,7 +19,10 @@
 //                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h), msiren_align_slices* (slices scored
 //                          under affine maps against targets; align.hip.h), msiren_align_solve* (the damped Gauss-Newton loop around it),
 //                          msiren_align_slices_w* / msiren_align_solve_w* (the two with a per-pixel weight and a per-slice gain and bias; align_w.hip.h),
-//                          msiren_align_volume* / msiren_align_volume_solve* (target slices against the stack read as a volume, 3 x 3 maps; align_volume.hip.h)
+//                          msiren_align_volume* / msiren_align_volume_solve* (target slices against the stack read as a volume, 3 x 3 maps; align_volume.hip.h).
+//                          The whole of these families lives here: checks, pipelines on the call's stream, host-pointer forms, entry points,
+//                          and the only inclusion of their five kernel headers
+//     align_plan.h         the scratch layouts and size limits of those calls: pure functions, no HIP (tests/test_align_plan.py)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -227,6 +231,12 @@ int forward_latent_dev(msiren_ctx* h, const Call& c, const float* z_dev, int64_t
 int forward_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t B, float* out_dev);
 int reconstruct_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, float* recon_dev, const OutGeom* og = nullptr,
                        const GradOut* go = nullptr);  // go: recon_dev may be null
+int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
+int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
+// what every slice call runs in front of its trunk: tiling -> black flags -> plan -> the handle's prologue over the kept tiles.  Leaves the
+// flags in sc.keep, the plan in sc.plan, the kept tiles' modulations in sc.mods; *pc: the call with the plan attached
+int slice_prologue(msiren_ctx* h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw, const float* patches_ro, int64_t n,
+                   int32_t nV, int32_t nH, Call* pc, bool* fused_out);
 int jet_supported(msiren_ctx* h);  // 0, or MSIREN_E_INVALID: dim_hidden > 256 / residual (what the jet trunk does not take)
 int launch_trunk_f32_jet(msiren_ctx* h, const Call& c, const float* mods_dev, int64_t B, float* out_dev /* may be null */, float* grad_dev, float gscale);
 
@@ -244,6 +254,7 @@ int launch_trunk_f32_jet_ragged(msiren_ctx* h, const Call& c, const RaggedSet& r
 // (siren_trunk_f32_ragged_cond_kernel); on every other handle launch_trunk_f32_ragged, bit for bit.  items: NP + 1 words as above.
 int launch_trunk_ragged_native(msiren_ctx* h, const Call& c, const RaggedSet& r, const float* mods_dev, float* out_dev /* (reps, T) */);
 
+// resample.hip: the geometry pipelines behind the slice prologue, on h->sc[c.stream].s; their scratch layouts and limits: align_plan.h
 // the reconstruction of n slices at M points shared by them (resample.hip.h); grad: out_dev may be null, grad_dev (2, n, M)
 int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad);  // 0, or MSIREN_E_INVALID: the model, or too many points
 int resample_slices(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M, float* out_dev,
@@ -288,8 +299,6 @@ int align_volume_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t w
 int align_volume_solve(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
                        int32_t tw, const msiren_align_volume_solve_opts* o, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out,
                        double* rigid_out, double* report, double* trace);
-int reconstruct_tiles_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom* og = nullptr);
-int weighted_fold_dev(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t n, int32_t nV, int32_t nH, float* recon_dev, const OutGeom& og);
 
 // sample_grid.hip
 // the call evaluates and folds the lattice of out_stride (built on first use); table = false: without the 16-bit trunks' layer-0 table

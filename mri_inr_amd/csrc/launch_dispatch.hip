@@ -18,11 +18,6 @@
 #include "siren_trunk_x1n.hip.h"
 #include "siren_trunk_x1w.hip.h"
 #include "tiling.hip.h"
-#include "resample.hip.h"
-#include "resample_volume.hip.h"
-#include "align.hip.h"
-#include "align_w.hip.h"
-#include "align_volume.hip.h"
 #include "launch_dispatch.h"
 
 namespace msiren {  // the trunk / prologue kernels are compiled in their own translation units (k_*.hip)
@@ -878,8 +873,8 @@ namespace mh {
 // What every slice call runs in front of its trunk: tiling -> black flags -> device-side plan -> the handle's prologue over the kept tiles.
 // Leaves the black flags in sc.keep, the plan in sc.plan, the kept tiles' modulations in sc.mods; *pc: the call with the plan attached.
 // `images_dev` given: `patches_rw` is scratch that image_to_patches fills; null: `patches_ro` are the caller's tiles
-static int slice_prologue(msiren_handle h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw, const float* patches_ro,
-                          int64_t n, int32_t nV, int32_t nH, Call* pc, bool* fused_out) {
+int slice_prologue(msiren_handle h, const Call& c, const float* images_dev, int32_t height, int32_t width, float* patches_rw, const float* patches_ro,
+                   int64_t n, int32_t nV, int32_t nH, Call* pc, bool* fused_out) {
     int rc;
     auto& sc = h->sc[c.stream];
     const int64_t NP = n * nV * nH;
@@ -974,605 +969,6 @@ int reconstruct_slices(msiren_handle h, const Call& c, const float* images_dev, 
     auto& sc = h->sc[c.stream];
     if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float)))) return rc;
     return reconstruct_tiles(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, recon_dev, og, go);
-}
-
-// The reconstruction at arbitrary points (kernels: resample.hip.h): the slice prologue, then on the same stream
-// bin the points by covering tile -> ragged exact-fp32 trunk (`native`: the handle's own, launch_trunk_ragged_native), replicated over the
-// slices, patch s NP + t on the plan's row -> blend.
-// `grad`: value (out_dev may be null) and the two gradient planes grad_dev (2, n, M), per reconstruction pixel.
-int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad) {
-    int rc;
-    if (grad ? (rc = jet_supported(h)) : 0) return rc;
-    if (n < 0 || M < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, M=%lld)", (long long)n, (long long)M);
-    if ((rc = check_tile_size(h, false))) return rc;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    if (KA > msiren::RESAMPLE_MAX_KA)
-        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
-    int32_t nV, nH;
-    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
-    // every buffer of the call below 2^31 bytes, every index in 32 bits: the entries' coordinates (8 bytes each), the trunk's three planes
-    if (M > 0x0fffffffLL || n > 0x0fffffffLL || M * K * 8 > 0x7fffffffLL || n * M * K * 12 > 0x7fffffffLL || n * nV * nH > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many points for one call: %lld points x %d covering tiles x %lld slices (8 M K and 12 n M K must stay below 2^31)",
-                    (long long)M, K, (long long)n);
-    return 0;
-}
-
-int resample_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M,
-                    float* out_dev, float* grad_dev, bool grad, bool native) {
-    int rc = resample_check(h, n, height, width, M, grad);
-    if (rc) return rc;
-    if (n > 0 && M > 0 && (!images_dev || !points_dev || (grad ? !grad_dev : !out_dev))) return fail(MSIREN_E_INVALID, "null argument");
-    if (n == 0 || M == 0) return 0;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    int32_t nV, nH;
-    (void)msiren_recon_shape(h, height, width, &nV, &nH);
-    const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, T = M * K;
-    if ((rc = check_pairs_aligned(points_dev, "points")) || (rc = check_reflect_padding(h, height, width))) return rc;
-    auto& sc = h->sc[c.stream];
-    // bins in the stream's scratch: [counts NPt][cursors NPt][offsets NPt + 1][items NPt + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T]
-    const size_t nint = (size_t)(4 * NPt + 2 + 2 * T + 1) & ~(size_t)1;
-    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, (nint + 3 * (size_t)T) * 4)) ||
-        (rc = ensure(h, sc.rec, (size_t)n * T * sizeof(float) * (grad ? 3 : 1))))
-        return rc;
-    Call pc;
-    bool fused;
-    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &pc, &fused))) return rc;
-    hipStream_t st = sc.s;
-    int* const ib = (int*)sc.ragged.p;
-    msiren::ResampleParams rp{points_dev, (int)M, nV, nH, h->S, h->I, (h->S - h->I) / 2, KA};
-    rp.counts = ib, rp.cursors = ib + NPt, rp.offsets = ib + 2 * NPt;
-    int* const items = rp.offsets + NPt + 1;
-    rp.ent = items + NPt + 1, rp.tile = rp.ent + T, rp.coords = (float*)(ib + nint), rp.w = rp.coords + 2 * T;
-    const unsigned gm = (unsigned)((M + 255) / 256);
-    hipEvent_t e1 = nullptr;
-    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-    HIPCHK(hipMemsetAsync(ib, 0, (size_t)2 * NPt * sizeof(int), st));
-    hipLaunchKernelGGL(msiren::resample_count_kernel, dim3(gm), dim3(256), 0, st, rp);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, rp.counts, (int)NPt, rp.offsets);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::resample_fill_kernel, dim3(gm), dim3(256), 0, st, rp);
-    HIPCHK(hipGetLastError());
-    if ((rc = profile_end(h, c.stream, e1, M, "resample_bin_kernels"))) return rc;
-    float* const rec = (float*)sc.rec.p;  // [value (n, T)][d/d row][d/d column]
-    const int* plan = (const int*)sc.plan.p;
-    const RaggedSet r{rp.coords, rp.offsets, T, NPt, n, plan + 2 + NP, NP, items};
-    const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
-    if (grad) rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, out_dev ? rec : nullptr, rec + (size_t)n * T, gscale);
-    else rc = native ? launch_trunk_ragged_native(h, pc, r, (const float*)sc.mods.p, rec) : launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
-    if (rc || (rc = profile_begin(h, c.stream, &e1))) return rc;
-    const unsigned gb = (unsigned)((n * M + 255) / 256);
-    if (out_dev) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, out_dev, (int)n, (int)M, K, (int)NPt, (int)T, 1);
-    if (grad) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec + (size_t)n * T, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, grad_dev, (int)n, (int)M, K, (int)NPt, (int)T, 2);
-    HIPCHK(hipGetLastError());
-    return profile_end(h, c.stream, e1, n * M, "resample_blend_kernel");
-}
-
-// A stack of slices read as a volume at points (Z, Y, X) (kernels: resample_volume.hip.h): the slice prologue, then on
-// the same stream bin the points by (slice, tile) -> the ragged trunk over those n nV nH bins as its patches, one replica, on the plan's rows
-// (`native`: launch_trunk_ragged_native) -> blend across tiles and the pair of slices.  Scratch grows with 2 M K, not with n.
-// `grad`: value (out_dev may be null) and the three gradient planes grad_dev (3, M): per slice of Z, per reconstruction pixel rows, columns.
-int resample_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad) {
-    int rc;
-    if (grad ? (rc = jet_supported(h)) : 0) return rc;
-    if (n < 0 || M < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, M=%lld)", (long long)n, (long long)M);
-    if (grad && n == 1) return fail(MSIREN_E_INVALID, "the volume's gradient needs two slices at least (n=1)");
-    if ((rc = check_tile_size(h, false))) return rc;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    if (KA > msiren::RESAMPLE_MAX_KA)
-        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
-    int32_t nV, nH;
-    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
-    // every buffer of the call below 2^31 bytes, every index in 32 bits.  The stream's bin scratch holds 32 M K + 8 M bytes over the points
-    // (2 M K entries: slot and 8 bytes of coordinates; tile and weight per M K; pair and fraction per M) and 16 n nV nH over the bins: each
-    // half below 2^30.  The trunk's three planes are 24 M K bytes.  n is compared as an fp32 integer.
-    if (M > 0x0fffffffLL || 32 * M * K + 8 * M > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many points for one call: %lld points x %d covering tiles (32 M K + 8 M must stay below 2^30)", (long long)M, K);
-    if (n > 0x00ffffffLL || 16 * n * nV * nH > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many slices for one call: %lld slices x %d x %d tiles (16 n nV nH must stay below 2^30)", (long long)n, nV, nH);
-    return 0;
-}
-
-int resample_volume(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M,
-                    float* out_dev, float* grad_dev, bool grad, bool native) {
-    int rc = resample_volume_check(h, n, height, width, M, grad);
-    if (rc) return rc;
-    if (n > 0 && M > 0 && (!images_dev || !points_dev || (grad ? !grad_dev : !out_dev))) return fail(MSIREN_E_INVALID, "null argument");
-    if (n == 0 || M == 0) return 0;
-    if ((uintptr_t)points_dev % 4) return fail(MSIREN_E_INVALID, "device points must be 4-byte aligned");
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    int32_t nV, nH;
-    (void)msiren_recon_shape(h, height, width, &nV, &nH);
-    const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, MK = M * K, T = 2 * MK;
-    if ((rc = check_reflect_padding(h, height, width))) return rc;
-    auto& sc = h->sc[c.stream];
-    // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile M K][pair M][coords 2 T, 8-byte aligned][w M K][f M]
-    const size_t nint = (size_t)(4 * NP + 2 + T + MK + M + 1) & ~(size_t)1;
-    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, (nint + 2 * (size_t)T + MK + M) * 4)) ||
-        (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * (grad ? 3 : 1))))
-        return rc;
-    Call pc;
-    bool fused;
-    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &pc, &fused))) return rc;
-    hipStream_t st = sc.s;
-    int* const ib = (int*)sc.ragged.p;
-    msiren::ResampleVolumeParams vp{points_dev, (int)M, (int)n, nV, nH, h->S, h->I, (h->S - h->I) / 2, KA, grad ? 1 : 0};
-    vp.counts = ib, vp.cursors = ib + NP, vp.offsets = ib + 2 * NP;
-    int* const items = vp.offsets + NP + 1;
-    vp.ent = items + NP + 1, vp.tile = vp.ent + T, vp.pair = vp.tile + MK;
-    vp.coords = (float*)(ib + nint), vp.w = vp.coords + 2 * T, vp.f = vp.w + MK;
-    const unsigned gm = (unsigned)((M + 255) / 256);
-    hipEvent_t e1 = nullptr;
-    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-    HIPCHK(hipMemsetAsync(ib, 0, (size_t)2 * NP * sizeof(int), st));
-    hipLaunchKernelGGL(msiren::resample_volume_count_kernel, dim3(gm), dim3(256), 0, st, vp);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, vp.counts, (int)NP, vp.offsets);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::resample_volume_fill_kernel, dim3(gm), dim3(256), 0, st, vp);
-    HIPCHK(hipGetLastError());
-    if ((rc = profile_end(h, c.stream, e1, M, "resample_volume_bin_kernels"))) return rc;
-    float* const rec = (float*)sc.rec.p;  // [value (T)][d/d row][d/d column]
-    const int* plan = (const int*)sc.plan.p;
-    const RaggedSet r{vp.coords, vp.offsets, T, NP, 1, plan + 2 + NP, NP, items};
-    const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
-    if (grad) rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale);  // (grad[0] needs the values)
-    else rc = native ? launch_trunk_ragged_native(h, pc, r, (const float*)sc.mods.p, rec) : launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
-    if (rc || (rc = profile_begin(h, c.stream, &e1))) return rc;
-    hipLaunchKernelGGL(msiren::resample_volume_blend_kernel, dim3(gm), dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, (const int*)sc.keep.p, vp.pair, vp.f,
-                       out_dev, grad ? grad_dev : nullptr, (int)M, K, (int)NPt, (int)T, grad ? 3 : 1, grad ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    return profile_end(h, c.stream, e1, M, "resample_volume_blend_kernel");
-}
-
-// Slices scored under one affine map each against targets (kernels: align.hip.h): the slice prologue, then on the same
-// stream the pixels of every target lattice, placed by their slice's map in the kernel, binned by (slice, tile) -> the exact-fp32 jet ragged
-// trunk over those n nV nH bins, one replica, on the plan's rows -> per (slice, chunk) the blend of the three planes and the 29 fp64 sums ->
-// per slice the chunks in index order.  sums_dev (n, 29) doubles; warped_dev (n, th, tw) and wgrad_dev (2, n, th, tw) may be null.
-static_assert(kAlignSums == msiren::ALIGN_SUMS, "host and kernels disagree about a slice's record");
-int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
-    int rc;
-    if ((rc = jet_supported(h))) return rc;
-    if (n < 0 || th < 0 || tw < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, th=%d, tw=%d)", (long long)n, th, tw);
-    if ((rc = check_tile_size(h, false))) return rc;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    if (KA > msiren::RESAMPLE_MAX_KA)
-        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
-    int32_t nV, nH;
-    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
-    // every buffer of the call below 2^31 bytes, every index in 32 bits.  Over the T = n th tw K entries the stream's bin scratch holds 20 T
-    // bytes (slot, tile, weight, 8 bytes of coordinates) and 232 bytes per chunk of 1024 pixels, 16 n nV nH over the bins: each half below
-    // 2^30.  The trunk's three planes are 12 T bytes.
-    const int64_t M = (int64_t)th * tw;
-    if (n > 0x00ffffffLL || M > 0x0fffffffLL || n * M > 0x0fffffffLL || 20 * n * M * K + 232 * n * ((M + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK) > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices x %d x %d target pixels x %d covering tiles (20 n th tw K must stay below 2^30)",
-                    (long long)n, th, tw, K);
-    if (16 * n * nV * nH > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many slices for one call: %lld slices x %d x %d tiles (16 n nV nH must stay below 2^30)", (long long)n, nV, nH);
-    return 0;
-}
-
-// What align_prepare leaves for align_evaluate: the call's geometry and the trunk's call state.  Nothing of it lives on the handle.
-struct AlignPlan {
-    int64_t n = 0, M = 0, NPt = 0, NP = 0, T = 0, chunks = 0;
-    int32_t th = 0, tw = 0, nV = 0, nH = 0;
-    int KA = 0, K = 0;
-    size_t nint = 0, nflt = 0, bytes = 0;  // words of the integer / float part of the bins, bytes of bins + partials (what follows is the caller's)
-    const float* targets = nullptr;
-    Call pc;
-    // msiren_align_slices_w* / msiren_align_solve_w* (DESIGN.md section 5.12): the 47-sum reduce; weights (n, th, tw) and intensity (n, 2) may be null
-    bool weighted = false;
-    const float *weights = nullptr, *intensity = nullptr;
-};
-
-// the checks, every workspace of the call (`extra` bytes more behind the partials in the stream's scratch: msiren_align_solve's state) and the
-// slice prologue.  *todo = false: nothing to do (n = 0 or th tw = 0).  No workspace moves after this.
-static int align_prepare(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
-                         const void* maps_dev, const void* sums_dev, size_t extra, AlignPlan* a, bool* todo, int nsums = msiren::ALIGN_SUMS) {
-    *todo = false;
-    int rc = align_check(h, n, height, width, th, tw);
-    if (rc) return rc;
-    const int64_t M = (int64_t)th * tw;
-    if (n > 0 && M > 0 && (!images_dev || !targets_dev || !maps_dev || !sums_dev)) return fail(MSIREN_E_INVALID, "null argument");
-    if (n == 0 || M == 0) return 0;
-    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_dev % 4 || (uintptr_t)sums_dev % 8) return fail(MSIREN_E_INVALID, "device targets and maps must be 4-byte aligned, sums 8-byte aligned");
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    int32_t nV, nH;
-    (void)msiren_recon_shape(h, height, width, &nV, &nH);
-    const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, T = n * M * K, chunks = (M + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK;
-    if ((rc = check_reflect_padding(h, height, width))) return rc;
-    auto& sc = h->sc[c.stream];
-    // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile T][coords 2 T, 8-byte aligned][w T][partials n chunks nsums doubles, 8-byte aligned]
-    const size_t nint = (size_t)(4 * NP + 2 + 2 * T + 1) & ~(size_t)1, nflt = (size_t)(3 * T + 1) & ~(size_t)1;
-    const size_t bytes = (nint + nflt) * 4 + (size_t)n * chunks * nsums * sizeof(double);
-    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, bytes + extra)) || (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * 3)))
-        return rc;
-    *a = AlignPlan{n, M, NPt, NP, T, chunks, th, tw, nV, nH, KA, K, nint, nflt, bytes, targets_dev, Call()};
-    bool fused;
-    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &a->pc, &fused))) return rc;
-    *todo = true;
-    return 0;
-}
-
-// one evaluation behind align_prepare, on the same stream: the memset, count, scan, fill, the trunk, partial and combine
-static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
-    int rc;
-    auto& sc = h->sc[c.stream];
-    const int64_t n = a.n, M = a.M, NP = a.NP, T = a.T;
-    hipStream_t st = sc.s;
-    int* const ib = (int*)sc.ragged.p;
-    msiren::AlignParams ap{maps_dev, (int)n, a.th, a.tw, (int)M, a.nV, a.nH, h->S, h->I, (h->S - h->I) / 2, a.KA};
-    ap.counts = ib, ap.cursors = ib + NP, ap.offsets = ib + 2 * NP;
-    int* const items = ap.offsets + NP + 1;
-    ap.ent = items + NP + 1, ap.tile = ap.ent + T;
-    ap.coords = (float*)(ib + a.nint), ap.w = ap.coords + 2 * T;
-    double* const partials = (double*)(ap.coords + a.nflt);
-    const unsigned gm = (unsigned)((n * M + 255) / 256);
-    hipEvent_t e1 = nullptr;
-    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-    HIPCHK(hipMemsetAsync(ib, 0, (size_t)2 * NP * sizeof(int), st));
-    hipLaunchKernelGGL(msiren::align_count_kernel, dim3(gm), dim3(256), 0, st, ap);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, ap.counts, (int)NP, ap.offsets);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::align_fill_kernel, dim3(gm), dim3(256), 0, st, ap);
-    HIPCHK(hipGetLastError());
-    if ((rc = profile_end(h, c.stream, e1, n * M, "align_bin_kernels"))) return rc;
-    float* const rec = (float*)sc.rec.p;  // [value (T)][d/d row][d/d column]
-    const int* plan = (const int*)sc.plan.p;
-    const RaggedSet r{ap.coords, ap.offsets, T, NP, 1, plan + 2 + NP, NP, items};
-    const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
-    if ((rc = launch_trunk_f32_jet_ragged(h, a.pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale)) || (rc = profile_begin(h, c.stream, &e1))) return rc;
-    if (a.weighted) {  // the 47-sum pair of align_w.hip.h: sums_dev (n, 47)
-        hipLaunchKernelGGL(msiren::align_partial_w_kernel, dim3((unsigned)(n * a.chunks)), dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, (const int*)sc.keep.p, a.targets,
-                           a.weights, a.intensity, warped_dev, wgrad_dev, partials, (int)n, (int)M, a.tw, a.K, (int)a.NPt, (int)T, (int)a.chunks);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(msiren::align_combine_w_kernel, dim3((unsigned)n), dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
-        HIPCHK(hipGetLastError());
-        return profile_end(h, c.stream, e1, n * M, "align_reduce_w_kernels");
-    }
-    hipLaunchKernelGGL(msiren::align_partial_kernel, dim3((unsigned)(n * a.chunks)), dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, (const int*)sc.keep.p, a.targets,
-                       warped_dev, wgrad_dev, partials, (int)n, (int)M, a.tw, a.K, (int)a.NPt, (int)T, (int)a.chunks);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::align_combine_kernel, dim3((unsigned)n), dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
-    HIPCHK(hipGetLastError());
-    return profile_end(h, c.stream, e1, n * M, "align_reduce_kernels");
-}
-
-int align_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
-                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
-    AlignPlan a;
-    bool todo;
-    const int rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_dev, sums_dev, 0, &a, &todo);
-    if (rc || !todo) return rc;
-    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
-}
-
-// msiren_align_solve* (kernels: align.hip.h): align_prepare once, then `iterations` x (align_evaluate at the trial maps ->
-// align_step_kernel), all on the call's stream, no host sync in between.  State and the per-evaluation sums: the stream's scratch behind
-// the partials, ensured before the prologue.
-int align_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_opts* o, const void* maps_in,
-                      const void* rigid_in, const void* maps_out, const void* report) {
-    int rc = align_check(h, n, height, width, th, tw);
-    if (rc) return rc;
-    if (!o) return fail(MSIREN_E_INVALID, "null options");
-    if (o->struct_size != sizeof(msiren_align_solve_opts))
-        return fail(MSIREN_E_INVALID, "msiren_align_solve_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_solve_opts));
-    if (o->mode != 0 && o->mode != 1) return fail(MSIREN_E_INVALID, "mode = %d (0: affine, 1: rigid)", o->mode);
-    if (o->iterations < 1 || o->iterations > 256) return fail(MSIREN_E_INVALID, "iterations = %d outside 1 .. 256", o->iterations);
-    const double inf = __builtin_inf();
-    if (!(0.0 < o->lam_min && o->lam_min <= o->damping && o->damping <= o->lam_max && o->lam_max < inf))
-        return fail(MSIREN_E_INVALID, "damping: 0 < lam_min <= damping <= lam_max < inf is required (lam_min=%g, damping=%g, lam_max=%g)", o->lam_min, o->damping, o->lam_max);
-    if (!(0.0 < o->down && o->down <= 1.0) || !(1.0 <= o->up && o->up < inf)) return fail(MSIREN_E_INVALID, "0 < down <= 1 <= up < inf is required (down=%g, up=%g)", o->down, o->up);
-    if (o->mode == 1 && !(o->centre_y - o->centre_y == 0.0 && o->centre_x - o->centre_x == 0.0)) return fail(MSIREN_E_INVALID, "rigid mode: the centre must be finite");
-    if (n > 0 && (int64_t)th * tw > 0 && (!(o->mode == 1 ? rigid_in : maps_in) || !maps_out || !report))
-        return fail(MSIREN_E_INVALID, "null argument (%s)", !maps_out ? "maps_out" : !report ? "report" : o->mode == 1 ? "rigid_in: rigid mode" : "maps_in: affine mode");
-    return 0;
-}
-
-int align_solve(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
-                const msiren_align_solve_opts* o, const float* maps_in, const double* rigid_in, float* maps_out, double* rigid_out, double* report, double* trace) {
-    int rc = align_solve_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, report);
-    if (rc || n == 0 || (int64_t)th * tw == 0) return rc;
-    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
-    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)trace % 8)
-        return fail(MSIREN_E_INVALID, "device maps must be 4-byte aligned, rigid states, report and trace 8-byte aligned");
-    // state in the stream's scratch, behind the partials: [sums n 29][sums_best n 29][rigid_trial n 4][rigid_best n 4][scal n 3][trial n 6][best n 6][cnt n 2]
-    const size_t nd = (size_t)n * (2 * msiren::ALIGN_SUMS + 4 + 4 + 3), extra = nd * sizeof(double) + (size_t)n * (6 + 6 + 2) * 4;
-    AlignPlan a;
-    bool todo;
-    if ((rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_out, report, extra, &a, &todo)) || !todo) return rc;
-    auto& sc = h->sc[c.stream];
-    double* const d0 = (double*)((char*)sc.ragged.p + a.bytes);  // (a.bytes is a multiple of 8)
-    msiren::AlignSolveParams sp{};
-    double* const sums = d0;
-    sp.sums = sums, sp.sums_best = d0 + n * msiren::ALIGN_SUMS, sp.rigid_trial = sp.sums_best + n * msiren::ALIGN_SUMS, sp.rigid_best = sp.rigid_trial + n * 4;
-    sp.scal = sp.rigid_best + n * 4;
-    sp.trial = (float*)(d0 + nd), sp.best = sp.trial + n * 6, sp.cnt = (int*)(sp.best + n * 6);
-    sp.trace = trace, sp.maps_out = maps_out, sp.rigid_out = rigid_out, sp.report = report;
-    sp.n = (int)n, sp.mode = o->mode;
-    sp.down = o->down, sp.up = o->up, sp.lam_min = o->lam_min, sp.lam_max = o->lam_max, sp.cy = o->centre_y, sp.cx = o->centre_x;
-    hipStream_t st = sc.s;
-    const unsigned gs = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(msiren::align_solve_init_kernel, dim3(gs), dim3(256), 0, st, sp, maps_in, rigid_in, o->damping);
-    HIPCHK(hipGetLastError());
-    for (int k = 0; k < o->iterations; ++k) {
-        if ((rc = align_evaluate(h, c, a, sp.trial, sums, nullptr, nullptr))) return rc;
-        hipEvent_t e1 = nullptr;
-        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-        sp.k = k, sp.last = k == o->iterations - 1;
-        hipLaunchKernelGGL(msiren::align_step_kernel, dim3(gs), dim3(256), 0, st, sp);
-        HIPCHK(hipGetLastError());
-        if ((rc = profile_end(h, c.stream, e1, n, "align_step_kernel"))) return rc;
-    }
-    return 0;
-}
-
-// msiren_align_slices_w* / msiren_align_solve_w* (kernels: align_w.hip.h): align_prepare and align_evaluate with the 47-sum
-// reduce.  Partial records are 376 bytes per chunk of 1024 pixels: the bin scratch and they stay below 2^30 together.
-static_assert(kAlignSumsW == msiren::ALIGN_SUMS_W, "host and kernels disagree about a slice's weighted record");
-int align_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
-    int rc = align_check(h, n, height, width, th, tw);
-    if (rc) return rc;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    const int64_t M = (int64_t)th * tw;
-    if (20 * n * M * K + 8 * msiren::ALIGN_SUMS_W * n * ((M + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK) > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices x %d x %d target pixels x %d covering tiles (20 n th tw K must stay below 2^30)",
-                    (long long)n, th, tw, K);
-    return 0;
-}
-
-int align_slices_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
-                   const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
-    int rc = align_w_check(h, n, height, width, th, tw);
-    if (rc) return rc;
-    if ((uintptr_t)weights_dev % 4 || (uintptr_t)intensity_dev % 4) return fail(MSIREN_E_INVALID, "device weights and intensity must be 4-byte aligned");
-    AlignPlan a;
-    bool todo;
-    rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_dev, sums_dev, 0, &a, &todo, msiren::ALIGN_SUMS_W);
-    if (rc || !todo) return rc;
-    a.weighted = true, a.weights = weights_dev, a.intensity = intensity_dev;
-    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
-}
-
-int align_solve_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_w_opts* o, const void* maps_in,
-                        const void* rigid_in, const void* maps_out, const void* intensity_out, const void* report) {
-    if (!o) return fail(MSIREN_E_INVALID, "null options");
-    if (o->struct_size != sizeof(msiren_align_solve_w_opts))
-        return fail(MSIREN_E_INVALID, "msiren_align_solve_w_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_solve_w_opts));
-    if (o->intensity_mode != 0 && o->intensity_mode != 1) return fail(MSIREN_E_INVALID, "intensity_mode = %d (0: fixed, 1: estimate)", o->intensity_mode);
-    const msiren_align_solve_opts base{(uint32_t)sizeof(msiren_align_solve_opts), o->mode, o->iterations, 0, o->damping, o->down, o->up, o->lam_min, o->lam_max,
-                                       o->centre_y, o->centre_x};
-    int rc = align_solve_check(h, n, height, width, th, tw, &base, maps_in, rigid_in, maps_out, report);  // (everything msiren_align_solve refuses)
-    if (rc || (rc = align_w_check(h, n, height, width, th, tw))) return rc;
-    if (n > 0 && (int64_t)th * tw > 0 && !intensity_out) return fail(MSIREN_E_INVALID, "null argument (intensity_out)");
-    return 0;
-}
-
-int align_solve_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
-                  const msiren_align_solve_w_opts* o, const float* maps_in, const double* rigid_in, const float* weights_dev, const float* intensity_in, float* maps_out,
-                  float* intensity_out, double* rigid_out, double* report, double* trace) {
-    int rc = align_solve_w_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, intensity_out, report);
-    if (rc || n == 0 || (int64_t)th * tw == 0) return rc;
-    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
-    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_in % 4 ||
-        (uintptr_t)intensity_out % 4 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)trace % 8)
-        return fail(MSIREN_E_INVALID, "device maps, weights and intensity must be 4-byte aligned, rigid states, report and trace 8-byte aligned");
-    // state in the stream's scratch, behind the partials:
-    // [sums n 47][sums_best n 47][rigid_trial n 4][rigid_best n 4][scal n 3][trial n 6][best n 6][gb_trial n 2][gb_best n 2][cnt n 2]
-    const size_t nd = (size_t)n * (2 * msiren::ALIGN_SUMS_W + 4 + 4 + 3), extra = nd * sizeof(double) + (size_t)n * (6 + 6 + 2 + 2 + 2) * 4;
-    AlignPlan a;
-    bool todo;
-    if ((rc = align_prepare(h, c, images_dev, n, height, width, targets_dev, th, tw, maps_out, report, extra, &a, &todo, msiren::ALIGN_SUMS_W)) || !todo) return rc;
-    auto& sc = h->sc[c.stream];
-    double* const d0 = (double*)((char*)sc.ragged.p + a.bytes);  // (a.bytes is a multiple of 8)
-    msiren::AlignSolveWParams sp{};
-    double* const sums = d0;
-    sp.sums = sums, sp.sums_best = d0 + n * msiren::ALIGN_SUMS_W, sp.rigid_trial = sp.sums_best + n * msiren::ALIGN_SUMS_W, sp.rigid_best = sp.rigid_trial + n * 4;
-    sp.scal = sp.rigid_best + n * 4;
-    sp.trial = (float*)(d0 + nd), sp.best = sp.trial + n * 6, sp.gb_trial = sp.best + n * 6, sp.gb_best = sp.gb_trial + n * 2, sp.cnt = (int*)(sp.gb_best + n * 2);
-    sp.trace = trace, sp.maps_out = maps_out, sp.intensity_out = intensity_out, sp.rigid_out = rigid_out, sp.report = report;
-    sp.n = (int)n, sp.mode = o->mode, sp.estimate = o->intensity_mode;
-    sp.down = o->down, sp.up = o->up, sp.lam_min = o->lam_min, sp.lam_max = o->lam_max, sp.cy = o->centre_y, sp.cx = o->centre_x;
-    a.weighted = true, a.weights = weights_dev, a.intensity = sp.gb_trial;
-    hipStream_t st = sc.s;
-    const unsigned gs = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(msiren::align_solve_init_w_kernel, dim3(gs), dim3(256), 0, st, sp, maps_in, rigid_in, intensity_in, o->damping);
-    HIPCHK(hipGetLastError());
-    for (int k = 0; k < o->iterations; ++k) {
-        if ((rc = align_evaluate(h, c, a, sp.trial, sums, nullptr, nullptr))) return rc;
-        hipEvent_t e1 = nullptr;
-        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-        sp.k = k, sp.last = k == o->iterations - 1;
-        hipLaunchKernelGGL(msiren::align_step_w_kernel, dim3(gs), dim3(256), 0, st, sp);
-        HIPCHK(hipGetLastError());
-        if ((rc = profile_end(h, c.stream, e1, n, "align_step_w_kernel"))) return rc;
-    }
-    return 0;
-}
-
-// Target slices scored against the stack read as a volume (kernels: align_volume.hip.h): the slice prologue over the n
-// slices, then on the same stream the pixels of the m target lattices, placed by their target's 3 x 3 map in the kernel, binned by (slice, tile)
-// with two slices per pixel -> the exact-fp32 jet ragged trunk over those n nV nH bins, one replica -> per (target, chunk) the blend across tiles
-// and the pair and the 56 fp64 sums -> per target the chunks in index order.  sums_dev (m, 56) doubles; warped_dev (m, th, tw) and wgrad_dev
-// (3, m, th, tw) may be null.
-static_assert(kAlignVolumeSums == msiren::ALIGN_VOLUME_SUMS, "host and kernels disagree about a target's record");
-int align_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw) {
-    int rc;
-    if ((rc = jet_supported(h))) return rc;
-    if (n < 0 || m < 0 || th < 0 || tw < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, m=%lld, th=%d, tw=%d)", (long long)n, (long long)m, th, tw);
-    if (n < 2) return fail(MSIREN_E_INVALID, "a volume needs two slices at least (n=%lld)", (long long)n);
-    if ((rc = check_tile_size(h, false))) return rc;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    if (KA > msiren::RESAMPLE_MAX_KA)
-        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
-    int32_t nV, nH;
-    if ((rc = msiren_recon_shape(h, height, width, &nV, &nH))) return rc;
-    // every buffer of the call below 2^31 bytes, every index in 32 bits.  With M = m th tw the stream's bin scratch holds resample_volume's
-    // 32 M K + 8 M bytes over the pixels and 448 bytes per chunk of 1024 pixels, 16 n nV nH over the bins: each half below 2^30.  The trunk's
-    // three planes are 24 M K bytes.  n is compared as an fp32 integer.
-    const int64_t Mt = (int64_t)th * tw, chunks = (Mt + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK;
-    if (Mt > 0x0fffffffLL || m > 0x0fffffffLL || m * Mt > 0x0fffffffLL || 32 * m * Mt * K + 8 * m * Mt + 8 * msiren::ALIGN_VOLUME_SUMS * m * chunks > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld targets x %d x %d pixels x %d covering tiles (32 m th tw K + 8 m th tw must stay below 2^30, m th tw below 2^28)",
-                    (long long)m, th, tw, K);
-    if (n > 0x00ffffffLL || 16 * n * nV * nH > 0x3fffffffLL)
-        return fail(MSIREN_E_INVALID, "too many slices for one call: %lld slices x %d x %d tiles (16 n nV nH must stay below 2^30)", (long long)n, nV, nH);
-    return 0;
-}
-
-// What align_volume_prepare leaves for align_volume_evaluate: the call's geometry and the trunk's call state.  Nothing of it lives on the handle.
-struct AlignVolumePlan {
-    int64_t n = 0, m = 0, Mt = 0, M = 0, NPt = 0, NP = 0, MK = 0, T = 0, chunks = 0;
-    int32_t th = 0, tw = 0, nV = 0, nH = 0;
-    int KA = 0, K = 0;
-    size_t nint = 0, nflt = 0, bytes = 0;  // words of the integer / float part of the bins, bytes of bins + partials (what follows is the caller's)
-    const float* targets = nullptr;
-    Call pc;
-};
-
-// the checks, every workspace of the call (`extra` bytes more behind the partials in the stream's scratch: the solve's state) and the slice
-// prologue.  *todo = false: nothing to do (m = 0 or th tw = 0).  No workspace moves after this.
-static int align_volume_prepare(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m,
-                                int32_t th, int32_t tw, const void* maps_dev, const void* sums_dev, size_t extra, AlignVolumePlan* a, bool* todo) {
-    *todo = false;
-    int rc = align_volume_check(h, n, height, width, m, th, tw);
-    if (rc) return rc;
-    const int64_t Mt = (int64_t)th * tw, M = m * Mt;
-    if (M > 0 && (!images_dev || !targets_dev || !maps_dev || !sums_dev)) return fail(MSIREN_E_INVALID, "null argument");
-    if (M == 0) return 0;
-    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_dev % 4 || (uintptr_t)sums_dev % 8) return fail(MSIREN_E_INVALID, "device targets and maps must be 4-byte aligned, sums 8-byte aligned");
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    int32_t nV, nH;
-    (void)msiren_recon_shape(h, height, width, &nV, &nH);
-    const int64_t NPt = (int64_t)nV * nH, NP = n * NPt, MK = M * K, T = 2 * MK, chunks = (Mt + msiren::ALIGN_CHUNK - 1) / msiren::ALIGN_CHUNK;
-    if ((rc = check_reflect_padding(h, height, width))) return rc;
-    auto& sc = h->sc[c.stream];
-    // bins in the stream's scratch: [counts NP][cursors NP][offsets NP + 1][items NP + 1][ent T][tile M K][pair M][coords 2 T, 8-byte aligned][w M K][f M]
-    // [partials m chunks 56 doubles, 8-byte aligned]
-    const size_t nint = (size_t)(4 * NP + 2 + T + MK + M + 1) & ~(size_t)1, nflt = (size_t)(2 * T + MK + M + 1) & ~(size_t)1;
-    const size_t bytes = (nint + nflt) * 4 + (size_t)m * chunks * msiren::ALIGN_VOLUME_SUMS * sizeof(double);
-    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, bytes + extra)) || (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * 3)))
-        return rc;
-    *a = AlignVolumePlan{n, m, Mt, M, NPt, NP, MK, T, chunks, th, tw, nV, nH, KA, K, nint, nflt, bytes, targets_dev, Call()};
-    bool fused;
-    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, nV, nH, &a->pc, &fused))) return rc;
-    *todo = true;
-    return 0;
-}
-
-// one evaluation behind align_volume_prepare, on the same stream: the memset, count, scan, fill, the trunk, partial and combine
-static int align_volume_evaluate(msiren_handle h, const Call& c, const AlignVolumePlan& a, const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
-    int rc;
-    auto& sc = h->sc[c.stream];
-    const int64_t M = a.M, NP = a.NP, MK = a.MK, T = a.T;
-    hipStream_t st = sc.s;
-    int* const ib = (int*)sc.ragged.p;
-    msiren::AlignVolumeParams ap{};
-    ap.v = msiren::ResampleVolumeParams{nullptr, (int)M, (int)a.n, a.nV, a.nH, h->S, h->I, (h->S - h->I) / 2, a.KA, 1};
-    ap.maps = maps_dev, ap.th = a.th, ap.tw = a.tw, ap.Mt = (int)a.Mt;
-    auto& vp = ap.v;
-    vp.counts = ib, vp.cursors = ib + NP, vp.offsets = ib + 2 * NP;
-    int* const items = vp.offsets + NP + 1;
-    vp.ent = items + NP + 1, vp.tile = vp.ent + T, vp.pair = vp.tile + MK;
-    vp.coords = (float*)(ib + a.nint), vp.w = vp.coords + 2 * T, vp.f = vp.w + MK;
-    double* const partials = (double*)(vp.coords + a.nflt);
-    const unsigned gm = (unsigned)((M + 255) / 256);
-    hipEvent_t e1 = nullptr;
-    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-    HIPCHK(hipMemsetAsync(ib, 0, (size_t)2 * NP * sizeof(int), st));
-    hipLaunchKernelGGL(msiren::align_volume_count_kernel, dim3(gm), dim3(256), 0, st, ap);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, vp.counts, (int)NP, vp.offsets);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::align_volume_fill_kernel, dim3(gm), dim3(256), 0, st, ap);
-    HIPCHK(hipGetLastError());
-    if ((rc = profile_end(h, c.stream, e1, M, "align_volume_bin_kernels"))) return rc;
-    float* const rec = (float*)sc.rec.p;  // [value (T)][d/d row][d/d column]
-    const int* plan = (const int*)sc.plan.p;
-    const RaggedSet r{vp.coords, vp.offsets, T, NP, 1, plan + 2 + NP, NP, items};
-    const float gscale = (float)(2.0 / (double)(h->S - 1));  // coordinate units per reconstruction pixel
-    if ((rc = launch_trunk_f32_jet_ragged(h, a.pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, gscale)) || (rc = profile_begin(h, c.stream, &e1))) return rc;
-    hipLaunchKernelGGL(msiren::align_volume_partial_kernel, dim3((unsigned)(a.m * a.chunks)), dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, (const int*)sc.keep.p, vp.pair,
-                       vp.f, a.targets, warped_dev, wgrad_dev, partials, (int)a.m, (int)a.Mt, a.tw, a.K, (int)a.NPt, (int)T, (int)a.chunks);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::align_volume_combine_kernel, dim3((unsigned)a.m), dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
-    HIPCHK(hipGetLastError());
-    return profile_end(h, c.stream, e1, M, "align_volume_reduce_kernels");
-}
-
-int align_volume(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
-                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
-    if ((uintptr_t)warped_dev % 4 || (uintptr_t)wgrad_dev % 4) return fail(MSIREN_E_INVALID, "device warped and wgrad must be 4-byte aligned");
-    AlignVolumePlan a;
-    bool todo;
-    const int rc = align_volume_prepare(h, c, images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, sums_dev, 0, &a, &todo);
-    if (rc || !todo) return rc;
-    return align_volume_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
-}
-
-// msiren_align_volume_solve* (kernels: align_volume.hip.h): align_volume_prepare once, then `iterations` x
-// (align_volume_evaluate at the trial maps -> align_volume_step_kernel of the mode), all on the call's stream, no host sync in between.  State and
-// the per-evaluation sums: the stream's scratch behind the partials, ensured before the prologue.
-int align_volume_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_opts* o,
-                             const void* maps_in, const void* planes, const void* rigid_in, const void* maps_out, const void* report) {
-    int rc = align_volume_check(h, n, height, width, m, th, tw);
-    if (rc) return rc;
-    if (!o) return fail(MSIREN_E_INVALID, "null options");
-    if (o->struct_size != sizeof(msiren_align_volume_solve_opts))
-        return fail(MSIREN_E_INVALID, "msiren_align_volume_solve_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_volume_solve_opts));
-    if (o->mode != 0 && o->mode != 1) return fail(MSIREN_E_INVALID, "mode = %d (0: affine, 1: rigid)", o->mode);
-    if (o->iterations < 1 || o->iterations > 256) return fail(MSIREN_E_INVALID, "iterations = %d outside 1 .. 256", o->iterations);
-    const double inf = __builtin_inf();
-    if (!(0.0 < o->lam_min && o->lam_min <= o->damping && o->damping <= o->lam_max && o->lam_max < inf))
-        return fail(MSIREN_E_INVALID, "damping: 0 < lam_min <= damping <= lam_max < inf is required (lam_min=%g, damping=%g, lam_max=%g)", o->lam_min, o->damping, o->lam_max);
-    if (!(0.0 < o->down && o->down <= 1.0) || !(1.0 <= o->up && o->up < inf)) return fail(MSIREN_E_INVALID, "0 < down <= 1 <= up < inf is required (down=%g, up=%g)", o->down, o->up);
-    if (o->mode == 1 && !(o->spacing > 0.0 && o->spacing < inf)) return fail(MSIREN_E_INVALID, "rigid mode: spacing = %g must be finite and > 0", o->spacing);
-    if (m > 0 && (int64_t)th * tw > 0 && (!(o->mode == 1 ? (rigid_in && planes) : maps_in != nullptr) || !maps_out || !report))
-        return fail(MSIREN_E_INVALID, "null argument (%s)", !maps_out ? "maps_out" : !report ? "report" : o->mode == 1 ? "planes or rigid_in: rigid mode" : "maps_in: affine mode");
-    return 0;
-}
-
-int align_volume_solve(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
-                       int32_t tw, const msiren_align_volume_solve_opts* o, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out,
-                       double* rigid_out, double* report, double* trace) {
-    int rc = align_volume_solve_check(h, n, height, width, m, th, tw, o, maps_in, planes, rigid_in, maps_out, report);
-    if (rc || m == 0 || (int64_t)th * tw == 0) return rc;
-    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
-    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)planes % 8 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 ||
-        (uintptr_t)report % 8 || (uintptr_t)trace % 8)
-        return fail(MSIREN_E_INVALID, "device maps must be 4-byte aligned, planes, rigid states, report and trace 8-byte aligned");
-    // state in the stream's scratch, behind the partials: [sums m 56][sums_best m 56][rigid_trial m 12][rigid_best m 12][scal m 3][trial m 9][best m 9][cnt m 2]
-    const size_t nd = (size_t)m * (2 * msiren::ALIGN_VOLUME_SUMS + 12 + 12 + 3), extra = nd * sizeof(double) + (size_t)m * (9 + 9 + 2) * 4;
-    AlignVolumePlan a;
-    bool todo;
-    if ((rc = align_volume_prepare(h, c, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report, extra, &a, &todo)) || !todo) return rc;
-    auto& sc = h->sc[c.stream];
-    double* const d0 = (double*)((char*)sc.ragged.p + a.bytes);  // (a.bytes is a multiple of 8)
-    msiren::AlignVolumeSolveParams sp{};
-    double* const sums = d0;
-    sp.sums = sums, sp.planes = planes, sp.sums_best = d0 + m * msiren::ALIGN_VOLUME_SUMS, sp.rigid_trial = sp.sums_best + m * msiren::ALIGN_VOLUME_SUMS;
-    sp.rigid_best = sp.rigid_trial + m * 12, sp.scal = sp.rigid_best + m * 12;
-    sp.trial = (float*)(d0 + nd), sp.best = sp.trial + m * 9, sp.cnt = (int*)(sp.best + m * 9);
-    sp.trace = trace, sp.maps_out = maps_out, sp.rigid_out = rigid_out, sp.report = report;
-    sp.m = (int)m;
-    sp.down = o->down, sp.up = o->up, sp.lam_min = o->lam_min, sp.lam_max = o->lam_max, sp.spacing = o->spacing;
-    hipStream_t st = sc.s;
-    const unsigned gs = (unsigned)((m + 255) / 256);
-    const bool rigid = o->mode == 1;
-    if (rigid) hipLaunchKernelGGL(msiren::align_volume_solve_init_kernel<msiren::ALIGN_VOLUME_RIGID>, dim3(gs), dim3(256), 0, st, sp, maps_in, rigid_in, o->damping);
-    else hipLaunchKernelGGL(msiren::align_volume_solve_init_kernel<msiren::ALIGN_VOLUME_AFFINE>, dim3(gs), dim3(256), 0, st, sp, maps_in, rigid_in, o->damping);
-    HIPCHK(hipGetLastError());
-    for (int k = 0; k < o->iterations; ++k) {
-        if ((rc = align_volume_evaluate(h, c, a, sp.trial, sums, nullptr, nullptr))) return rc;
-        hipEvent_t e1 = nullptr;
-        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-        sp.k = k, sp.last = k == o->iterations - 1;
-        if (rigid) hipLaunchKernelGGL(msiren::align_volume_step_kernel<msiren::ALIGN_VOLUME_RIGID>, dim3(gs), dim3(256), 0, st, sp);
-        else hipLaunchKernelGGL(msiren::align_volume_step_kernel<msiren::ALIGN_VOLUME_AFFINE>, dim3(gs), dim3(256), 0, st, sp);
-        HIPCHK(hipGetLastError());
-        if ((rc = profile_end(h, c.stream, e1, m, "align_volume_step_kernel"))) return rc;
-    }
-    return 0;
 }
 
 // msiren_weighted_fold_dev with the output side of another stride (kernel S', stride I', padding pad'): complete tiles, no black flags

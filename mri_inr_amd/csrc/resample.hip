@@ -3,13 +3,536 @@
 // (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
 // The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
 // msiren_resample_slices*, msiren_resample_volume*, msiren_align_slices*, msiren_align_solve* and their weighted forms msiren_align_slices_w*,
-// msiren_align_solve_w*, and msiren_align_volume*, msiren_align_volume_solve* (DESIGN.md sections 5.8 - 5.13) are built on these trunks: launch_dispatch.hip.
+// msiren_align_solve_w*, and msiren_align_volume*, msiren_align_volume_solve* (DESIGN.md sections 5.8 - 5.13) are built on these trunks: the five
+// geometry pipelines below (namespace mh), each behind launch_dispatch.hip's slice_prologue on the call's stream, then their host-pointer forms
+// and the entry points.  Where each call's scratch sections lie and what it refuses as too large: align_plan.h.
 #include "host_buffers.h"
 #include "host_ctx.h"
+#include "align_plan.h"
+#include "resample.hip.h"
+#include "resample_volume.hip.h"
+#include "align.hip.h"
+#include "align_w.hip.h"
+#include "align_volume.hip.h"
+
+namespace mh {
+
+static_assert(kAlignSums == msiren::ALIGN_SUMS && kAlignSumsW == msiren::ALIGN_SUMS_W && kAlignVolumeSums == msiren::ALIGN_VOLUME_SUMS,
+              "host and kernels disagree about a record");
+static_assert(msiren::kAlignChunk == msiren::ALIGN_CHUNK, "align_plan.h and the kernels disagree about a chunk");
+
+// ---- what the five pipelines share ------------------------------------------------------------------------------------------------------------
+// a slice's tiling as these calls see it: KA x KA tiles at most cover a point, nV x nH tiles per slice
+struct Geom { int KA = 0, K = 0; int32_t nV = 0, nH = 0; int64_t NPt = 0; };
+
+// the refusals every geometry call shares, in this order: the tile size, the cover, the reconstruction's shape.  (Each check asks
+// jet_supported and its own arguments first.)
+static int geom_check(msiren_ctx* h, int32_t height, int32_t width, Geom* g) {
+    int rc;
+    if ((rc = check_tile_size(h, false))) return rc;
+    g->KA = (h->S + h->I - 1) / h->I, g->K = g->KA * g->KA;
+    if (g->KA > msiren::RESAMPLE_MAX_KA)
+        return fail(MSIREN_E_INVALID, "siren_patch_size=%d over inner_patch_size=%d: more than %d tiles per axis would cover a point", h->S, h->I, msiren::RESAMPLE_MAX_KA);
+    if ((rc = msiren_recon_shape(h, height, width, &g->nV, &g->nH))) return rc;
+    g->NPt = (int64_t)g->nV * g->nH;
+    return 0;
+}
+static int fail_slices(int64_t n, const Geom& g) {
+    return fail(MSIREN_E_INVALID, "too many slices for one call: %lld slices x %d x %d tiles (16 n nV nH must stay below 2^30)", (long long)n, g.nV, g.nH);
+}
+
+// a kernel parameter struct's pointers into the block at `base` (align_plan.h)
+template <typename P>
+static void carve(P& p, char* base, const msiren::GeomLayout& l) {
+    p.counts = (int*)(base + l.counts), p.cursors = (int*)(base + l.cursors), p.offsets = (int*)(base + l.offsets);
+    p.ent = (int*)(base + l.ent), p.tile = (int*)(base + l.tile), p.coords = (float*)(base + l.coords), p.w = (float*)(base + l.w);
+}
+static void carve_volume(msiren::ResampleVolumeParams& p, char* base, const msiren::GeomLayout& l) {
+    carve(p, base, l);
+    p.pair = (int*)(base + l.pair), p.f = (float*)(base + l.f);
+}
+
+// the bin bracket, one profile entry `name`: memset of counts and cursors -> count -> scan over the bins -> fill, one thread per point
+template <typename P>
+static int bin_bracket(msiren_ctx* h, const Call& c, void (*count)(P), void (*fill)(P), const P& p, char* base, const msiren::GeomLayout& l, int64_t bins,
+                       int64_t points, const char* name) {
+    int rc;
+    hipStream_t st = h->sc[c.stream].s;
+    const unsigned gm = (unsigned)((points + 255) / 256);
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+    HIPCHK(hipMemsetAsync(base + l.counts, 0, l.zero_bytes, st));
+    hipLaunchKernelGGL(count, dim3(gm), dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::resample_scan_kernel, dim3(1), dim3(256), 0, st, (const int*)(base + l.counts), (int)bins, (int*)(base + l.offsets));
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(fill, dim3(gm), dim3(256), 0, st, p);
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, points, name);
+}
+
+// the filled bins as the ragged trunks take them: T entries in `bins` patches, `reps` replicas, on the plan's rows of the NP tiles
+static RaggedSet bins_set(msiren_ctx* h, const Call& c, char* base, const msiren::GeomLayout& l, int64_t T, int64_t bins, int64_t reps, int64_t NP) {
+    return RaggedSet{(const float*)(base + l.coords), (const int*)(base + l.offsets), T, bins, reps, (const int*)h->sc[c.stream].plan.p + 2 + NP, NP, (int*)(base + l.items)};
+}
+static float pixel_gscale(const msiren_ctx* h) { return (float)(2.0 / (double)(h->S - 1)); }  // coordinate units per reconstruction pixel
+
+// ---- the reconstruction at arbitrary points (kernels: resample.hip.h) ------------------------------------------------------
+// The slice prologue, then on the same stream bin the points by covering tile -> ragged exact-fp32 trunk (`native`: the handle's own,
+// launch_trunk_ragged_native), replicated over the slices, patch s NP + t on the plan's row -> blend.
+// `grad`: value (out_dev may be null) and the two gradient planes grad_dev (2, n, M), per reconstruction pixel.
+int resample_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad) {
+    int rc;
+    Geom g;
+    if (grad ? (rc = jet_supported(h)) : 0) return rc;
+    if (n < 0 || M < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, M=%lld)", (long long)n, (long long)M);
+    if ((rc = geom_check(h, height, width, &g))) return rc;
+    if (!msiren::resample_fits(n, M, g.K, g.NPt))
+        return fail(MSIREN_E_INVALID, "too many points for one call: %lld points x %d covering tiles x %lld slices (8 M K and 12 n M K must stay below 2^31)",
+                    (long long)M, g.K, (long long)n);
+    return 0;
+}
+
+int resample_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M,
+                    float* out_dev, float* grad_dev, bool grad, bool native) {
+    int rc = resample_check(h, n, height, width, M, grad);
+    if (rc) return rc;
+    if (n > 0 && M > 0 && (!images_dev || !points_dev || (grad ? !grad_dev : !out_dev))) return fail(MSIREN_E_INVALID, "null argument");
+    if (n == 0 || M == 0) return 0;
+    Geom g;
+    (void)geom_check(h, height, width, &g);
+    const int K = g.K;
+    const int64_t NPt = g.NPt, NP = n * NPt, T = M * K;
+    if ((rc = check_pairs_aligned(points_dev, "points")) || (rc = check_reflect_padding(h, height, width))) return rc;
+    auto& sc = h->sc[c.stream];
+    const msiren::GeomLayout lay = msiren::resample_layout(NPt, M, K);
+    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, lay.total)) ||
+        (rc = ensure(h, sc.rec, (size_t)n * T * sizeof(float) * (grad ? 3 : 1))))
+        return rc;
+    Call pc;
+    bool fused;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, g.nV, g.nH, &pc, &fused))) return rc;
+    hipStream_t st = sc.s;
+    char* const base = (char*)sc.ragged.p;
+    msiren::ResampleParams rp{points_dev, (int)M, g.nV, g.nH, h->S, h->I, (h->S - h->I) / 2, g.KA};
+    carve(rp, base, lay);
+    if ((rc = bin_bracket(h, c, msiren::resample_count_kernel, msiren::resample_fill_kernel, rp, base, lay, NPt, M, "resample_bin_kernels"))) return rc;
+    float* const rec = (float*)sc.rec.p;  // [value (n, T)][d/d row][d/d column]
+    const RaggedSet r = bins_set(h, c, base, lay, T, NPt, n, NP);
+    if (grad) rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, out_dev ? rec : nullptr, rec + (size_t)n * T, pixel_gscale(h));
+    else rc = native ? launch_trunk_ragged_native(h, pc, r, (const float*)sc.mods.p, rec) : launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
+    hipEvent_t e1 = nullptr;
+    if (rc || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    const unsigned gb = (unsigned)((n * M + 255) / 256);
+    if (out_dev) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, out_dev, (int)n, (int)M, K, (int)NPt, (int)T, 1);
+    if (grad) hipLaunchKernelGGL(msiren::resample_blend_kernel, dim3(gb), dim3(256), 0, st, rec + (size_t)n * T, rp.ent, rp.tile, rp.w, (const int*)sc.keep.p, grad_dev, (int)n, (int)M, K, (int)NPt, (int)T, 2);
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, n * M, "resample_blend_kernel");
+}
+
+// ---- a stack of slices read as a volume at points (Z, Y, X) (kernels: resample_volume.hip.h) -----------------------------
+// The slice prologue, then on the same stream bin the points by (slice, tile) -> the ragged trunk over those n nV nH bins as its patches, one
+// replica, on the plan's rows (`native`: launch_trunk_ragged_native) -> blend across tiles and the pair of slices.  Scratch grows with 2 M K,
+// not with n.  `grad`: value (out_dev may be null) and the three gradient planes grad_dev (3, M): per slice of Z, per reconstruction pixel rows, columns.
+int resample_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t M, bool grad) {
+    int rc;
+    Geom g;
+    if (grad ? (rc = jet_supported(h)) : 0) return rc;
+    if (n < 0 || M < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, M=%lld)", (long long)n, (long long)M);
+    if (grad && n == 1) return fail(MSIREN_E_INVALID, "the volume's gradient needs two slices at least (n=1)");
+    if ((rc = geom_check(h, height, width, &g))) return rc;
+    if (!msiren::volume_points_fit(M, g.K))
+        return fail(MSIREN_E_INVALID, "too many points for one call: %lld points x %d covering tiles (32 M K + 8 M must stay below 2^30)", (long long)M, g.K);
+    if (!msiren::volume_slices_fit(n, g.NPt)) return fail_slices(n, g);
+    return 0;
+}
+
+int resample_volume(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* points_dev, int64_t M,
+                    float* out_dev, float* grad_dev, bool grad, bool native) {
+    int rc = resample_volume_check(h, n, height, width, M, grad);
+    if (rc) return rc;
+    if (n > 0 && M > 0 && (!images_dev || !points_dev || (grad ? !grad_dev : !out_dev))) return fail(MSIREN_E_INVALID, "null argument");
+    if (n == 0 || M == 0) return 0;
+    if ((uintptr_t)points_dev % 4) return fail(MSIREN_E_INVALID, "device points must be 4-byte aligned");
+    Geom g;
+    (void)geom_check(h, height, width, &g);
+    const int K = g.K;
+    const int64_t NPt = g.NPt, NP = n * NPt, T = 2 * M * K;
+    if ((rc = check_reflect_padding(h, height, width))) return rc;
+    auto& sc = h->sc[c.stream];
+    const msiren::GeomLayout lay = msiren::resample_volume_layout(NP, M, K);
+    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, lay.total)) ||
+        (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * (grad ? 3 : 1))))
+        return rc;
+    Call pc;
+    bool fused;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, g.nV, g.nH, &pc, &fused))) return rc;
+    hipStream_t st = sc.s;
+    char* const base = (char*)sc.ragged.p;
+    msiren::ResampleVolumeParams vp{points_dev, (int)M, (int)n, g.nV, g.nH, h->S, h->I, (h->S - h->I) / 2, g.KA, grad ? 1 : 0};
+    carve_volume(vp, base, lay);
+    if ((rc = bin_bracket(h, c, msiren::resample_volume_count_kernel, msiren::resample_volume_fill_kernel, vp, base, lay, NP, M, "resample_volume_bin_kernels")))
+        return rc;
+    float* const rec = (float*)sc.rec.p;  // [value (T)][d/d row][d/d column]
+    const RaggedSet r = bins_set(h, c, base, lay, T, NP, 1, NP);
+    if (grad) rc = launch_trunk_f32_jet_ragged(h, pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, pixel_gscale(h));  // (grad[0] needs the values)
+    else rc = native ? launch_trunk_ragged_native(h, pc, r, (const float*)sc.mods.p, rec) : launch_trunk_f32_ragged(h, pc, r, (const float*)sc.mods.p, rec);
+    hipEvent_t e1 = nullptr;
+    if (rc || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    hipLaunchKernelGGL(msiren::resample_volume_blend_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, (const int*)sc.keep.p,
+                       vp.pair, vp.f, out_dev, grad ? grad_dev : nullptr, (int)M, K, (int)NPt, (int)T, grad ? 3 : 1, grad ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, M, "resample_volume_blend_kernel");
+}
+
+// ---- the three align families (DESIGN.md sections 5.10 - 5.13; kernels: align.hip.h, align_w.hip.h, align_volume.hip.h) ----------------------------
+// Slices scored under one 2 x 3 map each against their targets (plain: 29 fp64 sums per slice; weighted: 47, with a per-pixel weight and a
+// per-slice gain and bias), or m targets under one 3 x 3 map each against the stack read as a volume (56 per target).  One path: the slice
+// prologue over the n slices, then per evaluation on the same stream the pixels of every target lattice, placed by their map in the kernel,
+// binned by (slice, tile) -> the exact-fp32 jet ragged trunk over those n nV nH bins, one replica, on the plan's rows -> per (unit, chunk) the
+// blend and the sums -> per unit the chunks in index order.  A unit is a slice (plain, weighted) or a target (volume).
+enum AlignFamily { ALIGN_PLAIN, ALIGN_WEIGHTED, ALIGN_VOLUME };
+static int align_nsums(AlignFamily f) { return f == ALIGN_PLAIN ? msiren::ALIGN_SUMS : f == ALIGN_WEIGHTED ? msiren::ALIGN_SUMS_W : msiren::ALIGN_VOLUME_SUMS; }
+
+int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
+    int rc;
+    Geom g;
+    if ((rc = jet_supported(h))) return rc;
+    if (n < 0 || th < 0 || tw < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, th=%d, tw=%d)", (long long)n, th, tw);
+    if ((rc = geom_check(h, height, width, &g))) return rc;
+    if (!msiren::align_pixels_fit(n, (int64_t)th * tw, g.K, msiren::ALIGN_SUMS))
+        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices x %d x %d target pixels x %d covering tiles (20 n th tw K must stay below 2^30)",
+                    (long long)n, th, tw, g.K);
+    if (!msiren::bins_fit(n, g.NPt)) return fail_slices(n, g);
+    return 0;
+}
+
+// the weighted form's partial records are 376 bytes per chunk: the bin scratch and they stay below 2^30 together
+int align_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
+    int rc = align_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    if (!msiren::align_pixels_fit(n, (int64_t)th * tw, K, msiren::ALIGN_SUMS_W))
+        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices x %d x %d target pixels x %d covering tiles (20 n th tw K must stay below 2^30)",
+                    (long long)n, th, tw, K);
+    return 0;
+}
+
+int align_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw) {
+    int rc;
+    Geom g;
+    if ((rc = jet_supported(h))) return rc;
+    if (n < 0 || m < 0 || th < 0 || tw < 0) return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, m=%lld, th=%d, tw=%d)", (long long)n, (long long)m, th, tw);
+    if (n < 2) return fail(MSIREN_E_INVALID, "a volume needs two slices at least (n=%lld)", (long long)n);
+    if ((rc = geom_check(h, height, width, &g))) return rc;
+    if (!msiren::align_volume_pixels_fit(m, (int64_t)th * tw, g.K, msiren::ALIGN_VOLUME_SUMS))
+        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld targets x %d x %d pixels x %d covering tiles (32 m th tw K + 8 m th tw must stay below 2^30, m th tw below 2^28)",
+                    (long long)m, th, tw, g.K);
+    if (!msiren::volume_slices_fit(n, g.NPt)) return fail_slices(n, g);
+    return 0;
+}
+
+// What align_prepare leaves for align_evaluate: the call's geometry, its scratch layout and the trunk's call state.  Nothing of it lives on the handle.
+struct AlignPlan {
+    AlignFamily fam = ALIGN_PLAIN;
+    int64_t n = 0, units = 0, Mt = 0, M = 0, T = 0, chunks = 0;  // units: n slices or m targets; Mt = th tw; M = units Mt pixels; T entries
+    int32_t th = 0, tw = 0;
+    Geom g;
+    msiren::GeomLayout lay{};  // lay.total: what follows in the stream's scratch is the solve's
+    const float* targets = nullptr;
+    const float *weights = nullptr, *intensity = nullptr;  // weighted: (n, th, tw) and (n, 2), may be null
+    Call pc;
+};
+
+// the family's check, every workspace of the call (`extra` bytes more behind the partials: a solve's state) and the slice prologue.
+// `units`: n for the slice families, m for the volume.  *todo = false: nothing to do (no unit or th tw = 0).  No workspace moves after this.
+static int align_prepare(msiren_handle h, const Call& c, AlignFamily fam, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev,
+                         int64_t units, int32_t th, int32_t tw, const void* maps_dev, const void* sums_dev, size_t extra, AlignPlan* a, bool* todo) {
+    *todo = false;
+    const bool volume = fam == ALIGN_VOLUME;
+    int rc = volume ? align_volume_check(h, n, height, width, units, th, tw) : align_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    const int64_t Mt = (int64_t)th * tw, M = units * Mt;
+    if (M > 0 && (!images_dev || !targets_dev || !maps_dev || !sums_dev)) return fail(MSIREN_E_INVALID, "null argument");
+    if (M == 0) return 0;
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_dev % 4 || (uintptr_t)sums_dev % 8) return fail(MSIREN_E_INVALID, "device targets and maps must be 4-byte aligned, sums 8-byte aligned");
+    Geom g;
+    (void)geom_check(h, height, width, &g);
+    const int64_t NP = n * g.NPt, T = (volume ? 2 : 1) * M * g.K;
+    if ((rc = check_reflect_padding(h, height, width))) return rc;
+    auto& sc = h->sc[c.stream];
+    const int nsums = align_nsums(fam);
+    const msiren::GeomLayout lay = volume ? msiren::align_volume_layout(NP, units, Mt, g.K, nsums) : msiren::align_layout(NP, n, Mt, g.K, nsums);
+    if ((rc = ensure(h, sc.patches, (size_t)NP * h->O * h->O * sizeof(float))) || (rc = ensure(h, sc.ragged, lay.total + extra)) || (rc = ensure(h, sc.rec, (size_t)T * sizeof(float) * 3)))
+        return rc;
+    *a = AlignPlan{fam, n, units, Mt, M, T, msiren::align_chunks(Mt), th, tw, g, lay, targets_dev, nullptr, nullptr, Call()};
+    bool fused;
+    if ((rc = slice_prologue(h, c, images_dev, height, width, (float*)sc.patches.p, nullptr, n, g.nV, g.nH, &a->pc, &fused))) return rc;
+    *todo = true;
+    return 0;
+}
+
+// one evaluation behind align_prepare, on the same stream: the bin bracket, the trunk, then partial and combine as one profile entry
+static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc;
+    auto& sc = h->sc[c.stream];
+    const Geom& g = a.g;
+    const int64_t NP = a.n * g.NPt, T = a.T;
+    hipStream_t st = sc.s;
+    char* const base = (char*)sc.ragged.p;
+    msiren::AlignVolumeParams avp{};
+    msiren::ResampleVolumeParams& vp = avp.v;
+    msiren::AlignParams ap{maps_dev, (int)a.n, a.th, a.tw, (int)a.Mt, g.nV, g.nH, h->S, h->I, (h->S - h->I) / 2, g.KA};
+    if (a.fam == ALIGN_VOLUME) {
+        vp = msiren::ResampleVolumeParams{nullptr, (int)a.M, (int)a.n, g.nV, g.nH, h->S, h->I, (h->S - h->I) / 2, g.KA, 1};
+        avp.maps = maps_dev, avp.th = a.th, avp.tw = a.tw, avp.Mt = (int)a.Mt;
+        carve_volume(vp, base, a.lay);
+        rc = bin_bracket(h, c, msiren::align_volume_count_kernel, msiren::align_volume_fill_kernel, avp, base, a.lay, NP, a.M, "align_volume_bin_kernels");
+    } else {
+        carve(ap, base, a.lay);
+        rc = bin_bracket(h, c, msiren::align_count_kernel, msiren::align_fill_kernel, ap, base, a.lay, NP, a.M, "align_bin_kernels");
+    }
+    if (rc) return rc;
+    float* const rec = (float*)sc.rec.p;  // [value (T)][d/d row][d/d column]
+    double* const partials = (double*)(base + a.lay.partials);
+    const int* const black = (const int*)sc.keep.p;
+    const RaggedSet r = bins_set(h, c, base, a.lay, T, NP, 1, NP);
+    hipEvent_t e1 = nullptr;
+    if ((rc = launch_trunk_f32_jet_ragged(h, a.pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, pixel_gscale(h))) || (rc = profile_begin(h, c.stream, &e1))) return rc;
+    const dim3 gp((unsigned)(a.units * a.chunks)), gc((unsigned)a.units);
+    const char* name;
+    if (a.fam == ALIGN_VOLUME) {  // sums_dev (m, 56)
+        hipLaunchKernelGGL(msiren::align_volume_partial_kernel, gp, dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, black, vp.pair, vp.f, a.targets, warped_dev, wgrad_dev,
+                           partials, (int)a.units, (int)a.Mt, a.tw, g.K, (int)g.NPt, (int)T, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(msiren::align_volume_combine_kernel, gc, dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
+        name = "align_volume_reduce_kernels";
+    } else if (a.fam == ALIGN_WEIGHTED) {  // sums_dev (n, 47)
+        hipLaunchKernelGGL(msiren::align_partial_w_kernel, gp, dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, black, a.targets, a.weights, a.intensity, warped_dev, wgrad_dev,
+                           partials, (int)a.n, (int)a.Mt, a.tw, g.K, (int)g.NPt, (int)T, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(msiren::align_combine_w_kernel, gc, dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
+        name = "align_reduce_w_kernels";
+    } else {  // sums_dev (n, 29)
+        hipLaunchKernelGGL(msiren::align_partial_kernel, gp, dim3(256), 0, st, rec, ap.ent, ap.tile, ap.w, black, a.targets, warped_dev, wgrad_dev, partials, (int)a.n,
+                           (int)a.Mt, a.tw, g.K, (int)g.NPt, (int)T, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(msiren::align_combine_kernel, gc, dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
+        name = "align_reduce_kernels";
+    }
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, a.M, name);
+}
+
+// sums_dev (n, 29) doubles; warped_dev (n, th, tw) and wgrad_dev (2, n, th, tw) may be null
+int align_slices(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    AlignPlan a;
+    bool todo;
+    const int rc = align_prepare(h, c, ALIGN_PLAIN, images_dev, n, height, width, targets_dev, n, th, tw, maps_dev, sums_dev, 0, &a, &todo);
+    if (rc || !todo) return rc;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+// sums_dev (n, 47); weights_dev (n, th, tw) and intensity_dev (n, 2) may be null
+int align_slices_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                   const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = align_w_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    if ((uintptr_t)weights_dev % 4 || (uintptr_t)intensity_dev % 4) return fail(MSIREN_E_INVALID, "device weights and intensity must be 4-byte aligned");
+    AlignPlan a;
+    bool todo;
+    rc = align_prepare(h, c, ALIGN_WEIGHTED, images_dev, n, height, width, targets_dev, n, th, tw, maps_dev, sums_dev, 0, &a, &todo);
+    if (rc || !todo) return rc;
+    a.weights = weights_dev, a.intensity = intensity_dev;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+// sums_dev (m, 56); warped_dev (m, th, tw) and wgrad_dev (3, m, th, tw) may be null
+int align_volume(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                 const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    if ((uintptr_t)warped_dev % 4 || (uintptr_t)wgrad_dev % 4) return fail(MSIREN_E_INVALID, "device warped and wgrad must be 4-byte aligned");
+    AlignPlan a;
+    bool todo;
+    const int rc = align_prepare(h, c, ALIGN_VOLUME, images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, sums_dev, 0, &a, &todo);
+    if (rc || !todo) return rc;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+// ---- the solves (DESIGN.md sections 5.11 - 5.13): align_prepare once, then `iterations` x (align_evaluate at the trial maps -> the family's step
+// kernel), all on the call's stream, no host sync in between.  State and the per-evaluation sums: the stream's scratch behind the partials
+// (align_plan.h: solve_layout), ensured before the prologue.
+// the Levenberg-Marquardt options the three option structs share
+static int lm_opts_check(int mode, int iterations, double damping, double down, double up, double lam_min, double lam_max) {
+    if (mode != 0 && mode != 1) return fail(MSIREN_E_INVALID, "mode = %d (0: affine, 1: rigid)", mode);
+    if (iterations < 1 || iterations > 256) return fail(MSIREN_E_INVALID, "iterations = %d outside 1 .. 256", iterations);
+    const double inf = __builtin_inf();
+    if (!(0.0 < lam_min && lam_min <= damping && damping <= lam_max && lam_max < inf))
+        return fail(MSIREN_E_INVALID, "damping: 0 < lam_min <= damping <= lam_max < inf is required (lam_min=%g, damping=%g, lam_max=%g)", lam_min, damping, lam_max);
+    if (!(0.0 < down && down <= 1.0) || !(1.0 <= up && up < inf)) return fail(MSIREN_E_INVALID, "0 < down <= 1 <= up < inf is required (down=%g, up=%g)", down, up);
+    return 0;
+}
+
+// the step kernel's parameters every family has, by name: the state sections at `base` and what the options and the caller give
+template <typename SP, typename O>
+static void solve_params(SP& sp, char* base, const msiren::SolveLayout& s, const O& o, float* maps_out, double* rigid_out, double* report, double* trace) {
+    sp.sums = (double*)(base + s.sums), sp.sums_best = (double*)(base + s.sums_best);
+    sp.rigid_trial = (double*)(base + s.rigid_trial), sp.rigid_best = (double*)(base + s.rigid_best), sp.scal = (double*)(base + s.scal);
+    sp.trial = (float*)(base + s.trial), sp.best = (float*)(base + s.best), sp.cnt = (int*)(base + s.cnt);
+    sp.trace = trace, sp.maps_out = maps_out, sp.rigid_out = rigid_out, sp.report = report;
+    sp.down = o.down, sp.up = o.up, sp.lam_min = o.lam_min, sp.lam_max = o.lam_max;
+}
+
+// the loop behind the family's init kernel: evaluation k at the trial maps, then `step` over the units as one profile entry `name`
+template <typename SP>
+static int solve_loop(msiren_handle h, const Call& c, const AlignPlan& a, SP& sp, int iterations, void (*step)(SP), const char* name) {
+    int rc;
+    hipStream_t st = h->sc[c.stream].s;
+    for (int k = 0; k < iterations; ++k) {
+        if ((rc = align_evaluate(h, c, a, sp.trial, const_cast<double*>(sp.sums), nullptr, nullptr))) return rc;
+        hipEvent_t e1 = nullptr;
+        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+        sp.k = k, sp.last = k == iterations - 1;
+        hipLaunchKernelGGL(step, dim3((unsigned)((a.units + 255) / 256)), dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        if ((rc = profile_end(h, c.stream, e1, a.units, name))) return rc;
+    }
+    return 0;
+}
+
+// align_solve_check: every refusal that needs no device pointer (the host-pointer form asks it before it stages anything)
+int align_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_opts* o, const void* maps_in,
+                      const void* rigid_in, const void* maps_out, const void* report) {
+    int rc = align_check(h, n, height, width, th, tw);
+    if (rc) return rc;
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_solve_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_solve_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_solve_opts));
+    if ((rc = lm_opts_check(o->mode, o->iterations, o->damping, o->down, o->up, o->lam_min, o->lam_max))) return rc;
+    if (o->mode == 1 && !(o->centre_y - o->centre_y == 0.0 && o->centre_x - o->centre_x == 0.0)) return fail(MSIREN_E_INVALID, "rigid mode: the centre must be finite");
+    if (n > 0 && (int64_t)th * tw > 0 && (!(o->mode == 1 ? rigid_in : maps_in) || !maps_out || !report))
+        return fail(MSIREN_E_INVALID, "null argument (%s)", !maps_out ? "maps_out" : !report ? "report" : o->mode == 1 ? "rigid_in: rigid mode" : "maps_in: affine mode");
+    return 0;
+}
+
+int align_solve(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                const msiren_align_solve_opts* o, const float* maps_in, const double* rigid_in, float* maps_out, double* rigid_out, double* report, double* trace) {
+    int rc = align_solve_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, report);
+    if (rc || n == 0 || (int64_t)th * tw == 0) return rc;
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)trace % 8)
+        return fail(MSIREN_E_INVALID, "device maps must be 4-byte aligned, rigid states, report and trace 8-byte aligned");
+    AlignPlan a;
+    bool todo;
+    if ((rc = align_prepare(h, c, ALIGN_PLAIN, images_dev, n, height, width, targets_dev, n, th, tw, maps_out, report, msiren::solve_layout(0, n, msiren::ALIGN_SUMS, 4, 6, false).total,
+                            &a, &todo)) || !todo)
+        return rc;
+    auto& sc = h->sc[c.stream];
+    msiren::AlignSolveParams sp{};
+    solve_params(sp, (char*)sc.ragged.p, msiren::solve_layout(a.lay.total, n, msiren::ALIGN_SUMS, 4, 6, false), *o, maps_out, rigid_out, report, trace);
+    sp.n = (int)n, sp.mode = o->mode, sp.cy = o->centre_y, sp.cx = o->centre_x;
+    hipLaunchKernelGGL(msiren::align_solve_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc.s, sp, maps_in, rigid_in, o->damping);
+    HIPCHK(hipGetLastError());
+    return solve_loop(h, c, a, sp, o->iterations, msiren::align_step_kernel, "align_step_kernel");
+}
+
+int align_solve_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw, const msiren_align_solve_w_opts* o, const void* maps_in,
+                        const void* rigid_in, const void* maps_out, const void* intensity_out, const void* report) {
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_solve_w_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_solve_w_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_solve_w_opts));
+    if (o->intensity_mode != 0 && o->intensity_mode != 1) return fail(MSIREN_E_INVALID, "intensity_mode = %d (0: fixed, 1: estimate)", o->intensity_mode);
+    const msiren_align_solve_opts base{(uint32_t)sizeof(msiren_align_solve_opts), o->mode, o->iterations, 0, o->damping, o->down, o->up, o->lam_min, o->lam_max,
+                                       o->centre_y, o->centre_x};
+    int rc = align_solve_check(h, n, height, width, th, tw, &base, maps_in, rigid_in, maps_out, report);  // (everything msiren_align_solve refuses)
+    if (rc || (rc = align_w_check(h, n, height, width, th, tw))) return rc;
+    if (n > 0 && (int64_t)th * tw > 0 && !intensity_out) return fail(MSIREN_E_INVALID, "null argument (intensity_out)");
+    return 0;
+}
+
+int align_solve_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int32_t th, int32_t tw,
+                  const msiren_align_solve_w_opts* o, const float* maps_in, const double* rigid_in, const float* weights_dev, const float* intensity_in, float* maps_out,
+                  float* intensity_out, double* rigid_out, double* report, double* trace) {
+    int rc = align_solve_w_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, intensity_out, report);
+    if (rc || n == 0 || (int64_t)th * tw == 0) return rc;
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_in % 4 ||
+        (uintptr_t)intensity_out % 4 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)trace % 8)
+        return fail(MSIREN_E_INVALID, "device maps, weights and intensity must be 4-byte aligned, rigid states, report and trace 8-byte aligned");
+    AlignPlan a;
+    bool todo;
+    if ((rc = align_prepare(h, c, ALIGN_WEIGHTED, images_dev, n, height, width, targets_dev, n, th, tw, maps_out, report,
+                            msiren::solve_layout(0, n, msiren::ALIGN_SUMS_W, 4, 6, true).total, &a, &todo)) || !todo)
+        return rc;
+    auto& sc = h->sc[c.stream];
+    char* const base = (char*)sc.ragged.p;
+    const msiren::SolveLayout s = msiren::solve_layout(a.lay.total, n, msiren::ALIGN_SUMS_W, 4, 6, true);
+    msiren::AlignSolveWParams sp{};
+    solve_params(sp, base, s, *o, maps_out, rigid_out, report, trace);
+    sp.gb_trial = (float*)(base + s.gb_trial), sp.gb_best = (float*)(base + s.gb_best), sp.intensity_out = intensity_out;
+    sp.n = (int)n, sp.mode = o->mode, sp.estimate = o->intensity_mode, sp.cy = o->centre_y, sp.cx = o->centre_x;
+    a.weights = weights_dev, a.intensity = sp.gb_trial;
+    hipLaunchKernelGGL(msiren::align_solve_init_w_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc.s, sp, maps_in, rigid_in, intensity_in, o->damping);
+    HIPCHK(hipGetLastError());
+    return solve_loop(h, c, a, sp, o->iterations, msiren::align_step_w_kernel, "align_step_w_kernel");
+}
+
+int align_volume_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_opts* o,
+                             const void* maps_in, const void* planes, const void* rigid_in, const void* maps_out, const void* report) {
+    int rc = align_volume_check(h, n, height, width, m, th, tw);
+    if (rc) return rc;
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_volume_solve_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_volume_solve_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_volume_solve_opts));
+    if ((rc = lm_opts_check(o->mode, o->iterations, o->damping, o->down, o->up, o->lam_min, o->lam_max))) return rc;
+    if (o->mode == 1 && !(o->spacing > 0.0 && o->spacing < __builtin_inf())) return fail(MSIREN_E_INVALID, "rigid mode: spacing = %g must be finite and > 0", o->spacing);
+    if (m > 0 && (int64_t)th * tw > 0 && (!(o->mode == 1 ? (rigid_in && planes) : maps_in != nullptr) || !maps_out || !report))
+        return fail(MSIREN_E_INVALID, "null argument (%s)", !maps_out ? "maps_out" : !report ? "report" : o->mode == 1 ? "planes or rigid_in: rigid mode" : "maps_in: affine mode");
+    return 0;
+}
+
+int align_volume_solve(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                       int32_t tw, const msiren_align_volume_solve_opts* o, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out,
+                       double* rigid_out, double* report, double* trace) {
+    int rc = align_volume_solve_check(h, n, height, width, m, th, tw, o, maps_in, planes, rigid_in, maps_out, report);
+    if (rc || m == 0 || (int64_t)th * tw == 0) return rc;
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)planes % 8 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 ||
+        (uintptr_t)report % 8 || (uintptr_t)trace % 8)
+        return fail(MSIREN_E_INVALID, "device maps must be 4-byte aligned, planes, rigid states, report and trace 8-byte aligned");
+    AlignPlan a;
+    bool todo;
+    if ((rc = align_prepare(h, c, ALIGN_VOLUME, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report,
+                            msiren::solve_layout(0, m, msiren::ALIGN_VOLUME_SUMS, 12, 9, false).total, &a, &todo)) || !todo)
+        return rc;
+    auto& sc = h->sc[c.stream];
+    msiren::AlignVolumeSolveParams sp{};
+    solve_params(sp, (char*)sc.ragged.p, msiren::solve_layout(a.lay.total, m, msiren::ALIGN_VOLUME_SUMS, 12, 9, false), *o, maps_out, rigid_out, report, trace);
+    sp.planes = planes, sp.m = (int)m, sp.spacing = o->spacing;
+    const bool rigid = o->mode == 1;  // the kernels are instantiated per mode
+    const dim3 gs((unsigned)((m + 255) / 256));
+    if (rigid) hipLaunchKernelGGL(msiren::align_volume_solve_init_kernel<msiren::ALIGN_VOLUME_RIGID>, gs, dim3(256), 0, sc.s, sp, maps_in, rigid_in, o->damping);
+    else hipLaunchKernelGGL(msiren::align_volume_solve_init_kernel<msiren::ALIGN_VOLUME_AFFINE>, gs, dim3(256), 0, sc.s, sp, maps_in, rigid_in, o->damping);
+    HIPCHK(hipGetLastError());
+    return solve_loop(h, c, a, sp, o->iterations, rigid ? msiren::align_volume_step_kernel<msiren::ALIGN_VOLUME_RIGID> : msiren::align_volume_step_kernel<msiren::ALIGN_VOLUME_AFFINE>,
+                      "align_volume_step_kernel");
+}
+
+}  // namespace mh
 
 using namespace mh;
 
 namespace {
+
+// What every host-pointer form of the geometry calls does between its family's check (`rc`: check(h), then that check) and its staging: the
+// empty call (*done, success), the null images / points / targets / outputs (`null_arg`), the pixel limit of one upload.
+int host_preamble(int rc, bool empty, bool null_arg, int64_t n, int32_t height, int32_t width, bool* done) {
+    *done = rc || empty;
+    if (*done) return rc;
+    if (null_arg) return fail(MSIREN_E_INVALID, "null argument");
+    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    return 0;
+}
 
 // what both forms check before anything is enqueued; `grad`: the jet's limits on the model (jet_supported)
 int check_ragged_args(msiren_ctx* h, const float* coords, const int32_t* offsets, const float* mods, int64_t B, int64_t T, const float* out, const float* grad_out,
@@ -71,11 +594,10 @@ int ragged_host(msiren_ctx* h, const float* coords_host, const int32_t* offsets_
 // the reconstruction at points, one synchronous one-chunk call on host pointers: images + points -> [out], [grad]
 int resample_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
                   float* grad_host, bool grad, bool native = false) {
+    bool done;
     int rc = check(h);
-    if (rc || (rc = resample_check(h, n, height, width, M, grad))) return rc;
-    if (n == 0 || M == 0) return 0;
-    if (!images_host || !points_host || (grad ? !grad_host : !out_host)) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    if ((rc = host_preamble(rc ? rc : resample_check(h, n, height, width, M, grad),
+                            n == 0 || M == 0, !images_host || !points_host || (grad ? !grad_host : !out_host), n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     auto& sc = h->sc[c.stream];
     const size_t ni = (size_t)n * height * width * sizeof(float), np = (size_t)M * 2 * sizeof(float), no = (size_t)n * M * sizeof(float);
@@ -93,11 +615,10 @@ int resample_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t he
 // a stack read as a volume at points (Z, Y, X), one synchronous one-chunk call on host pointers: images + points -> [out (M)], [grad (3, M)]
 int volume_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* points_host, int64_t M, float* out_host,
                 float* grad_host, bool grad, bool native = false) {
+    bool done;
     int rc = check(h);
-    if (rc || (rc = resample_volume_check(h, n, height, width, M, grad))) return rc;
-    if (n == 0 || M == 0) return 0;
-    if (!images_host || !points_host || (grad ? !grad_host : !out_host)) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    if ((rc = host_preamble(rc ? rc : resample_volume_check(h, n, height, width, M, grad),
+                            n == 0 || M == 0, !images_host || !points_host || (grad ? !grad_host : !out_host), n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     auto& sc = h->sc[c.stream];
     const size_t ni = (size_t)n * height * width * sizeof(float), np = (size_t)M * 3 * sizeof(float), no = (size_t)M * sizeof(float);
@@ -115,12 +636,11 @@ int volume_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t heig
 // slices scored under affine maps against targets, one synchronous one-chunk call on host pointers: images + targets + maps -> sums, [warped], [wgrad]
 int align_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
                const float* maps_host, double* sums_host, float* warped_host, float* wgrad_host) {
-    int rc = check(h);
-    if (rc || (rc = align_check(h, n, height, width, th, tw))) return rc;
     const int64_t M = (int64_t)th * tw;
-    if (n == 0 || M == 0) return 0;
-    if (!images_host || !targets_host || !maps_host || !sums_host) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_check(h, n, height, width, th, tw),
+                            n == 0 || M == 0, !images_host || !targets_host || !maps_host || !sums_host, n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)n * M * sizeof(float);
     SyncHostCall io(h, c.stream);
@@ -138,12 +658,11 @@ int align_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t heigh
 // device, maps, [rigid states], report and [trace] come back
 int align_solve_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
                      const msiren_align_solve_opts* o, const float* maps_in, const double* rigid_in, float* maps_out, double* rigid_out, double* report, double* trace) {
-    int rc = check(h);
-    if (rc || (rc = align_solve_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, report))) return rc;
     const int64_t M = (int64_t)th * tw;
-    if (n == 0 || M == 0) return 0;
-    if (!images_host || !targets_host) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_solve_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, report),
+                            n == 0 || M == 0, !images_host || !targets_host, n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)n * M * sizeof(float);
     const bool rigid = o->mode == 1;
@@ -162,12 +681,11 @@ int align_solve_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t
 // the weighted forms: as the two above; the weights and the intensities go up once per call
 int align_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
                  const float* maps_host, const float* weights_host, const float* intensity_host, double* sums_host, float* warped_host, float* wgrad_host) {
-    int rc = check(h);
-    if (rc || (rc = align_w_check(h, n, height, width, th, tw))) return rc;
     const int64_t M = (int64_t)th * tw;
-    if (n == 0 || M == 0) return 0;
-    if (!images_host || !targets_host || !maps_host || !sums_host) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_w_check(h, n, height, width, th, tw),
+                            n == 0 || M == 0, !images_host || !targets_host || !maps_host || !sums_host, n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)n * M * sizeof(float);
     SyncHostCall io(h, c.stream);
@@ -185,12 +703,11 @@ int align_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t hei
 int align_solve_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
                        const msiren_align_solve_w_opts* o, const float* maps_in, const double* rigid_in, const float* weights_host, const float* intensity_in,
                        float* maps_out, float* intensity_out, double* rigid_out, double* report, double* trace) {
-    int rc = check(h);
-    if (rc || (rc = align_solve_w_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, intensity_out, report))) return rc;
     const int64_t M = (int64_t)th * tw;
-    if (n == 0 || M == 0) return 0;
-    if (!images_host || !targets_host) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_solve_w_check(h, n, height, width, th, tw, o, maps_in, rigid_in, maps_out, intensity_out, report),
+                            n == 0 || M == 0, !images_host || !targets_host, n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)n * M * sizeof(float);
     const bool rigid = o->mode == 1;
@@ -211,12 +728,11 @@ int align_solve_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32
 // target slices scored against the stack read as a volume, one synchronous one-chunk call on host pointers
 int align_volume_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
                       const float* maps_host, double* sums_host, float* warped_host, float* wgrad_host) {
-    int rc = check(h);
-    if (rc || (rc = align_volume_check(h, n, height, width, m, th, tw))) return rc;
     const int64_t M = m * (int64_t)th * tw;
-    if (M == 0) return 0;
-    if (!images_host || !targets_host || !maps_host || !sums_host) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_volume_check(h, n, height, width, m, th, tw),
+                            M == 0, !images_host || !targets_host || !maps_host || !sums_host, n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
     SyncHostCall io(h, c.stream);
@@ -234,12 +750,11 @@ int align_volume_host(msiren_ctx* h, const float* images_host, int64_t n, int32_
 int align_volume_solve_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
                             const msiren_align_volume_solve_opts* o, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out, double* rigid_out,
                             double* report, double* trace) {
-    int rc = check(h);
-    if (rc || (rc = align_volume_solve_check(h, n, height, width, m, th, tw, o, maps_in, planes, rigid_in, maps_out, report))) return rc;
     const int64_t M = m * (int64_t)th * tw;
-    if (M == 0) return 0;
-    if (!images_host || !targets_host) return fail(MSIREN_E_INVALID, "null argument");
-    if (n * (int64_t)height * width > 0x1fffffffLL) return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices of %dx%d", (long long)n, height, width);
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_volume_solve_check(h, n, height, width, m, th, tw, o, maps_in, planes, rigid_in, maps_out, report),
+                            M == 0, !images_host || !targets_host, n, height, width, &done)) || done) return rc;
     Call c = make_call(h, true);
     const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
     const bool rigid = o->mode == 1;
@@ -371,6 +886,8 @@ int msiren_align_slices_dev(msiren_handle h, const float* images_dev, int64_t n,
                             const float* maps_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
     int rc = check(h);
     if (rc) return rc;
+    // As the resample entry points, and unlike the weighted, volume and solve forms above: no check in front of dev_call, so a call that
+    // align_check refuses has rotated the stream already.  Kept: which stream the next call takes is observable.
     return align_slices(h, dev_call(h), images_dev, n, height, width, targets_dev, th, tw, maps_dev, sums_dev, warped_dev, wgrad_dev);
 }
 
