@@ -38,7 +38,8 @@ extern "C" {
  * against targets: cost, gradient, JtJ); msiren_align_solve(_dev) and msiren_align_solve_opts (the damped Gauss-Newton loop around it, on the device);
  * msiren_align_slices_w(_dev), msiren_align_solve_w(_dev) and msiren_align_solve_w_opts (the same two with a per-pixel weight and a per-slice gain and bias);
  * msiren_align_volume(_dev), msiren_align_volume_solve(_dev) and msiren_align_volume_solve_opts (target slices scored against, and aligned to, the stack
- * read as a volume under 3 x 3 maps).
+ * read as a volume under 3 x 3 maps); msiren_align_volume_w(_dev), msiren_align_volume_solve_w(_dev) and msiren_align_volume_solve_w_opts (the same two
+ * with a per-pixel weight and a per-target gain and bias).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -635,6 +636,79 @@ MSIREN_API int msiren_align_volume_solve_dev(msiren_handle h, const float* image
                                              const double* planes_dev /* (m, 12), rigid */, const double* rigid_in_dev /* (m, 12), rigid */,
                                              float* maps_out_dev /* (m, 9) */, double* rigid_out_dev /* (m, 12) or NULL */,
                                              double* report_dev /* (m, 6) */, double* trace_dev /* (iterations, m, 11) or NULL */);
+
+/* Build-defined: msiren_align_volume with a per-pixel weight and a per-TARGET gain and bias.  Images, targets, maps, the
+ * point rule, R, gZ, gY, gX and the pipeline are msiren_align_volume's, unchanged.
+ *     weights (m, th, tw) float32 or NULL (every weight 1);   intensity (m, 2) float32 = (g, b) per target or NULL ((1, 0))
+ * A pixel is VALID iff msiren_align_volume's condition holds (T, R, gZ, gY, gX finite) and its weight is finite and > 0.  Per valid pixel, in fp64
+ * from the fp32 numbers, no fused multiply-add, in exactly this association:
+ *     mm = ((double)g (double)R) + (double)b        r = mm - (double)T
+ *     gz = (double)g (double)gZ     gy = (double)g (double)gY     gx = (double)g (double)gX
+ *     J  = (gz i, gz j, gz, gy i, gy j, gy, gx i, gx j, gx, (double)R, 1.0)       (parameter order: the map's nine, then g, b)
+ *     wr = w r
+ *     count += 1;  wsum += w;  cost += wr r;  dcost[a] += (2 wr) J[a];  jtj[a, b] += (w J[a]) J[b]  for a <= b
+ * sums (m, 80) float64 = [count, wsum, cost, dcost[0..10], jtj: the upper triangle packed row-major (66)].
+ * warped (m, th, tw) = R and wgrad (3, m, th, tw) = gZ, gY, gX are optional and are written BEFORE gain and bias: the bits of
+ * msiren_resample_volume_grad.  Every sum has msiren_align_slices' one order, so the determinism properties of msiren_align_volume hold.  With
+ * weights and intensity NULL the 56 entries the two calls share are msiren_align_volume's bits and wsum == count; a weight that is a power of
+ * two scales wsum, cost, dcost and jtj exactly; weights in {0, 1} equal NaN-masked targets.
+ * MSIREN_E_INVALID before any launch: what msiren_align_volume refuses; 32 M K + 8 M (M = m th tw) with 640 bytes per chunk of 1024 pixels not
+ * below 2^30; device weights or intensity not 4-byte aligned.  Under msiren_profile_enable: "align_volume_bin_kernels", the jet ragged trunk
+ * under its name, "align_volume_reduce_w_kernels". */
+MSIREN_API int msiren_align_volume_w(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                     const float* targets_host, int64_t m_targets, int32_t th, int32_t tw, const float* maps_host /* (m, 9) */,
+                                     const float* weights_host /* (m, th, tw) or NULL */, const float* intensity_host /* (m, 2) or NULL */,
+                                     double* sums_host /* (m, 80) */, float* warped_host /* or NULL */, float* wgrad_host /* (3, m, th, tw) or NULL */);
+MSIREN_API int msiren_align_volume_w_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                         const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw, const float* maps_dev /* (m, 9) */,
+                                         const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */,
+                                         double* sums_dev /* (m, 80) */, float* warped_dev /* or NULL */, float* wgrad_dev /* or NULL */);
+
+/* Build-defined: msiren_align_volume_solve's loop around msiren_align_volume_w -- the prologue once, then `iterations` x
+ * (bin -> jet ragged trunk -> the 80-sum reduce -> one step kernel), no host synchronisation.  intensity_mode 0 (fixed): (g, b) stay at their
+ * inputs and the solve is over 9 parameters (affine) or 6 (rigid); 1 (estimate): (g, b) are solved for with the map, over 11 (affine) or 8
+ * (rigid).  With P the number of solved parameters and sums (count, wsum, cost, g[11], H[11][11]) at the trial (map, g, b):
+ *     mean = cost / wsum if count >= P else +inf;       accept / reject, lam and the flags: msiren_align_solve's
+ *     affine, fixed     msiren_align_volume_solve's 9 x 9 system on g[0..8] and the leading 9 x 9 block of H
+ *     affine, estimate  the same expressions with 11 in place of 9;  trial[a] = (float)((double)best[a] + d[a]) for a < 9,
+ *                       g' = (float)((double)g_best + d[9]),  b' = (float)((double)b_best + d[10])
+ *     rigid, fixed      msiren_align_volume_solve's B (9 x 6), g6, H6 and Cayley update on the leading block
+ *     rigid, estimate   B (11 x 8): msiren_align_volume_solve's 9 x 6 block, then B[9][6] = B[10][7] = 1, every other entry 0;  g8 = B^T g,
+ *                       H8 = B^T (H B), every sum ascending from 0.0, zero entries included;  the Cayley update on d[0..2], u' = u + d[3..5];
+ *                       g' = (float)((double)g_best + d[6]),  b' = (float)((double)b_best + d[7])
+ * fp64 + - * / one at a time; mri_inr_amd/align_volume.py: lm_step_vw restates it in Python floats and gives the same bits.  With unit weights
+ * wsum == count, so with intensity_mode 0, no weights and no intensity the call returns msiren_align_volume_solve's maps, rigid states and the
+ * report and trace columns the two calls share.
+ * weights (m, th, tw) or NULL; intensity_in (m, 2) or NULL ((1, 0)).  maps_out (m, 9), intensity_out (m, 2): the best map and (g, b);
+ * rigid_out (m, 12) or NULL.  report (m, 7) float64: accepted, mean_first, mean_best, count at the best map, wsum at the best map, lam, flags.
+ * trace (iterations, m, 14) float64 or NULL: per evaluation the trial map (9), the trial g, b, then cost, count, wsum.
+ * A target that reads black slices only (R = 0 everywhere: SINGULAR) and a target whose weights mask every pixel (NO_OVERLAP) keep their inputs.
+ * MSIREN_E_INVALID with a message, before any launch: everything msiren_align_volume_solve refuses; struct_size !=
+ * sizeof(msiren_align_volume_solve_w_opts); intensity_mode not 0 or 1; a null intensity_out or report; what msiren_align_volume_w refuses; device
+ * weights or intensities not 4-byte aligned.  Under msiren_profile_enable: the prologue's entries once per call; "align_volume_bin_kernels", the
+ * jet ragged trunk, "align_volume_reduce_w_kernels" and "align_volume_step_w_kernel" `iterations` times. */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(msiren_align_volume_solve_w_opts) */
+    int32_t mode;             /* 0 affine, 1 rigid */
+    int32_t iterations;       /* evaluations, 1 .. 256 */
+    int32_t intensity_mode;   /* 0 fixed, 1 estimate */
+    double damping, down, up, lam_min, lam_max, spacing;
+} msiren_align_volume_solve_w_opts;
+MSIREN_API int msiren_align_volume_solve_w(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                           const float* targets_host, int64_t m_targets, int32_t th, int32_t tw,
+                                           const msiren_align_volume_solve_w_opts* opts, const float* maps_in /* (m, 9), affine */,
+                                           const double* planes /* (m, 12), rigid */, const double* rigid_in /* (m, 12), rigid */,
+                                           const float* weights /* (m, th, tw) or NULL */, const float* intensity_in /* (m, 2) or NULL */,
+                                           float* maps_out /* (m, 9) */, float* intensity_out /* (m, 2) */, double* rigid_out /* (m, 12) or NULL */,
+                                           double* report /* (m, 7) */, double* trace /* (iterations, m, 14) or NULL */);
+MSIREN_API int msiren_align_volume_solve_w_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                               const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw,
+                                               const msiren_align_volume_solve_w_opts* opts, const float* maps_in_dev /* (m, 9), affine */,
+                                               const double* planes_dev /* (m, 12), rigid */, const double* rigid_in_dev /* (m, 12), rigid */,
+                                               const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_in_dev /* (m, 2) or NULL */,
+                                               float* maps_out_dev /* (m, 9) */, float* intensity_out_dev /* (m, 2) */,
+                                               double* rigid_out_dev /* (m, 12) or NULL */, double* report_dev /* (m, 7) */,
+                                               double* trace_dev /* (iterations, m, 14) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

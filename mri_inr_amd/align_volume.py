@@ -1,6 +1,8 @@
 """Helpers for ``ModulatedSiren.align_volume_cost`` and ``align_volume_solve`` / ``align_volume_solve_rigid``: the 3 x 3
 maps target slices are read under in a stack taken as a volume, the call's packed sums, a Gauss-Newton step on them, and the step rule of
-msiren_align_volume_solve restated operation by operation (``lm_step_v``, ``solve_on_host_v``).  Pure numpy; the step rule in plain Python floats.
+msiren_align_volume_solve restated operation by operation (``lm_step_v``, ``solve_on_host_v``); below them the same for the weighted,
+gain/bias-compensated forms ``align_volume_cost_w`` / ``align_volume_solve_w`` / ``align_volume_solve_rigid_w`` (section 5.14: ``lm_step_vw``,
+``solve_on_host_vw``).  Pure numpy; the step rules in plain Python floats.
 
 A map is nine float32 numbers (z0, z1, tz, y0, y1, ty, x0, x1, tx): pixel (i, j) of the target lattice is read at
     Z = ((z0 i) + (z1 j)) + tz      Y = ((y0 i) + (y1 j)) + ty      X = ((x0 i) + (x1 j)) + tx
@@ -259,3 +261,192 @@ def solve_result_v(maps, rigid, report, trace):
         rotation, shift = rigid[:, :9].reshape(-1, 3, 3).copy(), rigid[:, 9:12].copy()
     return SolveResultV(maps, rotation, shift, report[:, 0].astype(np.int64), report[:, 1].copy(), report[:, 2].copy(), report[:, 3].astype(np.int64),
                         report[:, 4].copy(), report[:, 5].astype(np.int64), trace)
+
+
+# ---- weighted, gain/bias-compensated alignment to the volume (msiren_align_volume_w, msiren_align_volume_solve_w) ------------
+# Parameter order: the map's nine (z0, z1, tz, y0, y1, ty, x0, x1, tx), then g, b: the model of a target pixel is g R + b, every pixel carries a
+# weight w, every TARGET its own (g, b).
+SUMS_VW = 80  # count, wsum, cost, dcost[11], jtj packed upper triangle row-major [66]
+FIXED, ESTIMATE = 0, 1
+_IU11 = np.triu_indices(11)
+
+AlignResultVW = collections.namedtuple("AlignResultVW", "count wsum cost grad jtj warped wgrad")
+AlignResultVW.__doc__ = """count (m,) int64 valid pixels (finite, weight > 0), wsum (m,) the sum of their weights, cost (m,) sum w (g R + b - T)^2, grad
+(m, 11) its gradient over (z0, z1, tz, y0, y1, ty, x0, x1, tx, g, b), jtj (m, 11, 11) the weighted Gauss-Newton matrix (symmetric); warped
+(m, th, tw) / wgrad (3, m, th, tw) (R, gZ, gY, gX before gain and bias) or None."""
+
+SolveOptionsVW = collections.namedtuple("SolveOptionsVW", "mode iterations damping down up lam_min lam_max spacing intensity_mode",
+                                        defaults=(AFFINE, 12, 1e-3, 0.1, 10.0, 1e-9, 1e9, 1.0, ESTIMATE))
+SolveResultVW = collections.namedtuple("SolveResultVW", "maps rotation shift accepted mean_first mean_best count damping flags trace intensity wsum")
+SolveResultVW.__doc__ = """SolveResultV's fields (mean_* = cost / wsum; +inf: fewer valid pixels than solved parameters; trace (iterations, m, 14) or None:
+per evaluation the trial map, the trial g, b, cost, count, wsum), then intensity (m, 2) float32 the best (g, b) and wsum (m,) at the best map."""
+
+
+def unpack_vw(sums, warped=None, wgrad=None):
+    """sums (m, 80) float64 as msiren_align_volume_w writes them -> AlignResultVW (jtj unpacked to symmetric (m, 11, 11))"""
+    sums = np.asarray(sums, dtype=np.float64)
+    if sums.ndim != 2 or sums.shape[1] != SUMS_VW:
+        raise ValueError(f"expected sums of shape (m, {SUMS_VW}), got {sums.shape}")
+    m = len(sums)
+    jtj = np.zeros((m, 11, 11), np.float64)
+    jtj[:, _IU11[0], _IU11[1]] = sums[:, 14:]
+    jtj[:, _IU11[1], _IU11[0]] = sums[:, 14:]
+    return AlignResultVW(sums[:, 0].astype(np.int64), sums[:, 1].copy(), sums[:, 2].copy(), sums[:, 3:14].copy(), jtj, warped, wgrad)
+
+
+def gauss_newton_step_vw(result, damping=0.0, estimate_intensity=True):
+    """(m, 11) float64: per target the solution of (JtJ + damping diag(JtJ)) delta = -grad / 2 over all 11 parameters, or over the nine of the map
+    (the last two entries zero).  A target with fewer valid pixels than parameters, or a singular system, gives a zero step."""
+    m, P = len(result.count), 11 if estimate_intensity else 9
+    step = np.zeros((m, 11), np.float64)
+    for q in range(m):
+        if result.count[q] < P:
+            continue
+        H = result.jtj[q][:P, :P]
+        try:
+            step[q, :P] = np.linalg.solve(H + float(damping) * np.diag(np.diag(H)), -0.5 * result.grad[q][:P])
+        except np.linalg.LinAlgError:
+            pass
+    return step
+
+
+# msiren_align_volume_solve_w's step rule, one target, in Python floats as lm_step_v above -- what align_volume_step_w_kernel computes, bit for bit.
+def solved_parameters_vw(o):
+    """P: affine 9 / rigid 6, and the two of the intensity where they are estimated"""
+    return (6 if o.mode == RIGID else 9) + (2 if o.intensity_mode == ESTIMATE else 0)
+
+
+def lm_mean_vw(sums, P):
+    """cost / wsum where at least P pixels are valid, +inf otherwise"""
+    return sums[2] / sums[1] if sums[0] >= float(P) else INF
+
+
+def intensity_update_vw(gb, dg, db):
+    """(g', b') as float32 from the best (g, b) and the step's last two entries"""
+    return [_f32(gb[0] + dg), _f32(gb[1] + db)]
+
+
+def rigid_jacobian3_w(state, plane, spacing):
+    """B (11 x 8): rigid_jacobian3's 9 x 6 block, then d (g, b) / d (g, b) = 1, every other entry 0.0"""
+    B9 = rigid_jacobian3(state, plane, spacing)
+    B = [[0.0] * 8 for _ in range(11)]
+    for a in range(9):
+        for k in range(6):
+            B[a][k] = B9[a][k]
+    B[9][6] = 1.0
+    B[10][7] = 1.0
+    return B
+
+
+def lm_init_vw(o, map_in=None, rigid_in=None, plane=None, intensity_in=None):
+    """lm_init_v's state with gb_trial, gb_best (float32 as floats; None: (1, 0)) and sums of 80"""
+    st = lm_init_v(o, map_in, rigid_in, plane)
+    st["sums"] = [0.0] * SUMS_VW
+    st["gb_trial"] = [1.0, 0.0] if intensity_in is None else [_f32(x) for x in intensity_in]
+    st["gb_best"] = list(st["gb_trial"])
+    return st
+
+
+def lm_step_vw(st, sums, k, o):
+    """One target after evaluation k: ``sums`` (80) are msiren_align_volume_w's at (st["trial"], st["gb_trial"]).  Accept or reject, then propose
+    the next trial from the best state.  ``st`` is updated in place and returned."""
+    sums = [float(x) for x in sums]
+    est = o.intensity_mode == ESTIMATE
+    mean = lm_mean_vw(sums, solved_parameters_vw(o))
+    accept, counted, st["lam"] = lm_decide(k, mean, st["mean_best"], st["lam"], o)
+    if accept:
+        st["best"], st["rigid_best"], st["gb_best"], st["sums"], st["mean_best"] = list(st["trial"]), list(st["rigid_trial"]), list(st["gb_trial"]), sums, mean
+        if k == 0:
+            st["mean_first"] = mean
+        if counted:
+            st["accepted"] += 1
+    lam, bs = st["lam"], st["sums"]
+    N = 11 if est else 9  # the leading block of the 11 parameters the proposal reads
+    g = bs[3:14]
+    H = [[0.0] * 11 for _ in range(11)]
+    s = 14
+    for a in range(11):
+        for b in range(a, 11):
+            H[a][b] = H[b][a] = bs[s]
+            s += 1
+    if o.mode == AFFINE:
+        A = [row[:N] for row in H[:N]]
+        for a in range(N):
+            A[a][a] = H[a][a] + lam * H[a][a]
+        d, ok = ldl_solve(A, [-0.5 * g[a] for a in range(N)], N)
+        st["trial"] = [_f32(st["best"][a] + d[a]) for a in range(9)]
+        dg, db = (d[9], d[10]) if est else (0.0, 0.0)
+    else:
+        rb, pl, sp = st["rigid_best"], st["plane"], float(o.spacing)
+        Q = 8 if est else 6
+        B = rigid_jacobian3_w(rb, pl, sp) if est else rigid_jacobian3(rb, pl, sp)
+        gq = [0.0] * Q
+        for p in range(Q):
+            t = 0.0
+            for a in range(N):
+                t = t + B[a][p] * g[a]
+            gq[p] = t
+        T = [[0.0] * Q for _ in range(N)]
+        for a in range(N):
+            for p in range(Q):
+                t = 0.0
+                for b in range(N):
+                    t = t + H[a][b] * B[b][p]
+                T[a][p] = t
+        A = [[0.0] * Q for _ in range(Q)]
+        for p in range(Q):
+            for r in range(Q):
+                t = 0.0
+                for a in range(N):
+                    t = t + B[a][p] * T[a][r]
+                A[p][r] = t
+        for p in range(Q):
+            A[p][p] = A[p][p] + lam * A[p][p]
+        d, ok = ldl_solve(A, [-0.5 * gq[p] for p in range(Q)], Q)
+        Cay = cayley3([d[0] / 2.0, d[1] / 2.0, d[2] / 2.0])
+        rt = [0.0] * 12
+        for r in range(3):
+            for c in range(3):
+                rt[3 * r + c] = ((Cay[r][0] * rb[c]) + (Cay[r][1] * rb[3 + c])) + (Cay[r][2] * rb[6 + c])
+        for a in range(3):
+            rt[9 + a] = rb[9 + a] + d[3 + a]
+        st["rigid_trial"] = rt
+        st["trial"] = rigid_map3(rt, pl, sp)
+        dg, db = (d[6], d[7]) if est else (0.0, 0.0)
+    st["gb_trial"] = intensity_update_vw(st["gb_best"], dg, db) if est else list(st["gb_best"])
+    st["flags"] = (0 if ok else SINGULAR) | (NO_OVERLAP if st["mean_first"] == INF else 0)
+    return st
+
+
+def solve_on_host_vw(cost_fn, m, *, maps=None, rigid=None, planes=None, intensity=None, options=SolveOptionsVW(), trace=False):
+    """msiren_align_volume_solve_w's loop around any ``cost_fn(maps (m, 9) float32, intensity (m, 2) float32) -> sums (m, 80)``:
+    ``options.iterations`` evaluations, ``lm_step_vw`` per target after each.  -> (SolveResultVW, rigid (m, 12) float64 best states)"""
+    o = options
+    st = [lm_init_vw(o, None if maps is None else maps[q], None if rigid is None else rigid[q], None if planes is None else planes[q],
+                     None if intensity is None else intensity[q]) for q in range(m)]
+    tr = np.zeros((o.iterations, m, 14), np.float64) if trace else None
+    for k in range(o.iterations):
+        trial = np.array([x["trial"] for x in st], np.float32).reshape(m, 9)
+        gb = np.array([x["gb_trial"] for x in st], np.float32).reshape(m, 2)
+        sums = np.asarray(cost_fn(trial, gb), np.float64).reshape(m, SUMS_VW)
+        if trace:
+            tr[k, :, :9], tr[k, :, 9:11], tr[k, :, 11], tr[k, :, 12], tr[k, :, 13] = trial, gb, sums[:, 2], sums[:, 0], sums[:, 1]
+        for q in range(m):
+            lm_step_vw(st[q], sums[q], k, o)
+    rb = np.array([x["rigid_best"] for x in st], np.float64).reshape(m, 12)
+    return solve_result_vw(np.array([x["best"] for x in st], np.float32).reshape(m, 9), np.array([x["gb_best"] for x in st], np.float32).reshape(m, 2),
+                           rb if o.mode == RIGID else None, report_vw(st), tr), rb
+
+
+def report_vw(states):
+    """the (m, 7) report of msiren_align_volume_solve_w from the states of lm_step_vw"""
+    return np.array([[x["accepted"], x["mean_first"], x["mean_best"], x["sums"][0], x["sums"][1], x["lam"], x["flags"]] for x in states], np.float64).reshape(len(states), 7)
+
+
+def solve_result_vw(maps, intensity, rigid, report, trace):
+    """what msiren_align_volume_solve_w writes -> SolveResultVW"""
+    rotation = shift = None
+    if rigid is not None:
+        rotation, shift = rigid[:, :9].reshape(-1, 3, 3).copy(), rigid[:, 9:12].copy()
+    return SolveResultVW(maps, rotation, shift, report[:, 0].astype(np.int64), report[:, 1].copy(), report[:, 2].copy(), report[:, 3].astype(np.int64),
+                         report[:, 5].copy(), report[:, 6].astype(np.int64), trace, intensity, report[:, 4].copy())

@@ -1,5 +1,5 @@
 // Scratch layouts and size limits of the geometry calls (plain C++, no HIP: unit-tested on the CPU by tests/test_align_plan.py): the five
-// pipelines of resample.hip -- resample, resample-volume, align, align-w, align-volume -- and the state of the three solves.  Every call
+// pipelines of resample.hip -- resample, resample-volume, align, align-w, align-volume (and its weighted form) -- and the state of the four solves.  Every call
 // carves one block of its stream's scratch, in this order, offsets in bytes:
 //     [counts B][cursors B][offsets B + 1][items B + 1][ent E][tile S][pair P]  ints, padded to an even count
 //     [coords 2 E][w S][f P]                                                    floats; coords are float2: 8-byte aligned
@@ -10,6 +10,7 @@
 //     resample-volume   B = n nV nH    E = 2 M K, S = M K      P = M
 //     align, align-w    B = n nV nH    E = S = n th tw K       P = 0          R = n chunks, chunks = ceil(th tw / 1024), 29 / 47 sums
 //     align-volume      B = n nV nH    E = 2 M K, S = M K      P = M = m th tw, R = m chunks, 56 sums
+//     align-volume-w    align-volume's, with 80 sums (640 bytes per partial record)
 // The memset in front of the count kernel covers counts and cursors: zero_bytes.  The limits keep every buffer of a call below 2^31 bytes and
 // every index in 32 bits; the bin scratch over the points and over the bins stays below 2^30 each.
 #pragma once
@@ -50,7 +51,7 @@ inline GeomLayout align_volume_layout(int64_t NP, int64_t m, int64_t Mt, int K, 
 
 // A solve's state per unit (slice or target) behind `base` = GeomLayout::total, a multiple of 8: the doubles, then the 4-byte words.
 //     [sums u nsums][sums_best u nsums][rigid_trial u nrigid][rigid_best u nrigid][scal u 3] [trial u nmap][best u nmap][gb_trial u 2][gb_best u 2][cnt u 2]
-// align: (29, 4, 6), align-w: (47, 4, 6) with the (gain, bias) pair, align-volume: (56, 12, 9)
+// align: (29, 4, 6), align-w: (47, 4, 6) with the (gain, bias) pair, align-volume: (56, 12, 9), align-volume-w: (80, 12, 9) with the pair
 struct SolveLayout {
     size_t sums, sums_best, rigid_trial, rigid_best, scal, trial, best, gb_trial, gb_best, cnt;  // gb_*: = cnt without the pair
     size_t total;  // from the start of the scratch

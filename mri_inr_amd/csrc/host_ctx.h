@@ -19,9 +19,10 @@
 //                          msiren_resample_volume* (a stack read as a volume; resample_volume.hip.h), msiren_align_slices* (slices scored
 //                          under affine maps against targets; align.hip.h), msiren_align_solve* (the damped Gauss-Newton loop around it),
 //                          msiren_align_slices_w* / msiren_align_solve_w* (the two with a per-pixel weight and a per-slice gain and bias; align_w.hip.h),
-//                          msiren_align_volume* / msiren_align_volume_solve* (target slices against the stack read as a volume, 3 x 3 maps; align_volume.hip.h).
+//                          msiren_align_volume* / msiren_align_volume_solve* (target slices against the stack read as a volume, 3 x 3 maps; align_volume.hip.h),
+//                          msiren_align_volume_w* / msiren_align_volume_solve_w* (those two with a per-pixel weight and a per-target gain and bias; align_volume_w.hip.h).
 //                          The whole of these families lives here: checks, pipelines on the call's stream, host-pointer forms, entry points,
-//                          and the only inclusion of their five kernel headers
+//                          and the only inclusion of their six kernel headers
 //     align_plan.h         the scratch layouts and size limits of those calls: pure functions, no HIP (tests/test_align_plan.py)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
@@ -299,6 +300,18 @@ int align_volume_solve_check(msiren_ctx* h, int64_t n, int32_t height, int32_t w
 int align_volume_solve(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
                        int32_t tw, const msiren_align_volume_solve_opts* o, const float* maps_in, const double* planes, const double* rigid_in, float* maps_out,
                        double* rigid_out, double* report, double* trace);
+// msiren_align_volume_w* and msiren_align_volume_solve_w* (align_volume_w.hip.h): the same pipeline with a per-pixel weight and a
+// per-target (gain, bias); weights_dev (m, th, tw) and intensity (m, 2) may be null; sums_dev (m, 80) doubles.  The checks as above;
+// align_volume_w_check also sizes the larger partial records.
+constexpr int kAlignVolumeSumsW = 80;  // doubles per target: count, wsum, cost, dcost[11], jtj[66] (align_volume_w.hip.h: ALIGN_VOLUME_SUMS_W)
+int align_volume_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw);
+int align_volume_w(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                   const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev);
+int align_volume_solve_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_w_opts* o,
+                               const void* maps_in, const void* planes, const void* rigid_in, const void* maps_out, const void* intensity_out, const void* report);
+int align_volume_solve_w(msiren_ctx* h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                         int32_t tw, const msiren_align_volume_solve_w_opts* o, const float* maps_in, const double* planes, const double* rigid_in, const float* weights_dev,
+                         const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report, double* trace);
 
 // sample_grid.hip
 // the call evaluates and folds the lattice of out_stride (built on first use); table = false: without the 16-bit trunks' layer-0 table

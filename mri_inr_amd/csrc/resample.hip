@@ -3,7 +3,8 @@
 // (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
 // The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
 // msiren_resample_slices*, msiren_resample_volume*, msiren_align_slices*, msiren_align_solve* and their weighted forms msiren_align_slices_w*,
-// msiren_align_solve_w*, and msiren_align_volume*, msiren_align_volume_solve* (DESIGN.md sections 5.8 - 5.13) are built on these trunks: the five
+// msiren_align_solve_w*, msiren_align_volume*, msiren_align_volume_solve* and their weighted forms msiren_align_volume_w*, msiren_align_volume_solve_w*
+// (DESIGN.md sections 5.8 - 5.14) are built on these trunks: the five
 // geometry pipelines below (namespace mh), each behind launch_dispatch.hip's slice_prologue on the call's stream, then their host-pointer forms
 // and the entry points.  Where each call's scratch sections lie and what it refuses as too large: align_plan.h.
 #include "host_buffers.h"
@@ -14,11 +15,13 @@
 #include "align.hip.h"
 #include "align_w.hip.h"
 #include "align_volume.hip.h"
+#include "align_volume_w.hip.h"
 
 namespace mh {
 
 static_assert(kAlignSums == msiren::ALIGN_SUMS && kAlignSumsW == msiren::ALIGN_SUMS_W && kAlignVolumeSums == msiren::ALIGN_VOLUME_SUMS,
               "host and kernels disagree about a record");
+static_assert(kAlignVolumeSumsW == msiren::ALIGN_VOLUME_SUMS_W, "host and kernels disagree about a record");
 static_assert(msiren::kAlignChunk == msiren::ALIGN_CHUNK, "align_plan.h and the kernels disagree about a chunk");
 
 // ---- what the five pipelines share ------------------------------------------------------------------------------------------------------------
@@ -185,14 +188,18 @@ int resample_volume(msiren_handle h, const Call& c, const float* images_dev, int
     return profile_end(h, c.stream, e1, M, "resample_volume_blend_kernel");
 }
 
-// ---- the three align families (DESIGN.md sections 5.10 - 5.13; kernels: align.hip.h, align_w.hip.h, align_volume.hip.h) ----------------------------
+// ---- the four align families (DESIGN.md sections 5.10 - 5.14; kernels: align.hip.h, align_w.hip.h, align_volume.hip.h, align_volume_w.hip.h) --------
 // Slices scored under one 2 x 3 map each against their targets (plain: 29 fp64 sums per slice; weighted: 47, with a per-pixel weight and a
-// per-slice gain and bias), or m targets under one 3 x 3 map each against the stack read as a volume (56 per target).  One path: the slice
+// per-slice gain and bias), or m targets under one 3 x 3 map each against the stack read as a volume (56 per target; weighted: 80, with a
+// per-pixel weight and a per-target gain and bias).  One path: the slice
 // prologue over the n slices, then per evaluation on the same stream the pixels of every target lattice, placed by their map in the kernel,
 // binned by (slice, tile) -> the exact-fp32 jet ragged trunk over those n nV nH bins, one replica, on the plan's rows -> per (unit, chunk) the
 // blend and the sums -> per unit the chunks in index order.  A unit is a slice (plain, weighted) or a target (volume).
-enum AlignFamily { ALIGN_PLAIN, ALIGN_WEIGHTED, ALIGN_VOLUME };
-static int align_nsums(AlignFamily f) { return f == ALIGN_PLAIN ? msiren::ALIGN_SUMS : f == ALIGN_WEIGHTED ? msiren::ALIGN_SUMS_W : msiren::ALIGN_VOLUME_SUMS; }
+enum AlignFamily { ALIGN_PLAIN, ALIGN_WEIGHTED, ALIGN_VOLUME, ALIGN_VOLUME_WEIGHTED };
+static int align_nsums(AlignFamily f) {
+    return f == ALIGN_PLAIN ? msiren::ALIGN_SUMS : f == ALIGN_WEIGHTED ? msiren::ALIGN_SUMS_W : f == ALIGN_VOLUME ? msiren::ALIGN_VOLUME_SUMS : msiren::ALIGN_VOLUME_SUMS_W;
+}
+static bool align_is_volume(AlignFamily f) { return f == ALIGN_VOLUME || f == ALIGN_VOLUME_WEIGHTED; }
 
 int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
     int rc;
@@ -232,6 +239,17 @@ int align_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, 
     return 0;
 }
 
+// the weighted volume form's partial records are 640 bytes per chunk: the bin scratch and they stay below 2^30 together
+int align_volume_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw) {
+    int rc = align_volume_check(h, n, height, width, m, th, tw);
+    if (rc) return rc;
+    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
+    if (!msiren::align_volume_pixels_fit(m, (int64_t)th * tw, K, msiren::ALIGN_VOLUME_SUMS_W))
+        return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld targets x %d x %d pixels x %d covering tiles (32 m th tw K + 8 m th tw with 640 bytes per chunk of 1024 pixels must stay below 2^30)",
+                    (long long)m, th, tw, K);
+    return 0;
+}
+
 // What align_prepare leaves for align_evaluate: the call's geometry, its scratch layout and the trunk's call state.  Nothing of it lives on the handle.
 struct AlignPlan {
     AlignFamily fam = ALIGN_PLAIN;
@@ -240,7 +258,7 @@ struct AlignPlan {
     Geom g;
     msiren::GeomLayout lay{};  // lay.total: what follows in the stream's scratch is the solve's
     const float* targets = nullptr;
-    const float *weights = nullptr, *intensity = nullptr;  // weighted: (n, th, tw) and (n, 2), may be null
+    const float *weights = nullptr, *intensity = nullptr;  // weighted: (units, th, tw) and (units, 2), may be null
     Call pc;
 };
 
@@ -249,7 +267,7 @@ struct AlignPlan {
 static int align_prepare(msiren_handle h, const Call& c, AlignFamily fam, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev,
                          int64_t units, int32_t th, int32_t tw, const void* maps_dev, const void* sums_dev, size_t extra, AlignPlan* a, bool* todo) {
     *todo = false;
-    const bool volume = fam == ALIGN_VOLUME;
+    const bool volume = align_is_volume(fam);
     int rc = volume ? align_volume_check(h, n, height, width, units, th, tw) : align_check(h, n, height, width, th, tw);
     if (rc) return rc;
     const int64_t Mt = (int64_t)th * tw, M = units * Mt;
@@ -283,7 +301,7 @@ static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, co
     msiren::AlignVolumeParams avp{};
     msiren::ResampleVolumeParams& vp = avp.v;
     msiren::AlignParams ap{maps_dev, (int)a.n, a.th, a.tw, (int)a.Mt, g.nV, g.nH, h->S, h->I, (h->S - h->I) / 2, g.KA};
-    if (a.fam == ALIGN_VOLUME) {
+    if (align_is_volume(a.fam)) {
         vp = msiren::ResampleVolumeParams{nullptr, (int)a.M, (int)a.n, g.nV, g.nH, h->S, h->I, (h->S - h->I) / 2, g.KA, 1};
         avp.maps = maps_dev, avp.th = a.th, avp.tw = a.tw, avp.Mt = (int)a.Mt;
         carve_volume(vp, base, a.lay);
@@ -301,7 +319,13 @@ static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, co
     if ((rc = launch_trunk_f32_jet_ragged(h, a.pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, pixel_gscale(h))) || (rc = profile_begin(h, c.stream, &e1))) return rc;
     const dim3 gp((unsigned)(a.units * a.chunks)), gc((unsigned)a.units);
     const char* name;
-    if (a.fam == ALIGN_VOLUME) {  // sums_dev (m, 56)
+    if (a.fam == ALIGN_VOLUME_WEIGHTED) {  // sums_dev (m, 80)
+        hipLaunchKernelGGL(msiren::align_volume_partial_w_kernel, gp, dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, black, vp.pair, vp.f, a.targets, a.weights, a.intensity,
+                           warped_dev, wgrad_dev, partials, (int)a.units, (int)a.Mt, a.tw, g.K, (int)g.NPt, (int)T, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(msiren::align_volume_combine_w_kernel, gc, dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
+        name = "align_volume_reduce_w_kernels";
+    } else if (a.fam == ALIGN_VOLUME) {  // sums_dev (m, 56)
         hipLaunchKernelGGL(msiren::align_volume_partial_kernel, gp, dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, black, vp.pair, vp.f, a.targets, warped_dev, wgrad_dev,
                            partials, (int)a.units, (int)a.Mt, a.tw, g.K, (int)g.NPt, (int)T, (int)a.chunks);
         HIPCHK(hipGetLastError());
@@ -359,7 +383,22 @@ int align_volume(msiren_handle h, const Call& c, const float* images_dev, int64_
     return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
 }
 
-// ---- the solves (DESIGN.md sections 5.11 - 5.13): align_prepare once, then `iterations` x (align_evaluate at the trial maps -> the family's step
+// sums_dev (m, 80); weights_dev (m, th, tw) and intensity_dev (m, 2) may be null
+int align_volume_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                   const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = align_volume_w_check(h, n, height, width, m, th, tw);
+    if (rc) return rc;
+    if ((uintptr_t)warped_dev % 4 || (uintptr_t)wgrad_dev % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_dev % 4)
+        return fail(MSIREN_E_INVALID, "device warped, wgrad, weights and intensity must be 4-byte aligned");
+    AlignPlan a;
+    bool todo;
+    rc = align_prepare(h, c, ALIGN_VOLUME_WEIGHTED, images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, sums_dev, 0, &a, &todo);
+    if (rc || !todo) return rc;
+    a.weights = weights_dev, a.intensity = intensity_dev;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+// ---- the solves (DESIGN.md sections 5.11 - 5.14): align_prepare once, then `iterations` x (align_evaluate at the trial maps -> the family's step
 // kernel), all on the call's stream, no host sync in between.  State and the per-evaluation sums: the stream's scratch behind the partials
 // (align_plan.h: solve_layout), ensured before the prologue.
 // the Levenberg-Marquardt options the three option structs share
@@ -516,6 +555,53 @@ int align_volume_solve(msiren_handle h, const Call& c, const float* images_dev, 
     HIPCHK(hipGetLastError());
     return solve_loop(h, c, a, sp, o->iterations, rigid ? msiren::align_volume_step_kernel<msiren::ALIGN_VOLUME_RIGID> : msiren::align_volume_step_kernel<msiren::ALIGN_VOLUME_AFFINE>,
                       "align_volume_step_kernel");
+}
+
+int align_volume_solve_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_w_opts* o,
+                               const void* maps_in, const void* planes, const void* rigid_in, const void* maps_out, const void* intensity_out, const void* report) {
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_volume_solve_w_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_volume_solve_w_opts.struct_size = %u, this library's is %u", o->struct_size, (unsigned)sizeof(msiren_align_volume_solve_w_opts));
+    if (o->intensity_mode != 0 && o->intensity_mode != 1) return fail(MSIREN_E_INVALID, "intensity_mode = %d (0: fixed, 1: estimate)", o->intensity_mode);
+    const msiren_align_volume_solve_opts base{(uint32_t)sizeof(msiren_align_volume_solve_opts), o->mode, o->iterations, 0, o->damping, o->down, o->up, o->lam_min, o->lam_max,
+                                              o->spacing};
+    int rc = align_volume_solve_check(h, n, height, width, m, th, tw, &base, maps_in, planes, rigid_in, maps_out, report);  // (everything msiren_align_volume_solve refuses)
+    if (rc || (rc = align_volume_w_check(h, n, height, width, m, th, tw))) return rc;
+    if (m > 0 && (int64_t)th * tw > 0 && !intensity_out) return fail(MSIREN_E_INVALID, "null argument (intensity_out)");
+    return 0;
+}
+
+int align_volume_solve_w(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                         int32_t tw, const msiren_align_volume_solve_w_opts* o, const float* maps_in, const double* planes, const double* rigid_in, const float* weights_dev,
+                         const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report, double* trace) {
+    int rc = align_volume_solve_w_check(h, n, height, width, m, th, tw, o, maps_in, planes, rigid_in, maps_out, intensity_out, report);
+    if (rc || m == 0 || (int64_t)th * tw == 0) return rc;
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_in % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_in % 4 ||
+        (uintptr_t)intensity_out % 4 || (uintptr_t)planes % 8 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)trace % 8)
+        return fail(MSIREN_E_INVALID, "device maps, weights and intensity must be 4-byte aligned, planes, rigid states, report and trace 8-byte aligned");
+    AlignPlan a;
+    bool todo;
+    if ((rc = align_prepare(h, c, ALIGN_VOLUME_WEIGHTED, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report,
+                            msiren::solve_layout(0, m, msiren::ALIGN_VOLUME_SUMS_W, 12, 9, true).total, &a, &todo)) || !todo)
+        return rc;
+    auto& sc = h->sc[c.stream];
+    char* const base = (char*)sc.ragged.p;
+    const msiren::SolveLayout s = msiren::solve_layout(a.lay.total, m, msiren::ALIGN_VOLUME_SUMS_W, 12, 9, true);
+    msiren::AlignVolumeSolveWParams sp{};
+    solve_params(sp, base, s, *o, maps_out, rigid_out, report, trace);
+    sp.gb_trial = (float*)(base + s.gb_trial), sp.gb_best = (float*)(base + s.gb_best), sp.intensity_out = intensity_out;
+    sp.planes = planes, sp.m = (int)m, sp.spacing = o->spacing;
+    a.weights = weights_dev, a.intensity = sp.gb_trial;
+    const bool rigid = o->mode == 1, est = o->intensity_mode == 1;  // the kernels are instantiated per mode; the step also per intensity mode
+    const dim3 gs((unsigned)((m + 255) / 256));
+    if (rigid) hipLaunchKernelGGL(msiren::align_volume_solve_init_w_kernel<msiren::ALIGN_VOLUME_RIGID>, gs, dim3(256), 0, sc.s, sp, maps_in, rigid_in, intensity_in, o->damping);
+    else hipLaunchKernelGGL(msiren::align_volume_solve_init_w_kernel<msiren::ALIGN_VOLUME_AFFINE>, gs, dim3(256), 0, sc.s, sp, maps_in, rigid_in, intensity_in, o->damping);
+    HIPCHK(hipGetLastError());
+    void (*const step)(msiren::AlignVolumeSolveWParams) =
+        rigid ? (est ? msiren::align_volume_step_w_kernel<msiren::ALIGN_VOLUME_RIGID, 1> : msiren::align_volume_step_w_kernel<msiren::ALIGN_VOLUME_RIGID, 0>)
+              : (est ? msiren::align_volume_step_w_kernel<msiren::ALIGN_VOLUME_AFFINE, 1> : msiren::align_volume_step_w_kernel<msiren::ALIGN_VOLUME_AFFINE, 0>);
+    return solve_loop(h, c, a, sp, o->iterations, step, "align_volume_step_w_kernel");
 }
 
 }  // namespace mh
@@ -771,9 +857,91 @@ int align_volume_solve_host(msiren_ctx* h, const float* images_host, int64_t n, 
     return io.finish();
 }
 
+// the weighted volume forms: as the two above; the weights and the intensities go up once per call
+int align_volume_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                        const float* maps_host, const float* weights_host, const float* intensity_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    const int64_t M = m * (int64_t)th * tw;
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_volume_w_check(h, n, height, width, m, th, tw),
+                            M == 0, !images_host || !targets_host || !maps_host || !sums_host, n, height, width, &done)) || done) return rc;
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)m * 9 * sizeof(float), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_host, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_s = io.out(sums_host, (size_t)m * kAlignVolumeSumsW * sizeof(double), HOST_IN_PLACE);
+    const int o_w = io.out(warped_host, nt, HOST_IN_PLACE), o_g = io.out(wgrad_host, 3 * nt, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_volume_w(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, io.src<float>(i_m), io.src<float>(i_w), io.src<float>(i_gb),
+                             io.dst<double>(o_s), io.dst<float>(o_w), io.dst<float>(o_g))))
+        return rc;
+    return io.finish();
+}
+
+int align_volume_solve_w_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                              const msiren_align_volume_solve_w_opts* o, const float* maps_in, const double* planes, const double* rigid_in, const float* weights_host,
+                              const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report, double* trace) {
+    const int64_t M = m * (int64_t)th * tw;
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_volume_solve_w_check(h, n, height, width, m, th, tw, o, maps_in, planes, rigid_in, maps_out, intensity_out, report),
+                            M == 0, !images_host || !targets_host, n, height, width, &done)) || done) return rc;
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    const bool rigid = o->mode == 1;
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY);
+    // six inputs at most per call (SyncHostCall): the start is the maps (affine) or the planes and the states (rigid), never all three
+    const int i_s = rigid ? io.in(planes, (size_t)m * 12 * sizeof(double), HOST_COPY) : io.in(maps_in, (size_t)m * 9 * sizeof(float), HOST_COPY);
+    const int i_r = io.in(rigid ? rigid_in : nullptr, (size_t)m * 12 * sizeof(double), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_in, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_m = io.out(maps_out, (size_t)m * 9 * sizeof(float), HOST_COPY), o_gb = io.out(intensity_out, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_r = io.out(rigid_out, (size_t)m * 12 * sizeof(double), HOST_COPY);
+    const int o_rep = io.out(report, (size_t)m * 7 * sizeof(double), HOST_COPY), o_tr = io.out(trace, (size_t)o->iterations * m * 14 * sizeof(double), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_volume_solve_w(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, o, rigid ? nullptr : io.src<float>(i_s), rigid ? io.src<double>(i_s) : nullptr,
+                                   io.src<double>(i_r), io.src<float>(i_w), io.src<float>(i_gb), io.dst<float>(o_m), io.dst<float>(o_gb), io.dst<double>(o_r), io.dst<double>(o_rep),
+                                   io.dst<double>(o_tr))))
+        return rc;
+    return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
+
+int msiren_align_volume_w(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                          const float* maps_host, const float* weights_host, const float* intensity_host, double* sums_host, float* warped_host, float* wgrad_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_volume_w_host(h, images_host, n, height, width, targets_host, m, th, tw, maps_host, weights_host, intensity_host, sums_host, warped_host, wgrad_host);
+}
+int msiren_align_volume_w_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                              const float* maps_dev, const float* weights_dev, const float* intensity_dev, double* sums_dev, float* warped_dev, float* wgrad_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_volume_w_check(h, n, height, width, m, th, tw))) return rc;  // (before the stream rotates)
+    return align_volume_w(h, dev_call(h), images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, weights_dev, intensity_dev, sums_dev, warped_dev, wgrad_dev);
+}
+int msiren_align_volume_solve_w(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th,
+                                int32_t tw, const msiren_align_volume_solve_w_opts* opts, const float* maps_in, const double* planes, const double* rigid_in,
+                                const float* weights_host, const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report,
+                                double* trace) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_volume_solve_w_host(h, images_host, n, height, width, targets_host, m, th, tw, opts, maps_in, planes, rigid_in, weights_host, intensity_in, maps_out,
+                                     intensity_out, rigid_out, report, trace);
+}
+int msiren_align_volume_solve_w_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                                    int32_t tw, const msiren_align_volume_solve_w_opts* opts, const float* maps_in_dev, const double* planes_dev, const double* rigid_in_dev,
+                                    const float* weights_dev, const float* intensity_in_dev, float* maps_out_dev, float* intensity_out_dev, double* rigid_out_dev,
+                                    double* report_dev, double* trace_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_volume_solve_w_check(h, n, height, width, m, th, tw, opts, maps_in_dev, planes_dev, rigid_in_dev, maps_out_dev, intensity_out_dev, report_dev)))
+        return rc;  // (before the stream rotates)
+    return align_volume_solve_w(h, dev_call(h), images_dev, n, height, width, targets_dev, m, th, tw, opts, maps_in_dev, planes_dev, rigid_in_dev, weights_dev, intensity_in_dev,
+                                maps_out_dev, intensity_out_dev, rigid_out_dev, report_dev, trace_dev);
+}
 
 int msiren_align_slices_w(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int32_t th, int32_t tw,
                           const float* maps_host, const float* weights_host, const float* intensity_host, double* sums_host, float* warped_host, float* wgrad_host) {

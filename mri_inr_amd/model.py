@@ -1110,6 +1110,98 @@ class ModulatedSiren:
         rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
         return self._align_volume_solve(images, targets, align.RIGID, None, pl, rigid, spacing, iterations, damping, down, up, lam_min, lam_max, trace)
 
+    @staticmethod
+    def _align_volume_w_inputs(images, targets, weights, intensity):
+        """-> (images, targets, weights or None, intensity or None) as contiguous float32, shapes checked"""
+        def f32(x):
+            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+
+        a, t = ModulatedSiren._align_volume_inputs(images, targets)
+        w = None if weights is None else f32(weights)
+        if w is not None and w.shape != t.shape:
+            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
+        gb = None if intensity is None else f32(intensity)
+        if gb is not None and gb.shape != (t.shape[0], 2):
+            raise ValueError(f"expected intensity of shape ({t.shape[0]}, 2), got {gb.shape}")
+        return a, t, w, gb
+
+    def align_volume_cost_w(self, images, targets, maps, *, weights=None, intensity=None, warped=False, gradient=False):
+        """``align_volume_cost`` with a per-pixel weight and a per-target gain and bias -> ``align_volume.AlignResultVW``: ``weights`` (m, th, tw)
+        or None (all 1; a weight that is zero, negative or not finite masks its pixel), ``intensity`` (m, 2) = (g, b) or None ((1, 0)); ``cost`` =
+        sum w (g R + b - T)^2 over the valid pixels, ``wsum`` their weights, ``grad`` (m, 11) and ``jtj`` (m, 11, 11) over the map's nine
+        parameters, then g, b (build-defined; msiren_align_volume_w).  Without weights and intensity the shared entries
+        are ``align_volume_cost``'s bits.  ``warped`` / ``gradient`` return R and (gZ, gY, gX) before gain and bias."""
+        from . import align_volume as av
+
+        self._ensure_committed()
+        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
+        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        if mp.shape != (m, 9):
+            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
+        sums = np.zeros((m, av.SUMS_VW), np.float64)
+        wp = np.full((m, th, tw), np.nan, np.float32) if warped else None
+        g = np.full((3, m, th, tw), np.nan, np.float32) if gradient else None
+        _lib.check(self._lib.msiren_align_volume_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, mp.ctypes.data, None if w is None else w.ctypes.data,
+                                                   None if gb is None else gb.ctypes.data, sums.ctypes.data, wp.ctypes.data if warped else None,
+                                                   g.ctypes.data if gradient else None))
+        return av.unpack_vw(sums, wp, g)
+
+    def _align_volume_solve_w(self, images, targets, mode, maps, planes, rigid, spacing, weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min,
+                              lam_max, trace):
+        from . import align, align_volume as av
+
+        self._ensure_committed()
+        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        if mode == align.AFFINE and maps.shape != (m, 9):
+            raise ValueError(f"expected maps of shape ({m}, 9), got {maps.shape}")
+        if mode == align.RIGID and (planes.shape != (m, 12) or rigid.shape != (m, 12)):
+            raise ValueError(f"expected planes and states of shape ({m}, 12), got {planes.shape} and {rigid.shape}")
+        o = _lib.AlignVolumeSolveWOpts(C.sizeof(_lib.AlignVolumeSolveWOpts), mode, int(iterations), av.ESTIMATE if estimate_intensity else av.FIXED, float(damping),
+                                       float(down), float(up), float(lam_min), float(lam_max), float(spacing))
+        is_rigid = mode == align.RIGID
+        out = np.zeros((m, 9), np.float32) if is_rigid else maps.copy()
+        gout = np.tile(np.array([1.0, 0.0], np.float32), (m, 1)) if gb is None else gb.copy()
+        rout = rigid.copy() if is_rigid else None
+        report = np.zeros((m, 7), np.float64)
+        tr = np.zeros((max(int(iterations), 0), m, 14), np.float64) if trace else None
+        _lib.check(self._lib.msiren_align_volume_solve_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), None if is_rigid else maps.ctypes.data,
+                                                         planes.ctypes.data if is_rigid else None, rigid.ctypes.data if is_rigid else None,
+                                                         None if w is None else w.ctypes.data, None if gb is None else gb.ctypes.data, out.ctypes.data,
+                                                         gout.ctypes.data, rout.ctypes.data if is_rigid else None, report.ctypes.data,
+                                                         tr.ctypes.data if trace else None))
+        return av.solve_result_vw(out, gout, rout, report, tr)
+
+    def align_volume_solve_w(self, images, targets, maps, *, weights=None, intensity=None, estimate_intensity=True, iterations=12, damping=1e-3, down=0.1, up=10.0,
+                             lam_min=1e-9, lam_max=1e9, trace=False):
+        """``align_volume_solve`` on ``align_volume_cost_w`` -> ``align_volume.SolveResultVW``: every pixel weighted by ``weights`` (m, th, tw), the
+        target modelled as g R + b per target from ``intensity`` (m, 2) (None: (1, 0)).  ``estimate_intensity``: (g, b) are solved for together
+        with the map (11 parameters); False: they stay at their inputs (9).  The accept / reject rule compares cost / wsum (build-defined,
+        DESIGN.md section 5.14; msiren_align_volume_solve_w); bit for bit what ``align_volume.solve_on_host_vw`` gives around
+        ``align_volume_cost_w``.  ``trace``: (iterations, m, 14)."""
+        from . import align
+
+        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        return self._align_volume_solve_w(images, targets, align.AFFINE, mp, None, None, 1.0, weights, intensity, estimate_intensity, iterations, damping, down, up,
+                                          lam_min, lam_max, trace)
+
+    def align_volume_solve_rigid_w(self, images, targets, planes, spacing, *, rotation=None, shift=None, weights=None, intensity=None, estimate_intensity=True,
+                                   iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
+        """As ``align_volume_solve_w`` over a rigid motion of every target's nominal plane (``align_volume_solve_rigid``'s arguments): 8 parameters
+        with the intensity, 6 without."""
+        from . import align
+
+        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
+        m = len(pl)
+        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (m, 3, 3)).reshape(m, 9)
+        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (m, 3))
+        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
+        return self._align_volume_solve_w(images, targets, align.RIGID, None, pl, rigid, spacing, weights, intensity, estimate_intensity, iterations, damping, down, up,
+                                          lam_min, lam_max, trace)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
