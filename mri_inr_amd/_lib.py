@@ -112,6 +112,22 @@ class AlignVolumeSolveWOpts(C.Structure):
     ]
 
 
+class AlignVolumeSolveGroupOpts(C.Structure):
+    """msiren_align_volume_solve_group_opts"""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("iterations", C.c_int32),
+        ("intensity_mode", C.c_int32),
+        ("reserved", C.c_int32),
+        ("damping", C.c_double),
+        ("down", C.c_double),
+        ("up", C.c_double),
+        ("lam_min", C.c_double),
+        ("lam_max", C.c_double),
+        ("spacing", C.c_double),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -194,6 +210,10 @@ PROTOTYPES = {
     "msiren_align_volume_w_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_align_volume_solve_w": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveWOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_align_volume_solve_w_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveWOpts), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_volume_solve_group": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp]),
+    "msiren_align_volume_solve_group_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                      _vp, _vp, _vp, _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

@@ -1,10 +1,10 @@
 // Scratch layouts and size limits of the geometry calls (plain C++, no HIP: unit-tested on the CPU by tests/test_align_plan.py): the five
-// pipelines of resample.hip -- resample, resample-volume, align, align-w, align-volume (and its weighted form) -- and the state of the four solves.  Every call
-// carves one block of its stream's scratch, in this order, offsets in bytes:
+// pipelines of resample.hip -- resample, resample-volume, align, align-w, align-volume (and its weighted form) -- the state of the solves, and
+// the groups of the grouped volume solve.  Every call carves one block of its stream's scratch, in this order, offsets in bytes:
 //     [counts B][cursors B][offsets B + 1][items B + 1][ent E][tile S][pair P]  ints, padded to an even count
 //     [coords 2 E][w S][f P]                                                    floats; coords are float2: 8-byte aligned
 //     [partials R records of `nsums` doubles]                                   behind the floats padded to an even count (align forms)
-//     [solve state]                                                             behind the partials (solve_layout)
+//     [solve state]                                                             behind the partials (solve_layout, group_solve_layout)
 // B bins, E entries (what the ragged trunk evaluates), S slots (tile and fold weight), P points (pair of slices and fraction):
 //     resample          B = nV nH      E = S = M K             P = 0          (M points, K = KA KA covering tiles at most)
 //     resample-volume   B = n nV nH    E = 2 M K, S = M K      P = M
@@ -65,6 +65,40 @@ inline SolveLayout solve_layout(size_t base, int64_t units, int nsums, int nrigi
     s.cnt = s.gb_best + (gb ? 4 * u * 2 : 0);
     s.total = s.cnt + 4 * u * 2;
     return s;
+}
+
+// The grouped volume solve (align_group.hip.h) behind `base`, a multiple of 8: per target the 80 sums at the trial and at
+// the best state and one record of `nrec` doubles, per group the rigid states and `nscal` doubles; then the 4-byte words.
+//     [sums m 80][sums_best m 80][rec m nrec][rigid_trial G 12][rigid_best G 12][scal G nscal]
+//     [trial m 9][best m 9][gb_trial m 2][gb_best m 2][group_of m][group_start G + 1][cnt G ncnt]
+struct GroupSolveLayout {
+    size_t sums, sums_best, rec, rigid_trial, rigid_best, scal, trial, best, gb_trial, gb_best, group_of, group_start, cnt;
+    size_t total;  // from the start of the scratch
+};
+inline GroupSolveLayout group_solve_layout(size_t base, int64_t m, int64_t G, int nsums, int nrec, int nscal, int ncnt) {
+    const size_t u = (size_t)m, g = (size_t)G;
+    GroupSolveLayout s{};
+    s.sums = base, s.sums_best = s.sums + 8 * u * nsums, s.rec = s.sums_best + 8 * u * nsums, s.rigid_trial = s.rec + 8 * u * nrec;
+    s.rigid_best = s.rigid_trial + 8 * g * 12, s.scal = s.rigid_best + 8 * g * 12;
+    s.trial = s.scal + 8 * g * nscal, s.best = s.trial + 4 * u * 9, s.gb_trial = s.best + 4 * u * 9, s.gb_best = s.gb_trial + 4 * u * 2;
+    s.group_of = s.gb_best + 4 * u * 2, s.group_start = s.group_of + 4 * u, s.cnt = s.group_start + 4 * (g + 1);
+    s.total = s.cnt + 4 * g * ncnt;
+    return s;
+}
+
+// group_start (G + 1) of the grouped solve: G >= 1 groups of consecutive targets, the first offset 0, the last m, strictly ascending (no empty
+// group).  GROUPS_OK, or what is wrong and in *index the offending offset's index (GROUPS_ORDER: the first i with group_start[i] <=
+// group_start[i - 1]; an offset outside 0 .. m shows as GROUPS_FIRST, GROUPS_ORDER or GROUPS_LAST).
+enum GroupStartError { GROUPS_OK = 0, GROUPS_NONE, GROUPS_NULL, GROUPS_FIRST, GROUPS_ORDER, GROUPS_LAST };
+inline GroupStartError group_start_check(const int32_t* group_start, int64_t G, int64_t m, int64_t* index) {
+    *index = 0;
+    if (G < 1) return GROUPS_NONE;
+    if (!group_start) return GROUPS_NULL;
+    if (group_start[0] != 0) return GROUPS_FIRST;
+    for (int64_t i = 1; i <= G; ++i)
+        if (group_start[i] <= group_start[i - 1]) return *index = i, GROUPS_ORDER;
+    if (group_start[G] != m) return *index = G, GROUPS_LAST;
+    return GROUPS_OK;
 }
 
 // The limits: true = the call fits.  NPt = nV nH tiles per slice.

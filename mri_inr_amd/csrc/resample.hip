@@ -3,8 +3,8 @@
 // (siren_trunk_f32_ragged.hip.h; the launches: launch_dispatch.hip): a layer-0 table per (patch, coordinate) would be 4 H bytes an entry.
 // The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
 // msiren_resample_slices*, msiren_resample_volume*, msiren_align_slices*, msiren_align_solve* and their weighted forms msiren_align_slices_w*,
-// msiren_align_solve_w*, msiren_align_volume*, msiren_align_volume_solve* and their weighted forms msiren_align_volume_w*, msiren_align_volume_solve_w*
-// (DESIGN.md sections 5.8 - 5.14) are built on these trunks: the five
+// msiren_align_solve_w*, msiren_align_volume*, msiren_align_volume_solve* and their weighted forms msiren_align_volume_w*, msiren_align_volume_solve_w*,
+// and the grouped msiren_align_volume_solve_group* (DESIGN.md sections 5.8 - 5.15) are built on these trunks: the five
 // geometry pipelines below (namespace mh), each behind launch_dispatch.hip's slice_prologue on the call's stream, then their host-pointer forms
 // and the entry points.  Where each call's scratch sections lie and what it refuses as too large: align_plan.h.
 #include "host_buffers.h"
@@ -16,6 +16,7 @@
 #include "align_w.hip.h"
 #include "align_volume.hip.h"
 #include "align_volume_w.hip.h"
+#include "align_group.hip.h"
 
 namespace mh {
 
@@ -604,6 +605,105 @@ int align_volume_solve_w(msiren_handle h, const Call& c, const float* images_dev
     return solve_loop(h, c, a, sp, o->iterations, step, "align_volume_step_w_kernel");
 }
 
+// ---- the grouped rigid solve (kernels: align_group.hip.h): align_volume_solve_w's loop with the step stage for groups of
+// consecutive targets under one rigid state per group.  Prologue, bins, trunk and the 80-sum reduce are the weighted volume family's.
+// the loop behind an init kernel with the step stage as a callable: evaluation k at the trial maps, then `stage(k, last)` as one profile entry `name`
+template <typename Stage>
+static int solve_loop_staged(msiren_handle h, const Call& c, const AlignPlan& a, const float* trial, double* sums, int iterations, const char* name, Stage stage) {
+    int rc;
+    for (int k = 0; k < iterations; ++k) {
+        if ((rc = align_evaluate(h, c, a, trial, sums, nullptr, nullptr))) return rc;
+        hipEvent_t e1 = nullptr;
+        if ((rc = profile_begin(h, c.stream, &e1)) || (rc = stage(k, k == iterations - 1))) return rc;
+        if ((rc = profile_end(h, c.stream, e1, a.units, name))) return rc;
+    }
+    return 0;
+}
+
+// every refusal that needs no device pointer: what align_volume_solve_w_check refuses in rigid mode, then the groups (group_start is a host array)
+int align_volume_solve_group_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_group_opts* o,
+                                   const int32_t* group_start, int64_t G, const void* planes, const void* rigid_in, const void* maps_out, const void* intensity_out,
+                                   const void* report) {
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_volume_solve_group_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_volume_solve_group_opts.struct_size = %u, this library's is %u", o->struct_size,
+                    (unsigned)sizeof(msiren_align_volume_solve_group_opts));
+    const msiren_align_volume_solve_w_opts w{(uint32_t)sizeof(msiren_align_volume_solve_w_opts), 1, o->iterations, o->intensity_mode, o->damping, o->down, o->up, o->lam_min,
+                                             o->lam_max, o->spacing};
+    int rc = align_volume_solve_w_check(h, n, height, width, m, th, tw, &w, nullptr, planes, rigid_in, maps_out, intensity_out, report);
+    if (rc || m == 0) return rc;
+    int64_t at = 0;
+    switch (msiren::group_start_check(group_start, G, m, &at)) {
+        case msiren::GROUPS_OK: return 0;
+        case msiren::GROUPS_NONE: return fail(MSIREN_E_INVALID, "n_groups = %lld: one group at least", (long long)G);
+        case msiren::GROUPS_NULL: return fail(MSIREN_E_INVALID, "null argument (group_start)");
+        case msiren::GROUPS_FIRST: return fail(MSIREN_E_INVALID, "group_start[0] = %d: the first offset must be 0", group_start[0]);
+        case msiren::GROUPS_ORDER:
+            return fail(MSIREN_E_INVALID, "group_start[%lld] = %d is not above group_start[%lld] = %d: offsets must be strictly ascending", (long long)at, group_start[at],
+                        (long long)at - 1, group_start[at - 1]);
+        default: return fail(MSIREN_E_INVALID, "group_start[%lld] = %d: the last offset must be m = %lld", (long long)at, group_start[at], (long long)m);
+    }
+}
+
+int align_volume_solve_group(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                             int32_t tw, const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
+                             const float* weights_dev, const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report, double* target_report,
+                             double* trace) {
+    int rc = align_volume_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report);
+    if (rc || m == 0 || (int64_t)th * tw == 0) return rc;
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_in % 4 || (uintptr_t)intensity_out % 4 ||
+        (uintptr_t)planes % 8 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)target_report % 8 || (uintptr_t)trace % 8)
+        return fail(MSIREN_E_INVALID, "device maps, weights and intensity must be 4-byte aligned, planes, rigid states, reports and trace 8-byte aligned");
+    constexpr int S = msiren::ALIGN_VOLUME_SUMS_W, R = msiren::ALIGN_GROUP_REC, NS = msiren::ALIGN_GROUP_SCAL, NC = msiren::ALIGN_GROUP_CNT;
+    AlignPlan a;
+    bool todo;
+    if ((rc = align_prepare(h, c, ALIGN_VOLUME_WEIGHTED, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report,
+                            msiren::group_solve_layout(0, m, G, S, R, NS, NC).total, &a, &todo)) || !todo)
+        return rc;
+    auto& sc = h->sc[c.stream];
+    hipStream_t st = sc.s;
+    char* const base = (char*)sc.ragged.p;
+    const msiren::GroupSolveLayout s = msiren::group_solve_layout(a.lay.total, m, G, S, R, NS, NC);
+    msiren::AlignGroupParams sp{};
+    sp.sums = (double*)(base + s.sums), sp.sums_best = (double*)(base + s.sums_best), sp.rec = (double*)(base + s.rec);
+    sp.rigid_trial = (double*)(base + s.rigid_trial), sp.rigid_best = (double*)(base + s.rigid_best), sp.scal = (double*)(base + s.scal);
+    sp.trial = (float*)(base + s.trial), sp.best = (float*)(base + s.best), sp.gb_trial = (float*)(base + s.gb_trial), sp.gb_best = (float*)(base + s.gb_best);
+    sp.group_of = (int*)(base + s.group_of), sp.group_start = (int*)(base + s.group_start), sp.cnt = (int*)(base + s.cnt);
+    sp.planes = planes, sp.trace = trace, sp.maps_out = maps_out, sp.intensity_out = intensity_out, sp.rigid_out = rigid_out, sp.report = report;
+    sp.target_report = target_report;
+    sp.m = (int)m, sp.G = (int)G, sp.est = o->intensity_mode == 1;
+    sp.down = o->down, sp.up = o->up, sp.lam_min = o->lam_min, sp.lam_max = o->lam_max, sp.spacing = o->spacing;
+    a.weights = weights_dev, a.intensity = sp.gb_trial;
+    // group_start: up to 512 offsets per launch, by value in the kernel's arguments (no copy from a host buffer that the caller may reuse, no sync)
+    for (int64_t at = 0; at < G + 1; at += msiren::ALIGN_GROUP_OFFSETS) {
+        msiren::AlignGroupOffsets off{};
+        const int count = (int)(G + 1 - at < msiren::ALIGN_GROUP_OFFSETS ? G + 1 - at : msiren::ALIGN_GROUP_OFFSETS);
+        for (int i = 0; i < count; ++i) off.v[i] = group_start[at + i];
+        hipLaunchKernelGGL(msiren::align_group_upload_kernel, dim3(msiren::ALIGN_GROUP_OFFSETS / 256), dim3(256), 0, st, off, sp.group_start, (int)at, count);
+        HIPCHK(hipGetLastError());
+    }
+    const dim3 gt((unsigned)((m + 255) / 256)), gg((unsigned)((G + 255) / 256));
+    hipLaunchKernelGGL(msiren::align_group_init_kernel, gt, dim3(256), 0, st, sp, rigid_in, intensity_in, o->damping);
+    HIPCHK(hipGetLastError());
+    const bool est = sp.est;
+    return solve_loop_staged(h, c, a, sp.trial, const_cast<double*>(sp.sums), o->iterations, "align_group_step_kernels", [&](int k, bool last) {
+        sp.k = k, sp.last = last;
+        hipLaunchKernelGGL(msiren::align_group_decide_kernel, gg, dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        if (est) hipLaunchKernelGGL(msiren::align_group_project_kernel<1>, gt, dim3(256), 0, st, sp);
+        else hipLaunchKernelGGL(msiren::align_group_project_kernel<0>, gt, dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        if (est) hipLaunchKernelGGL(msiren::align_group_step_kernel<1>, gg, dim3(256), 0, st, sp);
+        else hipLaunchKernelGGL(msiren::align_group_step_kernel<0>, gg, dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        if (est) hipLaunchKernelGGL(msiren::align_group_apply_kernel<1>, gt, dim3(256), 0, st, sp);
+        else hipLaunchKernelGGL(msiren::align_group_apply_kernel<0>, gt, dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
+}
+
 }  // namespace mh
 
 using namespace mh;
@@ -907,9 +1007,56 @@ int align_volume_solve_w_host(msiren_ctx* h, const float* images_host, int64_t n
     return io.finish();
 }
 
+// the grouped solve: six inputs and six outputs, all staged; group_start stays on the host
+int align_volume_solve_group_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                                  const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
+                                  const float* weights_host, const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report,
+                                  double* target_report, double* trace) {
+    const int64_t M = m * (int64_t)th * tw;
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_volume_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report),
+                            M == 0, !images_host || !targets_host, n, height, width, &done)) || done) return rc;
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY);
+    const int i_p = io.in(planes, (size_t)m * 12 * sizeof(double), HOST_COPY), i_r = io.in(rigid_in, (size_t)G * 12 * sizeof(double), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_in, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_m = io.out(maps_out, (size_t)m * 9 * sizeof(float), HOST_COPY), o_gb = io.out(intensity_out, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_r = io.out(rigid_out, (size_t)G * 12 * sizeof(double), HOST_COPY), o_rep = io.out(report, (size_t)G * 7 * sizeof(double), HOST_COPY);
+    const int o_tr = io.out(target_report, (size_t)m * 3 * sizeof(double), HOST_COPY), o_trace = io.out(trace, (size_t)o->iterations * G * 15 * sizeof(double), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_volume_solve_group(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, o, group_start, G, io.src<double>(i_p), io.src<double>(i_r),
+                                       io.src<float>(i_w), io.src<float>(i_gb), io.dst<float>(o_m), io.dst<float>(o_gb), io.dst<double>(o_r), io.dst<double>(o_rep),
+                                       io.dst<double>(o_tr), io.dst<double>(o_trace))))
+        return rc;
+    return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
+
+int msiren_align_volume_solve_group(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th,
+                                    int32_t tw, const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start, int64_t n_groups, const double* planes,
+                                    const double* rigid_in, const float* weights_host, const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out,
+                                    double* report, double* target_report, double* trace) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_volume_solve_group_host(h, images_host, n, height, width, targets_host, m, th, tw, opts, group_start, n_groups, planes, rigid_in, weights_host, intensity_in,
+                                         maps_out, intensity_out, rigid_out, report, target_report, trace);
+}
+int msiren_align_volume_solve_group_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                                        int32_t tw, const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start, int64_t n_groups, const double* planes_dev,
+                                        const double* rigid_in_dev, const float* weights_dev, const float* intensity_in_dev, float* maps_out_dev, float* intensity_out_dev,
+                                        double* rigid_out_dev, double* report_dev, double* target_report_dev, double* trace_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_volume_solve_group_check(h, n, height, width, m, th, tw, opts, group_start, n_groups, planes_dev, rigid_in_dev, maps_out_dev, intensity_out_dev, report_dev)))
+        return rc;  // (before the stream rotates)
+    return align_volume_solve_group(h, dev_call(h), images_dev, n, height, width, targets_dev, m, th, tw, opts, group_start, n_groups, planes_dev, rigid_in_dev, weights_dev,
+                                    intensity_in_dev, maps_out_dev, intensity_out_dev, rigid_out_dev, report_dev, target_report_dev, trace_dev);
+}
 
 int msiren_align_volume_w(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
                           const float* maps_host, const float* weights_host, const float* intensity_host, double* sums_host, float* warped_host, float* wgrad_host) {

@@ -1202,6 +1202,42 @@ class ModulatedSiren:
         return self._align_volume_solve_w(images, targets, align.RIGID, None, pl, rigid, spacing, weights, intensity, estimate_intensity, iterations, damping, down, up,
                                           lam_min, lam_max, trace)
 
+    def align_volume_solve_group(self, images, targets, planes, spacing, groups, *, rotation=None, shift=None, weights=None, intensity=None, estimate_intensity=True,
+                                 iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
+        """``align_volume_solve_rigid_w`` for GROUPS of consecutive targets that moved together (stacks, interleaves): one rigid state per group, every
+        target with its own plane, weights and intensity -> ``align_group.SolveResultG``.  ``groups``: the (G + 1) offsets into the targets (first 0,
+        last m, strictly ascending) or a list of G group sizes.  ``rotation`` (G, 3, 3) (None: the identity) and ``shift`` (G, 3) (None: zero) are per
+        group.  A group is accepted or rejected on sum cost / sum wsum over its members; with ``estimate_intensity`` every member's (g, b) is solved
+        for jointly with the group's motion (6 + 2 size parameters, the 2 x 2 blocks eliminated exactly), a member without valid pixels is placed by
+        the others (build-defined; msiren_align_volume_solve_group); bit for bit what ``align_group.solve_on_host_g`` gives
+        around ``align_volume_cost_w``.  One PHYSICAL motion per group needs the same centre c in every member's plane (e_i, e_j, o, c): the state
+        moves a point p of a member to Rot (p - c) + c + shift with that member's c; the call does not check it.  ``trace``: (iterations, G, 15)."""
+        from . import align_group as ag, align_volume as av
+
+        self._ensure_committed()
+        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
+        if pl.shape != (m, 12):
+            raise ValueError(f"expected planes of shape ({m}, 12), got {pl.shape}")
+        gs = np.ascontiguousarray(ag.group_offsets(groups, m), dtype=np.int32)
+        G = len(gs) - 1
+        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (G, 3, 3)).reshape(G, 9)
+        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (G, 3))
+        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
+        o = _lib.AlignVolumeSolveGroupOpts(C.sizeof(_lib.AlignVolumeSolveGroupOpts), int(iterations), av.ESTIMATE if estimate_intensity else av.FIXED, 0, float(damping),
+                                           float(down), float(up), float(lam_min), float(lam_max), float(spacing))
+        out = np.zeros((m, 9), np.float32)
+        gout = np.tile(np.array([1.0, 0.0], np.float32), (m, 1)) if gb is None else gb.copy()
+        rout, report, trep = rigid.copy(), np.zeros((G, 7), np.float64), np.zeros((m, 3), np.float64)
+        tr = np.zeros((max(int(iterations), 0), G, 15), np.float64) if trace else None
+        _lib.check(self._lib.msiren_align_volume_solve_group(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), gs.ctypes.data, G, pl.ctypes.data,
+                                                             rigid.ctypes.data, None if w is None else w.ctypes.data, None if gb is None else gb.ctypes.data,
+                                                             out.ctypes.data, gout.ctypes.data, rout.ctypes.data, report.ctypes.data, trep.ctypes.data,
+                                                             tr.ctypes.data if trace else None))
+        return ag.solve_result_g(out, gout, rout, report, trep, tr)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
