@@ -40,7 +40,8 @@ extern "C" {
  * msiren_align_volume(_dev), msiren_align_volume_solve(_dev) and msiren_align_volume_solve_opts (target slices scored against, and aligned to, the stack
  * read as a volume under 3 x 3 maps); msiren_align_volume_w(_dev), msiren_align_volume_solve_w(_dev) and msiren_align_volume_solve_w_opts (the same two
  * with a per-pixel weight and a per-target gain and bias); msiren_align_volume_solve_group(_dev) and msiren_align_volume_solve_group_opts (groups of
- * consecutive targets aligned to the volume under one shared rigid motion per group).
+ * consecutive targets aligned to the volume under one shared rigid motion per group); msiren_align_volume_r(_dev) and
+ * msiren_align_volume_solve_group_r(_dev) (the weighted volume cost and the grouped solve under a Geman-McClure loss with one scale per target).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -761,6 +762,59 @@ MSIREN_API int msiren_align_volume_solve_group_dev(msiren_handle h, const float*
                                                    float* maps_out_dev /* (m, 9) */, float* intensity_out_dev /* (m, 2) */,
                                                    double* rigid_out_dev /* (G, 12) or NULL */, double* report_dev /* (G, 7) */,
                                                    double* target_report_dev /* (m, 3) or NULL */, double* trace_dev /* (iterations, G, 15) or NULL */);
+
+/* Build-defined: msiren_align_volume_w under a robust (Geman-McClure) loss rho(r) = r^2 / (1 + r^2 / s), for targets whose
+ * bad pixels (dropout, artefacts, anatomy that is not in the stack) come without a mask.  Every argument of msiren_align_volume_w, and
+ *     scale (m) float64: s = (c sigma)^2 per target, in SQUARED intensity units;  rweight (m, th, tw) float32 or NULL
+ * A pixel is VALID iff msiren_align_volume_w's condition holds and s > 0: a target whose s is NaN, zero or negative has count 0.  s = +inf is
+ * allowed.  Per valid pixel, with w, r and J[11] formed exactly as msiren_align_volume_w forms them, in fp64, no fused multiply-add, one rounding
+ * per operation, in exactly this association:
+ *     u  = (r r) / s        v = 1.0 + u        om = 1.0 / v
+ *     wl = w om             wq = wl om
+ *     count += 1;  wsum += w;  cost += (wl r) r;  dcost[a] += (2.0 (wq r)) J[a];  jtj[a, b] += (wq J[a]) J[b]  for a <= b
+ * sums (m, 80) float64 in msiren_align_volume_w's layout and summation order.  cost is the weighted loss sum w rho(r), dcost its EXACT gradient
+ * over the eleven parameters, jtj the Gauss-Newton matrix of the loss's quadratic majoriser (iteratively reweighted least squares), wsum the
+ * plain sum of the weights -- cost / wsum cannot be lowered by rejecting pixels.  With s = +inf every term is msiren_align_volume_w's term: the 80
+ * sums are its bits.  warped and wgrad as there; rweight = (float)(om om) at a valid pixel (1: an inlier, towards 0: rejected) and NaN elsewhere.
+ * mri_inr_amd/align_robust.py: robust_terms restates the five lines in Python floats.
+ * MSIREN_E_INVALID before any launch: what msiren_align_volume_w refuses; a null scale; device rweight not 4-byte, scale not 8-byte aligned.
+ * Under msiren_profile_enable: "align_volume_bin_kernels", the jet ragged trunk under its name, "align_volume_reduce_r_kernels". */
+MSIREN_API int msiren_align_volume_r(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                     const float* targets_host, int64_t m_targets, int32_t th, int32_t tw, const float* maps_host /* (m, 9) */,
+                                     const float* weights_host /* (m, th, tw) or NULL */, const float* intensity_host /* (m, 2) or NULL */,
+                                     const double* scale_host /* (m) */, double* sums_host /* (m, 80) */, float* warped_host /* or NULL */,
+                                     float* wgrad_host /* (3, m, th, tw) or NULL */, float* rweight_host /* (m, th, tw) or NULL */);
+MSIREN_API int msiren_align_volume_r_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                         const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw, const float* maps_dev /* (m, 9) */,
+                                         const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */,
+                                         const double* scale_dev /* (m) */, double* sums_dev /* (m, 80) */, float* warped_dev /* or NULL */,
+                                         float* wgrad_dev /* or NULL */, float* rweight_dev /* or NULL */);
+
+/* Build-defined: msiren_align_volume_solve_group's loop around msiren_align_volume_r -- every evaluation's 80 sums are the
+ * robust ones, the grouped step stage, its rule (mri_inr_amd/align_group.py: lm_step_g), the options struct and every output are
+ * msiren_align_volume_solve_group's.  scale (m) float64 stands behind intensity_in and is FIXED for the whole call, so every evaluation of one call
+ * scores the same objective; mean = sum cost / sum wsum is the mean robust loss per unit weight.  All groups of one target make it the robust
+ * rigid solve per target.  With every scale +inf the call returns msiren_align_volume_solve_group's bits.  A first scale from a quadratic pass:
+ * mri_inr_amd/align_robust.py: scale_from.
+ * MSIREN_E_INVALID before any launch: everything msiren_align_volume_solve_group refuses; a null scale; a device scale not 8-byte aligned.  Under
+ * msiren_profile_enable: as msiren_align_volume_solve_group, with "align_volume_reduce_r_kernels" in place of "align_volume_reduce_w_kernels". */
+MSIREN_API int msiren_align_volume_solve_group_r(msiren_handle h, const float* images_host, int64_t n_slices, int32_t height, int32_t width,
+                                                 const float* targets_host, int64_t m_targets, int32_t th, int32_t tw,
+                                                 const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start /* host, (G + 1) */,
+                                                 int64_t n_groups, const double* planes /* (m, 12) */, const double* rigid_in /* (G, 12) */,
+                                                 const float* weights /* (m, th, tw) or NULL */, const float* intensity_in /* (m, 2) or NULL */,
+                                                 const double* scale /* (m) */, float* maps_out /* (m, 9) */, float* intensity_out /* (m, 2) */,
+                                                 double* rigid_out /* (G, 12) or NULL */, double* report /* (G, 7) */,
+                                                 double* target_report /* (m, 3) or NULL */, double* trace /* (iterations, G, 15) or NULL */);
+MSIREN_API int msiren_align_volume_solve_group_r_dev(msiren_handle h, const float* images_dev, int64_t n_slices, int32_t height, int32_t width,
+                                                     const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw,
+                                                     const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start /* host, (G + 1) */,
+                                                     int64_t n_groups, const double* planes_dev /* (m, 12) */, const double* rigid_in_dev /* (G, 12) */,
+                                                     const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_in_dev /* (m, 2) or NULL */,
+                                                     const double* scale_dev /* (m) */, float* maps_out_dev /* (m, 9) */,
+                                                     float* intensity_out_dev /* (m, 2) */, double* rigid_out_dev /* (G, 12) or NULL */,
+                                                     double* report_dev /* (G, 7) */, double* target_report_dev /* (m, 3) or NULL */,
+                                                     double* trace_dev /* (iterations, G, 15) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

@@ -214,6 +214,12 @@ PROTOTYPES = {
                                                   _vp, _vp, _vp]),
     "msiren_align_volume_solve_group_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                                       _vp, _vp, _vp, _vp]),
+    "msiren_align_volume_r": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_volume_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_volume_solve_group_r": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                    _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_volume_solve_group_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                        _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

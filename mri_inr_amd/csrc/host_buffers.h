@@ -80,7 +80,7 @@ enum HostPolicy : unsigned {
 //     resample_slices(_grad)                    out (optional) / grad
 class SyncHostCall {
 public:
-    static constexpr int kMax = 6;  // buffers per direction
+    static constexpr int kMax = 7;  // buffers per direction (msiren_align_volume_solve_group_r stages seven inputs)
     // wait_all: finish() waits for all the handle's streams (sync_all) instead of `stream` alone
     SyncHostCall(msiren_ctx* h, int stream, bool wait_all = false) : h_(h), stream_(stream), wait_all_(wait_all) {}
     SyncHostCall(const SyncHostCall&) = delete;

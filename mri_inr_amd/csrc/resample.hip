@@ -4,7 +4,8 @@
 // The *_native value forms run the handle's own trunk arithmetic instead, layer 0 computed in the kernel (launch_trunk_ragged_native).
 // msiren_resample_slices*, msiren_resample_volume*, msiren_align_slices*, msiren_align_solve* and their weighted forms msiren_align_slices_w*,
 // msiren_align_solve_w*, msiren_align_volume*, msiren_align_volume_solve* and their weighted forms msiren_align_volume_w*, msiren_align_volume_solve_w*,
-// and the grouped msiren_align_volume_solve_group* (DESIGN.md sections 5.8 - 5.15) are built on these trunks: the five
+// the grouped msiren_align_volume_solve_group* and the robust msiren_align_volume_r*, msiren_align_volume_solve_group_r* (DESIGN.md sections
+// 5.8 - 5.16) are built on these trunks: the five
 // geometry pipelines below (namespace mh), each behind launch_dispatch.hip's slice_prologue on the call's stream, then their host-pointer forms
 // and the entry points.  Where each call's scratch sections lie and what it refuses as too large: align_plan.h.
 #include "host_buffers.h"
@@ -16,6 +17,7 @@
 #include "align_w.hip.h"
 #include "align_volume.hip.h"
 #include "align_volume_w.hip.h"
+#include "align_volume_r.hip.h"
 #include "align_group.hip.h"
 
 namespace mh {
@@ -195,12 +197,15 @@ int resample_volume(msiren_handle h, const Call& c, const float* images_dev, int
 // per-pixel weight and a per-target gain and bias).  One path: the slice
 // prologue over the n slices, then per evaluation on the same stream the pixels of every target lattice, placed by their map in the kernel,
 // binned by (slice, tile) -> the exact-fp32 jet ragged trunk over those n nV nH bins, one replica, on the plan's rows -> per (unit, chunk) the
-// blend and the sums -> per unit the chunks in index order.  A unit is a slice (plain, weighted) or a target (volume).
-enum AlignFamily { ALIGN_PLAIN, ALIGN_WEIGHTED, ALIGN_VOLUME, ALIGN_VOLUME_WEIGHTED };
+// blend and the sums -> per unit the chunks in index order.  A unit is a slice (plain, weighted) or a target (volume).  What is launched for
+// these four is untouched by the fifth:
+// ALIGN_VOLUME_ROBUST (align_volume_r.hip.h): the weighted volume family's layout, bins and limits, its 80 sums formed under
+// a Geman-McClure loss with one scale per target.
+enum AlignFamily { ALIGN_PLAIN, ALIGN_WEIGHTED, ALIGN_VOLUME, ALIGN_VOLUME_WEIGHTED, ALIGN_VOLUME_ROBUST };
 static int align_nsums(AlignFamily f) {
     return f == ALIGN_PLAIN ? msiren::ALIGN_SUMS : f == ALIGN_WEIGHTED ? msiren::ALIGN_SUMS_W : f == ALIGN_VOLUME ? msiren::ALIGN_VOLUME_SUMS : msiren::ALIGN_VOLUME_SUMS_W;
 }
-static bool align_is_volume(AlignFamily f) { return f == ALIGN_VOLUME || f == ALIGN_VOLUME_WEIGHTED; }
+static bool align_is_volume(AlignFamily f) { return f == ALIGN_VOLUME || f == ALIGN_VOLUME_WEIGHTED || f == ALIGN_VOLUME_ROBUST; }
 
 int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
     int rc;
@@ -261,6 +266,8 @@ struct AlignPlan {
     const float* targets = nullptr;
     const float *weights = nullptr, *intensity = nullptr;  // weighted: (units, th, tw) and (units, 2), may be null
     Call pc;
+    const double* scale = nullptr;  // robust: (units) doubles
+    float* rweight = nullptr;       // robust: (units, th, tw) or null
 };
 
 // the family's check, every workspace of the call (`extra` bytes more behind the partials: a solve's state) and the slice prologue.
@@ -320,7 +327,13 @@ static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, co
     if ((rc = launch_trunk_f32_jet_ragged(h, a.pc, r, (const float*)sc.mods.p, rec, rec + (size_t)T, pixel_gscale(h))) || (rc = profile_begin(h, c.stream, &e1))) return rc;
     const dim3 gp((unsigned)(a.units * a.chunks)), gc((unsigned)a.units);
     const char* name;
-    if (a.fam == ALIGN_VOLUME_WEIGHTED) {  // sums_dev (m, 80)
+    if (a.fam == ALIGN_VOLUME_ROBUST) {  // sums_dev (m, 80)
+        hipLaunchKernelGGL(msiren::align_volume_partial_r_kernel, gp, dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, black, vp.pair, vp.f, a.targets, a.weights, a.intensity,
+                           a.scale, warped_dev, wgrad_dev, a.rweight, partials, (int)a.units, (int)a.Mt, a.tw, g.K, (int)g.NPt, (int)T, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(msiren::align_volume_combine_w_kernel, gc, dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
+        name = "align_volume_reduce_r_kernels";
+    } else if (a.fam == ALIGN_VOLUME_WEIGHTED) {  // sums_dev (m, 80)
         hipLaunchKernelGGL(msiren::align_volume_partial_w_kernel, gp, dim3(256), 0, st, rec, vp.ent, vp.tile, vp.w, black, vp.pair, vp.f, a.targets, a.weights, a.intensity,
                            warped_dev, wgrad_dev, partials, (int)a.units, (int)a.Mt, a.tw, g.K, (int)g.NPt, (int)T, (int)a.chunks);
         HIPCHK(hipGetLastError());
@@ -396,6 +409,24 @@ int align_volume_w(msiren_handle h, const Call& c, const float* images_dev, int6
     rc = align_prepare(h, c, ALIGN_VOLUME_WEIGHTED, images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, sums_dev, 0, &a, &todo);
     if (rc || !todo) return rc;
     a.weights = weights_dev, a.intensity = intensity_dev;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+// sums_dev (m, 80) under the robust loss; scale_dev (m) doubles; rweight_dev (m, th, tw) may be null; the rest: align_volume_w's
+int align_volume_r(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                   const float* maps_dev, const float* weights_dev, const float* intensity_dev, const double* scale_dev, double* sums_dev, float* warped_dev, float* wgrad_dev,
+                   float* rweight_dev) {
+    int rc = align_volume_w_check(h, n, height, width, m, th, tw);
+    if (rc) return rc;
+    if (m > 0 && (int64_t)th * tw > 0 && !scale_dev) return fail(MSIREN_E_INVALID, "null argument (scale)");
+    if ((uintptr_t)warped_dev % 4 || (uintptr_t)wgrad_dev % 4 || (uintptr_t)rweight_dev % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_dev % 4 ||
+        (uintptr_t)scale_dev % 8)
+        return fail(MSIREN_E_INVALID, "device warped, wgrad, rweight, weights and intensity must be 4-byte aligned, scale 8-byte aligned");
+    AlignPlan a;
+    bool todo;
+    rc = align_prepare(h, c, ALIGN_VOLUME_ROBUST, images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, sums_dev, 0, &a, &todo);
+    if (rc || !todo) return rc;
+    a.weights = weights_dev, a.intensity = intensity_dev, a.scale = scale_dev, a.rweight = rweight_dev;
     return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
 }
 
@@ -645,20 +676,24 @@ int align_volume_solve_group_check(msiren_ctx* h, int64_t n, int32_t height, int
     }
 }
 
-int align_volume_solve_group(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
-                             int32_t tw, const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
-                             const float* weights_dev, const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report, double* target_report,
-                             double* trace) {
+// the grouped solve on the sums of `fam`: ALIGN_VOLUME_WEIGHTED (scale_dev unused) or ALIGN_VOLUME_ROBUST (scale_dev (m) doubles,
+// fixed for the call, so every evaluation scores one objective).  The step stage reads the 80 sums whatever loss formed them.
+static int group_solve(msiren_handle h, const Call& c, AlignFamily fam, const double* scale_dev, const float* images_dev, int64_t n, int32_t height, int32_t width,
+                       const float* targets_dev, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G,
+                       const double* planes, const double* rigid_in, const float* weights_dev, const float* intensity_in, float* maps_out, float* intensity_out,
+                       double* rigid_out, double* report, double* target_report, double* trace) {
     int rc = align_volume_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report);
     if (rc || m == 0 || (int64_t)th * tw == 0) return rc;
     if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
+    if (fam == ALIGN_VOLUME_ROBUST && !scale_dev) return fail(MSIREN_E_INVALID, "null argument (scale)");
+    if (fam == ALIGN_VOLUME_ROBUST && (uintptr_t)scale_dev % 8) return fail(MSIREN_E_INVALID, "device scale must be 8-byte aligned");
     if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_in % 4 || (uintptr_t)intensity_out % 4 ||
         (uintptr_t)planes % 8 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)target_report % 8 || (uintptr_t)trace % 8)
         return fail(MSIREN_E_INVALID, "device maps, weights and intensity must be 4-byte aligned, planes, rigid states, reports and trace 8-byte aligned");
     constexpr int S = msiren::ALIGN_VOLUME_SUMS_W, R = msiren::ALIGN_GROUP_REC, NS = msiren::ALIGN_GROUP_SCAL, NC = msiren::ALIGN_GROUP_CNT;
     AlignPlan a;
     bool todo;
-    if ((rc = align_prepare(h, c, ALIGN_VOLUME_WEIGHTED, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report,
+    if ((rc = align_prepare(h, c, fam, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report,
                             msiren::group_solve_layout(0, m, G, S, R, NS, NC).total, &a, &todo)) || !todo)
         return rc;
     auto& sc = h->sc[c.stream];
@@ -674,7 +709,7 @@ int align_volume_solve_group(msiren_handle h, const Call& c, const float* images
     sp.target_report = target_report;
     sp.m = (int)m, sp.G = (int)G, sp.est = o->intensity_mode == 1;
     sp.down = o->down, sp.up = o->up, sp.lam_min = o->lam_min, sp.lam_max = o->lam_max, sp.spacing = o->spacing;
-    a.weights = weights_dev, a.intensity = sp.gb_trial;
+    a.weights = weights_dev, a.intensity = sp.gb_trial, a.scale = scale_dev;
     // group_start: up to 512 offsets per launch, by value in the kernel's arguments (no copy from a host buffer that the caller may reuse, no sync)
     for (int64_t at = 0; at < G + 1; at += msiren::ALIGN_GROUP_OFFSETS) {
         msiren::AlignGroupOffsets off{};
@@ -702,6 +737,23 @@ int align_volume_solve_group(msiren_handle h, const Call& c, const float* images
         HIPCHK(hipGetLastError());
         return 0;
     });
+}
+
+int align_volume_solve_group(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                             int32_t tw, const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
+                             const float* weights_dev, const float* intensity_in, float* maps_out, float* intensity_out, double* rigid_out, double* report, double* target_report,
+                             double* trace) {
+    return group_solve(h, c, ALIGN_VOLUME_WEIGHTED, nullptr, images_dev, n, height, width, targets_dev, m, th, tw, o, group_start, G, planes, rigid_in, weights_dev,
+                       intensity_in, maps_out, intensity_out, rigid_out, report, target_report, trace);
+}
+
+// the same loop on the robust sums; a null scale is refused
+int align_volume_solve_group_r(msiren_handle h, const Call& c, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                               int32_t tw, const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
+                               const float* weights_dev, const float* intensity_in, const double* scale_dev, float* maps_out, float* intensity_out, double* rigid_out,
+                               double* report, double* target_report, double* trace) {
+    return group_solve(h, c, ALIGN_VOLUME_ROBUST, scale_dev, images_dev, n, height, width, targets_dev, m, th, tw, o, group_start, G, planes, rigid_in, weights_dev,
+                       intensity_in, maps_out, intensity_out, rigid_out, report, target_report, trace);
 }
 
 }  // namespace mh
@@ -1034,9 +1086,97 @@ int align_volume_solve_group_host(msiren_ctx* h, const float* images_host, int64
     return io.finish();
 }
 
+// the robust forms: as align_volume_w_host and align_volume_solve_group_host; the scales go up once per call
+int align_volume_r_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                        const float* maps_host, const float* weights_host, const float* intensity_host, const double* scale_host, double* sums_host, float* warped_host,
+                        float* wgrad_host, float* rweight_host) {
+    const int64_t M = m * (int64_t)th * tw;
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_volume_w_check(h, n, height, width, m, th, tw),
+                            M == 0, !images_host || !targets_host || !maps_host || !sums_host || !scale_host, n, height, width, &done)) || done) return rc;
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)m * 9 * sizeof(float), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_host, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int i_s = io.in(scale_host, (size_t)m * sizeof(double), HOST_COPY);
+    const int o_s = io.out(sums_host, (size_t)m * kAlignVolumeSumsW * sizeof(double), HOST_IN_PLACE);
+    const int o_w = io.out(warped_host, nt, HOST_IN_PLACE), o_g = io.out(wgrad_host, 3 * nt, HOST_IN_PLACE), o_rw = io.out(rweight_host, nt, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_volume_r(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, io.src<float>(i_m), io.src<float>(i_w), io.src<float>(i_gb),
+                             io.src<double>(i_s), io.dst<double>(o_s), io.dst<float>(o_w), io.dst<float>(o_g), io.dst<float>(o_rw))))
+        return rc;
+    return io.finish();
+}
+
+// seven inputs: SyncHostCall::kMax
+int align_volume_solve_group_r_host(msiren_ctx* h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                                    const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
+                                    const float* weights_host, const float* intensity_in, const double* scale_host, float* maps_out, float* intensity_out, double* rigid_out,
+                                    double* report, double* target_report, double* trace) {
+    const int64_t M = m * (int64_t)th * tw;
+    bool done;
+    int rc = check(h);
+    if ((rc = host_preamble(rc ? rc : align_volume_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report),
+                            M == 0, !images_host || !targets_host || !scale_host, n, height, width, &done)) || done) return rc;
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(images_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY);
+    const int i_p = io.in(planes, (size_t)m * 12 * sizeof(double), HOST_COPY), i_r = io.in(rigid_in, (size_t)G * 12 * sizeof(double), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_in, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int i_s = io.in(scale_host, (size_t)m * sizeof(double), HOST_COPY);
+    const int o_m = io.out(maps_out, (size_t)m * 9 * sizeof(float), HOST_COPY), o_gb = io.out(intensity_out, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_r = io.out(rigid_out, (size_t)G * 12 * sizeof(double), HOST_COPY), o_rep = io.out(report, (size_t)G * 7 * sizeof(double), HOST_COPY);
+    const int o_tr = io.out(target_report, (size_t)m * 3 * sizeof(double), HOST_COPY), o_trace = io.out(trace, (size_t)o->iterations * G * 15 * sizeof(double), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_volume_solve_group_r(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, o, group_start, G, io.src<double>(i_p), io.src<double>(i_r),
+                                         io.src<float>(i_w), io.src<float>(i_gb), io.src<double>(i_s), io.dst<float>(o_m), io.dst<float>(o_gb), io.dst<double>(o_r),
+                                         io.dst<double>(o_rep), io.dst<double>(o_tr), io.dst<double>(o_trace))))
+        return rc;
+    return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
+
+int msiren_align_volume_r(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                          const float* maps_host, const float* weights_host, const float* intensity_host, const double* scale_host, double* sums_host, float* warped_host,
+                          float* wgrad_host, float* rweight_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_volume_r_host(h, images_host, n, height, width, targets_host, m, th, tw, maps_host, weights_host, intensity_host, scale_host, sums_host, warped_host, wgrad_host,
+                               rweight_host);
+}
+int msiren_align_volume_r_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                              const float* maps_dev, const float* weights_dev, const float* intensity_dev, const double* scale_dev, double* sums_dev, float* warped_dev,
+                              float* wgrad_dev, float* rweight_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_volume_w_check(h, n, height, width, m, th, tw))) return rc;  // (before the stream rotates)
+    return align_volume_r(h, dev_call(h), images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, weights_dev, intensity_dev, scale_dev, sums_dev, warped_dev, wgrad_dev,
+                          rweight_dev);
+}
+int msiren_align_volume_solve_group_r(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th,
+                                      int32_t tw, const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start, int64_t n_groups, const double* planes,
+                                      const double* rigid_in, const float* weights_host, const float* intensity_in, const double* scale, float* maps_out, float* intensity_out,
+                                      double* rigid_out, double* report, double* target_report, double* trace) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_volume_solve_group_r_host(h, images_host, n, height, width, targets_host, m, th, tw, opts, group_start, n_groups, planes, rigid_in, weights_host, intensity_in,
+                                           scale, maps_out, intensity_out, rigid_out, report, target_report, trace);
+}
+int msiren_align_volume_solve_group_r_dev(msiren_handle h, const float* images_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                                          int32_t tw, const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start, int64_t n_groups, const double* planes_dev,
+                                          const double* rigid_in_dev, const float* weights_dev, const float* intensity_in_dev, const double* scale_dev, float* maps_out_dev,
+                                          float* intensity_out_dev, double* rigid_out_dev, double* report_dev, double* target_report_dev, double* trace_dev) {
+    int rc = check(h);
+    if (rc) return rc;
+    if ((rc = align_volume_solve_group_check(h, n, height, width, m, th, tw, opts, group_start, n_groups, planes_dev, rigid_in_dev, maps_out_dev, intensity_out_dev, report_dev)))
+        return rc;  // (before the stream rotates)
+    return align_volume_solve_group_r(h, dev_call(h), images_dev, n, height, width, targets_dev, m, th, tw, opts, group_start, n_groups, planes_dev, rigid_in_dev, weights_dev,
+                                      intensity_in_dev, scale_dev, maps_out_dev, intensity_out_dev, rigid_out_dev, report_dev, target_report_dev, trace_dev);
+}
 
 int msiren_align_volume_solve_group(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th,
                                     int32_t tw, const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start, int64_t n_groups, const double* planes,

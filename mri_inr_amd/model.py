@@ -1238,6 +1238,65 @@ class ModulatedSiren:
                                                              tr.ctypes.data if trace else None))
         return ag.solve_result_g(out, gout, rout, report, trep, tr)
 
+    def align_volume_cost_r(self, images, targets, maps, scale, *, weights=None, intensity=None, warped=False, gradient=False, rweight=False):
+        """``align_volume_cost_w`` under a robust (Geman-McClure) loss -> ``align_robust.AlignResultR``: ``scale`` a scalar or (m,), s = (c sigma)^2 in
+        squared intensity units; ``cost`` = sum w r^2 / (1 + r^2 / s) over the valid pixels, ``grad`` its exact gradient, ``jtj`` the majoriser's
+        Gauss-Newton matrix, ``wsum`` the plain sum of the weights (build-defined; msiren_align_volume_r).  A target whose
+        scale is not > 0 has count 0; with scale +inf the sums are ``align_volume_cost_w``'s bits.  ``rweight``: (m, th, tw) float32, the factor
+        1 / (1 + r^2 / s)^2 of every valid pixel (towards 0: rejected), NaN elsewhere."""
+        from . import align_robust as ar, align_volume as av
+
+        self._ensure_committed()
+        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
+        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        if mp.shape != (m, 9):
+            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
+        s = ar.scales(scale, m)
+        sums = np.zeros((m, av.SUMS_VW), np.float64)
+        wp = np.full((m, th, tw), np.nan, np.float32) if warped else None
+        g = np.full((3, m, th, tw), np.nan, np.float32) if gradient else None
+        rw = np.full((m, th, tw), np.nan, np.float32) if rweight else None
+        _lib.check(self._lib.msiren_align_volume_r(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, mp.ctypes.data, None if w is None else w.ctypes.data,
+                                                   None if gb is None else gb.ctypes.data, s.ctypes.data, sums.ctypes.data, wp.ctypes.data if warped else None,
+                                                   g.ctypes.data if gradient else None, rw.ctypes.data if rweight else None))
+        return ar.unpack_r(sums, wp, g, rw)
+
+    def align_volume_solve_group_robust(self, images, targets, planes, spacing, groups, scale, *, rotation=None, shift=None, weights=None, intensity=None,
+                                        estimate_intensity=True, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
+        """``align_volume_solve_group`` on ``align_volume_cost_r``: targets whose bad pixels come without a mask -> ``align_group.SolveResultG``.
+        ``scale`` a scalar or (m,), fixed for the call (``align_robust.scale_from`` gives one from a quadratic pass); every other argument, the step
+        rule and the result are ``align_volume_solve_group``'s, ``cost`` and the means the robust loss (build-defined, DESIGN.md section 5.16;
+        msiren_align_volume_solve_group_r); bit for bit what ``align_robust.solve_on_host_r`` gives around ``align_volume_cost_r``.  Groups of one
+        target each: the robust rigid solve per target.  With scale +inf: ``align_volume_solve_group``'s bits."""
+        from . import align_group as ag, align_robust as ar, align_volume as av
+
+        self._ensure_committed()
+        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
+        if pl.shape != (m, 12):
+            raise ValueError(f"expected planes of shape ({m}, 12), got {pl.shape}")
+        s = ar.scales(scale, m)
+        gs = np.ascontiguousarray(ag.group_offsets(groups, m), dtype=np.int32)
+        G = len(gs) - 1
+        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (G, 3, 3)).reshape(G, 9)
+        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (G, 3))
+        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
+        o = _lib.AlignVolumeSolveGroupOpts(C.sizeof(_lib.AlignVolumeSolveGroupOpts), int(iterations), av.ESTIMATE if estimate_intensity else av.FIXED, 0, float(damping),
+                                           float(down), float(up), float(lam_min), float(lam_max), float(spacing))
+        out = np.zeros((m, 9), np.float32)
+        gout = np.tile(np.array([1.0, 0.0], np.float32), (m, 1)) if gb is None else gb.copy()
+        rout, report, trep = rigid.copy(), np.zeros((G, 7), np.float64), np.zeros((m, 3), np.float64)
+        tr = np.zeros((max(int(iterations), 0), G, 15), np.float64) if trace else None
+        _lib.check(self._lib.msiren_align_volume_solve_group_r(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), gs.ctypes.data, G, pl.ctypes.data,
+                                                               rigid.ctypes.data, None if w is None else w.ctypes.data, None if gb is None else gb.ctypes.data,
+                                                               s.ctypes.data, out.ctypes.data, gout.ctypes.data, rout.ctypes.data, report.ctypes.data, trep.ctypes.data,
+                                                               tr.ctypes.data if trace else None))
+        return ag.solve_result_g(out, gout, rout, report, trep, tr)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
