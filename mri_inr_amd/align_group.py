@@ -13,8 +13,8 @@ import collections
 import numpy as np
 
 from .align import INF, NO_OVERLAP, RIGID, SINGULAR, _f32, ldl_solve, lm_decide  # noqa: F401
-from .align_volume import (ESTIMATE, FIXED, SUMS_VW, cayley3, intensity_update_vw, rigid_jacobian3, rigid_jacobian3_w,  # noqa: F401
-                           rigid_map3)
+from .align_volume import (ESTIMATE, FIXED, SUMS_VW, cayley3, cayley_update, intensity_update_vw, project_rigid, rigid_jacobian3,  # noqa: F401
+                           rigid_jacobian3_w, rigid_map3)
 
 SolveOptionsG = collections.namedtuple("SolveOptionsG", "iterations damping down up lam_min lam_max spacing intensity_mode",
                                        defaults=(12, 1e-3, 0.1, 10.0, 1e-9, 1e9, 1.0, ESTIMATE))
@@ -74,33 +74,13 @@ def project_member(bs, B, est):
     """One member's sums at the best state (80) and its B (11 x 8 estimated, 9 x 6 fixed) -> (t (Q), HQ (Q x Q, the lower triangle k >= r filled)):
     t[k] = sum_a B[a][k] g[a], HQ = B^T (H B), align_volume_step_w_kernel's expressions, undamped"""
     N, Q = (11, 8) if est else (9, 6)
-    g = bs[3:14]
     H = [[0.0] * 11 for _ in range(11)]
     s = 14
     for a in range(11):
         for b in range(a, 11):
             H[a][b] = H[b][a] = bs[s]
             s += 1
-    t = [0.0] * Q
-    for k in range(Q):
-        x = 0.0
-        for a in range(N):
-            x = x + B[a][k] * g[a]
-        t[k] = x
-    HQ = [[0.0] * Q for _ in range(Q)]
-    for r in range(Q):
-        Tc = [0.0] * N
-        for a in range(N):
-            x = 0.0
-            for b in range(N):
-                x = x + H[a][b] * B[b][r]
-            Tc[a] = x
-        for k in range(r, Q):
-            x = 0.0
-            for a in range(N):
-                x = x + B[a][k] * Tc[a]
-            HQ[k][r] = x
-    return t, HQ
+    return project_rigid(H, bs[3:14], B, N, Q)
 
 
 def eliminate_member(t, HQ, count, lam):
@@ -198,13 +178,7 @@ def lm_step_group(g, ts, sums, k, o):
     # 2. project, per member;  3. reduce and solve, per group
     d, ok, dgb = solve_group(project_group([t["sums"] for t in ts], [t["plane"] for t in ts], rb, lam, o), lam)
     # 4. propose
-    Cay = cayley3([d[0] / 2.0, d[1] / 2.0, d[2] / 2.0])
-    rt = [0.0] * 12
-    for r in range(3):
-        for c in range(3):
-            rt[3 * r + c] = ((Cay[r][0] * rb[c]) + (Cay[r][1] * rb[3 + c])) + (Cay[r][2] * rb[6 + c])
-    for a in range(3):
-        rt[9 + a] = rb[9 + a] + d[3 + a]
+    rt = cayley_update(rb, d)
     g["rigid_trial"] = rt
     for t, x in zip(ts, dgb):
         t["trial"] = rigid_map3(rt, t["plane"], sp)

@@ -153,6 +153,45 @@ def cayley3(a):
             [((t2 * a0) - t1) / den, ((t2 * a1) + t0) / den, (sc + (t2 * a2)) / den]]
 
 
+def project_rigid(H, g, B, N, Q):
+    """The system over the rigid parameters from the one over the map's: H (at least N x N, symmetric), g (at least N), B (N x Q) ->
+    (t (Q), HQ (Q x Q, the lower triangle k >= r filled, which ldl_solve reads)): t[k] = sum_a B[a][k] g[a], HQ = B^T (H B) column by column,
+    T[., r] = H B[., r], then HQ[k][r] = sum_a B[a][k] T[a][r] -- the expressions of align_volume_step_kernel, align_volume_step_w_kernel (rigid
+    mode) and align_group_project_kernel, undamped"""
+    t = [0.0] * Q
+    for k in range(Q):
+        x = 0.0
+        for a in range(N):
+            x = x + B[a][k] * g[a]
+        t[k] = x
+    HQ = [[0.0] * Q for _ in range(Q)]
+    for r in range(Q):
+        Tc = [0.0] * N
+        for a in range(N):
+            x = 0.0
+            for b in range(N):
+                x = x + H[a][b] * B[b][r]
+            Tc[a] = x
+        for k in range(r, Q):
+            x = 0.0
+            for a in range(N):
+                x = x + B[a][k] * Tc[a]
+            HQ[k][r] = x
+    return t, HQ
+
+
+def cayley_update(rb, d):
+    """the rigid state (Rot 9, u 3) behind the step d (w 3, u 3, ...): Rot' = Cay(w / 2) Rot, u' = u + d[3:6] -- align_cayley_update's expressions"""
+    Cay = cayley3([d[0] / 2.0, d[1] / 2.0, d[2] / 2.0])
+    rt = [0.0] * 12
+    for r in range(3):
+        for c in range(3):
+            rt[3 * r + c] = ((Cay[r][0] * rb[c]) + (Cay[r][1] * rb[3 + c])) + (Cay[r][2] * rb[6 + c])
+    for a in range(3):
+        rt[9 + a] = rb[9 + a] + d[3 + a]
+    return rt
+
+
 def lm_init_v(o, map_in=None, rigid_in=None, plane=None):
     """the state of one target before its first evaluation: a dict (trial, best, rigid_trial, rigid_best, plane, sums, mean_best, mean_first, lam,
     accepted, flags).  Affine: map_in (9); rigid: rigid_in (Rot 9, u 3) on plane (12), the trial map formed from it."""
@@ -199,36 +238,11 @@ def lm_step_v(st, sums, k, o):
     else:
         rb, pl, sp = st["rigid_best"], st["plane"], float(o.spacing)
         B = rigid_jacobian3(rb, pl, sp)
-        g6 = [0.0] * 6
-        for p in range(6):
-            t = 0.0
-            for a in range(9):
-                t = t + B[a][p] * g[a]
-            g6[p] = t
-        T = [[0.0] * 6 for _ in range(9)]
-        for a in range(9):
-            for p in range(6):
-                t = 0.0
-                for b in range(9):
-                    t = t + H[a][b] * B[b][p]
-                T[a][p] = t
-        A = [[0.0] * 6 for _ in range(6)]
-        for p in range(6):
-            for r in range(6):
-                t = 0.0
-                for a in range(9):
-                    t = t + B[a][p] * T[a][r]
-                A[p][r] = t
+        g6, A = project_rigid(H, g, B, 9, 6)
         for p in range(6):
             A[p][p] = A[p][p] + lam * A[p][p]
         d, ok = ldl_solve(A, [-0.5 * g6[p] for p in range(6)], 6)
-        Cay = cayley3([d[0] / 2.0, d[1] / 2.0, d[2] / 2.0])
-        rt = [0.0] * 12
-        for r in range(3):
-            for c in range(3):
-                rt[3 * r + c] = ((Cay[r][0] * rb[c]) + (Cay[r][1] * rb[3 + c])) + (Cay[r][2] * rb[6 + c])
-        for a in range(3):
-            rt[9 + a] = rb[9 + a] + d[3 + a]
+        rt = cayley_update(rb, d)
         st["rigid_trial"] = rt
         st["trial"] = rigid_map3(rt, pl, sp)
     st["flags"] = (0 if ok else SINGULAR) | (NO_OVERLAP if st["mean_first"] == INF else 0)
@@ -380,36 +394,11 @@ def lm_step_vw(st, sums, k, o):
         rb, pl, sp = st["rigid_best"], st["plane"], float(o.spacing)
         Q = 8 if est else 6
         B = rigid_jacobian3_w(rb, pl, sp) if est else rigid_jacobian3(rb, pl, sp)
-        gq = [0.0] * Q
-        for p in range(Q):
-            t = 0.0
-            for a in range(N):
-                t = t + B[a][p] * g[a]
-            gq[p] = t
-        T = [[0.0] * Q for _ in range(N)]
-        for a in range(N):
-            for p in range(Q):
-                t = 0.0
-                for b in range(N):
-                    t = t + H[a][b] * B[b][p]
-                T[a][p] = t
-        A = [[0.0] * Q for _ in range(Q)]
-        for p in range(Q):
-            for r in range(Q):
-                t = 0.0
-                for a in range(N):
-                    t = t + B[a][p] * T[a][r]
-                A[p][r] = t
+        gq, A = project_rigid(H, g, B, N, Q)
         for p in range(Q):
             A[p][p] = A[p][p] + lam * A[p][p]
         d, ok = ldl_solve(A, [-0.5 * gq[p] for p in range(Q)], Q)
-        Cay = cayley3([d[0] / 2.0, d[1] / 2.0, d[2] / 2.0])
-        rt = [0.0] * 12
-        for r in range(3):
-            for c in range(3):
-                rt[3 * r + c] = ((Cay[r][0] * rb[c]) + (Cay[r][1] * rb[3 + c])) + (Cay[r][2] * rb[6 + c])
-        for a in range(3):
-            rt[9 + a] = rb[9 + a] + d[3 + a]
+        rt = cayley_update(rb, d)
         st["rigid_trial"] = rt
         st["trial"] = rigid_map3(rt, pl, sp)
         dg, db = (d[6], d[7]) if est else (0.0, 0.0)

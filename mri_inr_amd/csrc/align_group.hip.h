@@ -15,6 +15,8 @@
 // The rule is restated by mri_inr_amd/align_group.py: lm_step_g -- fp64 + - * / one at a time, every sum in the order written there; a sum over
 // the members of a group starts with the first member's term.  Within a system every loop has constant bounds and is unrolled and nothing is
 // indexed at run time; plain stores, no atomics: a group's trajectory depends on that group only.
+// Shared with the per-target solves (align_volume.hip.h): B is align_rigid_jacobian3, the proposal align_cayley_update.  The projection in the
+// project kernel is its own copy of align_volume_step_w_kernel's (align_volume_w.hip.h says why).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -162,27 +164,11 @@ __global__ __launch_bounds__(256) void align_group_project_kernel(AlignGroupPara
     const double* bs = p.sums_best + (size_t)q * S;  // the sums at the best state
     double* rec = p.rec + (size_t)q * ALIGN_GROUP_REC;
     double B[N][Q];
-#pragma unroll
-    for (int a = 0; a < N; ++a)
-#pragma unroll
-        for (int k = 0; k < Q; ++k) B[a][k] = 0.0;
     {
-        double rb[12], pl[12], vi[3], vj[3], vo[3];
+        double rb[12], pl[12];
 #pragma unroll
         for (int a = 0; a < 12; ++a) rb[a] = p.rigid_best[(size_t)y * 12 + a], pl[a] = p.planes[(size_t)q * 12 + a];
-        align_rigid_vectors3(rb, pl, vi, vj, vo);
-#pragma unroll
-        for (int col = 0; col < 3; ++col) {
-            const double v0 = col == 0 ? vi[0] : col == 1 ? vj[0] : vo[0];
-            const double v1 = col == 0 ? vi[1] : col == 1 ? vj[1] : vo[1];
-            const double v2 = col == 0 ? vi[2] : col == 1 ? vj[2] : vo[2];
-            // e_0 x v = (0, -v2, v1);  e_1 x v = (v2, 0, -v0);  e_2 x v = (-v1, v0, 0)
-            B[col][1] = v2 / p.spacing, B[col][2] = (-v1) / p.spacing;
-            B[3 + col][0] = -v2, B[3 + col][2] = v0;
-            B[6 + col][0] = v1, B[6 + col][1] = -v0;
-        }
-        B[2][3] = 1.0 / p.spacing, B[5][4] = 1.0, B[8][5] = 1.0;
-        if (EST) B[N - 2][Q - 2] = 1.0, B[N - 1][Q - 1] = 1.0;
+        align_rigid_jacobian3<N, Q>(rb, pl, p.spacing, B);
     }
     double t6 = 0.0, t7 = 0.0;
 #pragma unroll
@@ -312,29 +298,10 @@ __global__ __launch_bounds__(256) void align_group_step_kernel(AlignGroupParams 
     }
     const bool ok = align_ldl_solve<6>(A, rhs, d);
     __asm__ volatile("" ::: "memory");
-    // Cayley: a = d[0:3] / 2, Cay = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a);  Rot' = Cay Rot, u' = u + d[3:6]
-    const double a0 = d[0] / 2.0, a1 = d[1] / 2.0, a2 = d[2] / 2.0;
-    const double q0 = a0 * a0, q1 = a1 * a1, q2 = a2 * a2;
-    const double q01 = q0 + q1, aa = q01 + q2;
-    const double den = 1.0 + aa, scl = 1.0 - aa;
-    const double t0 = 2.0 * a0, t1 = 2.0 * a1, t2 = 2.0 * a2;
-    double Cy[3][3];
-    Cy[0][0] = (scl + t0 * a0) / den, Cy[0][1] = (t0 * a1 - t2) / den, Cy[0][2] = (t0 * a2 + t1) / den;
-    Cy[1][0] = (t1 * a0 + t2) / den, Cy[1][1] = (scl + t1 * a1) / den, Cy[1][2] = (t1 * a2 - t0) / den;
-    Cy[2][0] = (t2 * a0 - t1) / den, Cy[2][1] = (t2 * a1 + t0) / den, Cy[2][2] = (scl + t2 * a2) / den;
     double rb[12], rt[12];
 #pragma unroll
     for (int a = 0; a < 12; ++a) rb[a] = p.rigid_best[(size_t)y * 12 + a];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double p0 = Cy[r][0] * rb[c], p1 = Cy[r][1] * rb[3 + c], p2 = Cy[r][2] * rb[6 + c];
-            const double s = p0 + p1;
-            rt[3 * r + c] = s + p2;
-        }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) rt[9 + a] = rb[9 + a] + d[3 + a];
+    align_cayley_update(d, rb, rt);
 #pragma unroll
     for (int a = 0; a < 12; ++a) p.rigid_trial[(size_t)y * 12 + a] = rt[a];
 #pragma unroll

@@ -19,6 +19,12 @@
 // record = [count, cost, dcost 9, jtj packed upper triangle row-major 45].  The order of every sum is align.hip.h's: thread t of a chunk adds
 // its pixels lo + t, lo + t + 256, ..., score_block_sum's combine for all 56 behind one barrier, the chunks of a target in index order.  No
 // floating-point atomics.
+//
+// What the volume families share lives here (align_volume_w.hip.h, align_volume_r.hip.h and align_group.hip.h call it; LAB_NOTES.md section 30):
+//   align_volume_pixel            R, gZ, gY, gX of one pixel with the optional warped / wgrad stores: all three partial kernels
+//   align_rigid_jacobian3<N, Q>   B of the rigid modes: both step kernels and align_group_project_kernel
+//   align_cayley_update           Rot' = Cay Rot, u' = u + d[3:6]: align_volume_step_w_kernel and align_group_step_kernel.  align_volume_step_kernel<RIGID>
+//                                 keeps these lines in its own body (through the function it spills), as it keeps its projection on the unpacked H
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -114,6 +120,42 @@ __global__ __launch_bounds__(256) void align_volume_fill_kernel(AlignVolumeParam
     }
 }
 
+// R, gZ, gY, gX of pixel gp, the bits of msiren_resample_volume_grad at its point: per plane the blend of both slices of the pair, then
+// resample_volume_blend_kernel's selection; gZ = R1 - R0 of the value plane; an invalid Z: NaN in all four.  [warped], [wgrad] (3, M) get them.
+// The three partial kernels (here, align_volume_w.hip.h, align_volume_r.hip.h) read their pixels through this.
+__device__ __forceinline__ void align_volume_pixel(const float* __restrict__ vals, const int* __restrict__ ent, const int* __restrict__ tile, const float* __restrict__ w,
+                                                   const int* __restrict__ black, const int* __restrict__ pair, const float* __restrict__ fz, float* __restrict__ warped,
+                                                   float* __restrict__ wgrad, size_t gp, size_t M, int K, int NPt, int T, float* R, float* gZ, float* gY, float* gX) {
+#pragma clang fp contract(off)
+    const int z0 = pair[gp];
+    float pl[3], dz;
+    if (z0 < 0) {  // invalid Z: NaN in every plane, as resample_volume_blend_kernel writes it
+        pl[0] = pl[1] = pl[2] = dz = __builtin_nanf("");
+    } else {
+        const float f = fz[gp], a0 = 1.0f - f;
+        const int* e0 = ent + 2 * gp * K;
+        const int* tl = tile + gp * K;
+        const float* ww = w + gp * K;
+        const int *b0 = black + (size_t)z0 * NPt, *b1 = black + (size_t)(z0 + 1) * NPt;
+        dz = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* v = vals + (size_t)c * T;
+            const float R0 = volume_slice_blend(v, e0, tl, ww, b0, K);
+            const float R1 = volume_slice_blend(v, e0 + K, tl, ww, b1, K);
+            pl[c] = f == 0.f ? R0 : f == 1.f ? R1 : __builtin_fmaf(f, R1, a0 * R0);
+            if (c == 0) dz = R1 - R0;
+        }
+    }
+    *R = pl[0], *gZ = dz, *gY = pl[1], *gX = pl[2];
+    if (warped) warped[gp] = pl[0];
+    if (wgrad) {
+        wgrad[gp] = dz;
+        wgrad[M + gp] = pl[1];
+        wgrad[2 * M + gp] = pl[2];
+    }
+}
+
 // vals (3, T): the jet ragged trunk's outputs by entry, T = 2 M K.  ent (2 M K), tile / w (M K), pair / fz (M): the fill kernel's.  black (n NPt).
 // targets (m, Mt).  warped (m, Mt) and wgrad (3, m, Mt) may be null.  partials (m chunks, ALIGN_VOLUME_SUMS).
 // grid: m * chunks workgroups (target-major), chunks = ceil(Mt / ALIGN_CHUNK)
@@ -132,33 +174,8 @@ __global__ __launch_bounds__(256) void align_volume_partial_kernel(const float* 
     for (int a = 0; a < ALIGN_VOLUME_SUMS; ++a) acc[a] = 0.0;
     for (int px = lo + threadIdx.x; px < hi; px += 256) {
         const size_t g = (size_t)q * Mt + px;
-        const int z0 = pair[g];
-        float pl[3], gZ;
-        if (z0 < 0) {  // invalid Z: NaN in every plane, as resample_volume_blend_kernel writes it
-            pl[0] = pl[1] = pl[2] = gZ = __builtin_nanf("");
-        } else {
-            const float f = fz[g], a0 = 1.0f - f;
-            const int* e0 = ent + 2 * g * K;
-            const int* tl = tile + g * K;
-            const float* ww = w + g * K;
-            const int *b0 = black + (size_t)z0 * NPt, *b1 = black + (size_t)(z0 + 1) * NPt;
-            gZ = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* v = vals + (size_t)c * T;
-                const float R0 = volume_slice_blend(v, e0, tl, ww, b0, K);
-                const float R1 = volume_slice_blend(v, e0 + K, tl, ww, b1, K);
-                pl[c] = f == 0.f ? R0 : f == 1.f ? R1 : __builtin_fmaf(f, R1, a0 * R0);
-                if (c == 0) gZ = R1 - R0;
-            }
-        }
-        const float R = pl[0], gY = pl[1], gX = pl[2];
-        if (warped) warped[g] = R;
-        if (wgrad) {
-            wgrad[g] = gZ;
-            wgrad[M + g] = gY;
-            wgrad[2 * M + g] = gX;
-        }
+        float R, gZ, gY, gX;
+        align_volume_pixel(vals, ent, tile, w, black, pair, fz, warped, wgrad, g, M, K, NPt, T, &R, &gZ, &gY, &gX);
         const float tv = targets[g];
         if (align_finite(tv) && align_finite(R) && align_finite(gZ) && align_finite(gY) && align_finite(gX)) {
             const int i = px / tw, j = px - i * tw;
@@ -248,6 +265,59 @@ __device__ __forceinline__ void align_rigid_map3(const double (&st)[12], const d
         if (r == 0) mp[0] = (float)(vi[0] / spacing), mp[1] = (float)(vj[0] / spacing), mp[2] = (float)(t / spacing);
         else mp[3 * r] = (float)vi[r], mp[3 * r + 1] = (float)vj[r], mp[3 * r + 2] = (float)t;
     }
+}
+
+// B (N x Q), N = 9 or 11, Q = 6 or 8: d map / d (w, u) at the rigid state rb on the plane pl, rigid_jacobian3's entries (mri_inr_amd/align_volume.py):
+// B[3 r + col][k] = (e_k x v_col)[r], v_col = v_i, v_j, v_o;  B[3 r + 2][3 + k] = [r == k];  the rows of Z over the spacing;  N = 11: then
+// B[9][6] = B[10][7] = 1 for the intensity;  every other entry 0.  Both step kernels and align_group_project_kernel form their B here.
+template <int N, int Q>
+__device__ __forceinline__ void align_rigid_jacobian3(const double (&rb)[12], const double (&pl)[12], double spacing, double (&B)[N][Q]) {
+#pragma clang fp contract(off)
+    static_assert((N == 9 && Q == 6) || (N == 11 && Q == 8), "the map's nine over the motion's six, or both with the intensity's two");
+#pragma unroll
+    for (int a = 0; a < N; ++a)
+#pragma unroll
+        for (int k = 0; k < Q; ++k) B[a][k] = 0.0;
+    double vi[3], vj[3], vo[3];
+    align_rigid_vectors3(rb, pl, vi, vj, vo);
+#pragma unroll
+    for (int col = 0; col < 3; ++col) {
+        const double v0 = col == 0 ? vi[0] : col == 1 ? vj[0] : vo[0];
+        const double v1 = col == 0 ? vi[1] : col == 1 ? vj[1] : vo[1];
+        const double v2 = col == 0 ? vi[2] : col == 1 ? vj[2] : vo[2];
+        // e_0 x v = (0, -v2, v1);  e_1 x v = (v2, 0, -v0);  e_2 x v = (-v1, v0, 0)
+        B[col][1] = v2 / spacing, B[col][2] = (-v1) / spacing;
+        B[3 + col][0] = -v2, B[3 + col][2] = v0;
+        B[6 + col][0] = v1, B[6 + col][1] = -v0;
+    }
+    B[2][3] = 1.0 / spacing, B[5][4] = 1.0, B[8][5] = 1.0;
+    if (N == 11) B[N - 2][Q - 2] = 1.0, B[N - 1][Q - 1] = 1.0;
+}
+
+// the rigid state rt behind the step d = (w 3, u 3, ...) from the state rb, cayley_update's rule (mri_inr_amd/align_volume.py):
+// Cayley: a = d[0:3] / 2, Cay = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a);  Rot' = Cay Rot, u' = u + d[3:6]
+template <int Q>
+__device__ __forceinline__ void align_cayley_update(const double (&d)[Q], const double (&rb)[12], double (&rt)[12]) {
+#pragma clang fp contract(off)
+    const double a0 = d[0] / 2.0, a1 = d[1] / 2.0, a2 = d[2] / 2.0;
+    const double q0 = a0 * a0, q1 = a1 * a1, q2 = a2 * a2;
+    const double q01 = q0 + q1, aa = q01 + q2;
+    const double den = 1.0 + aa, sc = 1.0 - aa;
+    const double t0 = 2.0 * a0, t1 = 2.0 * a1, t2 = 2.0 * a2;
+    double C[3][3];
+    C[0][0] = (sc + t0 * a0) / den, C[0][1] = (t0 * a1 - t2) / den, C[0][2] = (t0 * a2 + t1) / den;
+    C[1][0] = (t1 * a0 + t2) / den, C[1][1] = (sc + t1 * a1) / den, C[1][2] = (t1 * a2 - t0) / den;
+    C[2][0] = (t2 * a0 - t1) / den, C[2][1] = (t2 * a1 + t0) / den, C[2][2] = (sc + t2 * a2) / den;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double p0 = C[r][0] * rb[c], p1 = C[r][1] * rb[3 + c], p2 = C[r][2] * rb[6 + c];
+            const double s = p0 + p1;
+            rt[3 * r + c] = s + p2;
+        }
+#pragma unroll
+    for (int a = 0; a < 3; ++a) rt[9 + a] = rb[9 + a] + d[3 + a];
 }
 
 // before the first evaluation: trial := best := the input (rigid: the map of the input state), lam := damping, nothing accepted
@@ -342,28 +412,12 @@ __global__ __launch_bounds__(256) void align_volume_step_kernel(AlignVolumeSolve
 #pragma unroll
         for (int a = 0; a < 9; ++a) trial[a] = (float)((double)p.best[(size_t)q * 9 + a] + d[a]);
     } else {
-        // B (9 x 6): B[3 r + col][k] = (e_k x v_col)[r], v_col = v_i, v_j, v_o;  B[3 r + 2][3 + k] = [r == k];  the rows of Z over the spacing
         double B[9][6];
-#pragma unroll
-        for (int a = 0; a < 9; ++a)
-#pragma unroll
-            for (int k = 0; k < 6; ++k) B[a][k] = 0.0;
         {
-            double rb[12], pl[12], vi[3], vj[3], vo[3];
+            double rb[12], pl[12];
 #pragma unroll
             for (int a = 0; a < 12; ++a) rb[a] = p.rigid_best[(size_t)q * 12 + a], pl[a] = p.planes[(size_t)q * 12 + a];
-            align_rigid_vectors3(rb, pl, vi, vj, vo);
-#pragma unroll
-            for (int col = 0; col < 3; ++col) {
-                const double v0 = col == 0 ? vi[0] : col == 1 ? vj[0] : vo[0];
-                const double v1 = col == 0 ? vi[1] : col == 1 ? vj[1] : vo[1];
-                const double v2 = col == 0 ? vi[2] : col == 1 ? vj[2] : vo[2];
-                // e_0 x v = (0, -v2, v1);  e_1 x v = (v2, 0, -v0);  e_2 x v = (-v1, v0, 0)
-                B[col][1] = v2 / p.spacing, B[col][2] = (-v1) / p.spacing;
-                B[3 + col][0] = -v2, B[3 + col][2] = v0;
-                B[6 + col][0] = v1, B[6 + col][1] = -v0;
-            }
-            B[2][3] = 1.0 / p.spacing, B[5][4] = 1.0, B[8][5] = 1.0;
+            align_rigid_jacobian3<9, 6>(rb, pl, p.spacing, B);
         }
         double A[6][6], rhs[6], d[6];
 #pragma unroll
@@ -416,7 +470,7 @@ __global__ __launch_bounds__(256) void align_volume_step_kernel(AlignVolumeSolve
         }
         ok = align_ldl_solve<6>(A, rhs, d);
         __asm__ volatile("" ::: "memory");
-        // Cayley: a = d[0:3] / 2, Cay = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a);  Rot' = Cay Rot, u' = u + d[3:6]
+        // align_cayley_update's expressions in line: through the function this instantiation, which fills the register file, spills four registers
         const double a0 = d[0] / 2.0, a1 = d[1] / 2.0, a2 = d[2] / 2.0;
         const double q0 = a0 * a0, q1 = a1 * a1, q2 = a2 * a2;
         const double q01 = q0 + q1, aa = q01 + q2;

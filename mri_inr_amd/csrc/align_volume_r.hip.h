@@ -13,12 +13,22 @@
 // cost is the weighted loss, dcost its exact gradient, jtj the majoriser's (IRLS) Gauss-Newton matrix, wsum the plain sum of the weights.  With
 // s = +inf: u = 0, v = om = 1, wl = wq = wd, and every term is align_volume_partial_w_kernel's term -- the same bits.
 // rweight (m, Mt) float32, optional: (float)(om om) at a valid pixel, NaN elsewhere (the outlier map).
+// The kernel's body is align_volume_partial_w_body<true> (align_volume_w.hip.h), shared with the weighted reduce; here are the robust factors it
+// calls and the kernel as a wrapper.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "align_volume_w.hip.h"
 
 namespace msiren {
+
+// u = (r r) / s,  v = 1.0 + u,  om = 1.0 / v  ->  wl = wd om,  wq = wl om,  rw = (float)(om om)
+__device__ __forceinline__ void align_robust_factors(double wd, double r, double s, double* wl, double* wq, float* rw) {
+#pragma clang fp contract(off)
+    const double rr = r * r, u = rr / s, v = 1.0 + u, om = 1.0 / v;
+    *wl = wd * om, *wq = *wl * om;
+    *rw = (float)(om * om);
+}
 
 // scale (m) doubles.  rweight (m, Mt) may be null.  Every other argument and the grid: align_volume_partial_w_kernel's
 __global__ __launch_bounds__(256) void align_volume_partial_r_kernel(const float* __restrict__ vals, const int* __restrict__ ent, const int* __restrict__ tile,
@@ -28,76 +38,8 @@ __global__ __launch_bounds__(256) void align_volume_partial_r_kernel(const float
                                                                      const double* __restrict__ scale, float* __restrict__ warped, float* __restrict__ wgrad,
                                                                      float* __restrict__ rweight, double* __restrict__ partials, int m, int Mt, int tw, int K, int NPt,
                                                                      int T, int chunks) {
-#pragma clang fp contract(off)
-    __shared__ double red[ALIGN_VOLUME_SUMS_W][4];
-    const int q = blockIdx.x / chunks, chunk = blockIdx.x - q * chunks;
-    const int lo = chunk * ALIGN_CHUNK, hi = lo + ALIGN_CHUNK < Mt ? lo + ALIGN_CHUNK : Mt;
-    const size_t M = (size_t)m * Mt;
-    const double g = intensity ? (double)intensity[(size_t)q * 2] : 1.0, b = intensity ? (double)intensity[(size_t)q * 2 + 1] : 0.0;
-    const double s = scale[q];
-    const bool scored = s > 0.0;  // (false for a NaN)
-    double acc[ALIGN_VOLUME_SUMS_W];
-#pragma unroll
-    for (int a = 0; a < ALIGN_VOLUME_SUMS_W; ++a) acc[a] = 0.0;
-    for (int px = lo + threadIdx.x; px < hi; px += 256) {
-        const size_t gp = (size_t)q * Mt + px;
-        const int z0 = pair[gp];
-        float pl[3], gZ;
-        if (z0 < 0) {  // invalid Z: NaN in every plane, as resample_volume_blend_kernel writes it
-            pl[0] = pl[1] = pl[2] = gZ = __builtin_nanf("");
-        } else {
-            const float f = fz[gp], a0 = 1.0f - f;
-            const int* e0 = ent + 2 * gp * K;
-            const int* tl = tile + gp * K;
-            const float* ww = w + gp * K;
-            const int *b0 = black + (size_t)z0 * NPt, *b1 = black + (size_t)(z0 + 1) * NPt;
-            gZ = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* v = vals + (size_t)c * T;
-                const float R0 = volume_slice_blend(v, e0, tl, ww, b0, K);
-                const float R1 = volume_slice_blend(v, e0 + K, tl, ww, b1, K);
-                pl[c] = f == 0.f ? R0 : f == 1.f ? R1 : __builtin_fmaf(f, R1, a0 * R0);
-                if (c == 0) gZ = R1 - R0;
-            }
-        }
-        const float R = pl[0], gY = pl[1], gX = pl[2];
-        if (warped) warped[gp] = R;
-        if (wgrad) {
-            wgrad[gp] = gZ;
-            wgrad[M + gp] = gY;
-            wgrad[2 * M + gp] = gX;
-        }
-        const float tv = targets[gp], wv = weights ? weights[gp] : 1.f;
-        float rw = __builtin_nanf("");
-        if (scored && align_finite(tv) && align_finite(R) && align_finite(gZ) && align_finite(gY) && align_finite(gX) && align_finite(wv) && wv > 0.f) {
-            const int i = px / tw, j = px - i * tw;
-            const double wd = (double)wv, gr = g * (double)R, mm = gr + b, di = (double)i, dj = (double)j;
-            const double r = mm - (double)tv, gz = g * (double)gZ, gy = g * (double)gY, gx = g * (double)gX;
-            const double rr = r * r, u = rr / s, v = 1.0 + u, om = 1.0 / v;
-            const double wl = wd * om, wq = wl * om;
-            const double wlr = wl * r, wqr = wq * r, wr2 = 2.0 * wqr;
-            rw = (float)(om * om);
-            double J[11];
-            J[0] = gz * di, J[1] = gz * dj, J[2] = gz;
-            J[3] = gy * di, J[4] = gy * dj, J[5] = gy;
-            J[6] = gx * di, J[7] = gx * dj, J[8] = gx;
-            J[9] = (double)R, J[10] = 1.0;
-            acc[0] += 1.0;
-            acc[1] += wd;
-            acc[2] += wlr * r;
-            int t = 14;
-#pragma unroll
-            for (int a = 0; a < 11; ++a) {
-                acc[3 + a] += wr2 * J[a];
-                const double wj = wq * J[a];
-#pragma unroll
-                for (int c = a; c < 11; ++c, ++t) acc[t] += wj * J[c];
-            }
-        }
-        if (rweight) rweight[gp] = rw;
-    }
-    align_block_reduce<ALIGN_VOLUME_SUMS_W>(acc, red, partials);
+    align_volume_partial_w_body<true>(vals, ent, tile, w, black, pair, fz, targets, weights, intensity, scale, warped, wgrad, rweight, partials, m, Mt, tw, K, NPt, T,
+                                      chunks);
 }
 
 }  // namespace msiren

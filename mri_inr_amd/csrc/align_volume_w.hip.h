@@ -13,6 +13,12 @@
 // record = [count, wsum, cost, dcost 11, jtj packed upper triangle row-major 66].  With g = 1, b = 0, w = 1 every term over the map's nine
 // parameters is align_volume_partial_kernel's term; a weight that is a power of two scales wsum, cost, dcost and jtj exactly.  The order of every
 // sum is align.hip.h's.
+//
+// Shared: the pixel, B and the Cayley update are align_volume.hip.h's functions.  The reduce is align_volume_partial_w_body<ROBUST> below, which
+// align_volume_r.hip.h instantiates for the robust loss; align_volume_partial_w_kernel is its ROBUST = false instance and carries nothing of the
+// other (no scale, no division, no rweight).  The projection t = B^T g, HQ = B^T (H B) on the packed sums stands twice, in the step kernel below
+// and in align_group_project_kernel: as one function it took align_volume_step_w_kernel<RIGID, 1> over its recorded registers (LAB_NOTES.md
+// section 30); mri_inr_amd/align_volume.py: project_rigid is the one statement of it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -22,6 +28,68 @@ namespace msiren {
 
 constexpr int ALIGN_VOLUME_SUMS_W = 80;  // count, wsum, cost, dcost[11], jtj[66]
 
+// the robust factors of a valid pixel (align_volume_r.hip.h): wl for the cost, wq for dcost and jtj, rw the outlier weight
+__device__ __forceinline__ void align_robust_factors(double wd, double r, double s, double* wl, double* wq, float* rw);
+
+// The reduce of the 80 sums under the square loss (ROBUST = false: align_volume_partial_w_kernel, wl = wq = w, neither scale nor rweight is touched)
+// or the Geman-McClure loss (ROBUST = true: align_volume_partial_r_kernel, scale (m) doubles, rweight (m, Mt) or null).  Per valid pixel
+//     count += 1, wsum += w, cost += (wl r) r, dcost[a] += (2 (wq r)) J[a], jtj[a, b] += (wq J[a]) J[b] (a <= b)
+template <bool ROBUST>
+__device__ __forceinline__ void align_volume_partial_w_body(const float* __restrict__ vals, const int* __restrict__ ent, const int* __restrict__ tile,
+                                                            const float* __restrict__ w, const int* __restrict__ black, const int* __restrict__ pair,
+                                                            const float* __restrict__ fz, const float* __restrict__ targets, const float* __restrict__ weights,
+                                                            const float* __restrict__ intensity, const double* __restrict__ scale, float* __restrict__ warped,
+                                                            float* __restrict__ wgrad, float* __restrict__ rweight, double* __restrict__ partials, int m, int Mt,
+                                                            int tw, int K, int NPt, int T, int chunks) {
+#pragma clang fp contract(off)
+    __shared__ double red[ALIGN_VOLUME_SUMS_W][4];
+    const int q = blockIdx.x / chunks, chunk = blockIdx.x - q * chunks;
+    const int lo = chunk * ALIGN_CHUNK, hi = lo + ALIGN_CHUNK < Mt ? lo + ALIGN_CHUNK : Mt;
+    const size_t M = (size_t)m * Mt;
+    const double g = intensity ? (double)intensity[(size_t)q * 2] : 1.0, b = intensity ? (double)intensity[(size_t)q * 2 + 1] : 0.0;
+    double s = 0.0;
+    if constexpr (ROBUST) s = scale[q];
+    const bool scored = !ROBUST || s > 0.0;  // (false for a NaN)
+    double acc[ALIGN_VOLUME_SUMS_W];
+#pragma unroll
+    for (int a = 0; a < ALIGN_VOLUME_SUMS_W; ++a) acc[a] = 0.0;
+    for (int px = lo + threadIdx.x; px < hi; px += 256) {
+        const size_t gp = (size_t)q * Mt + px;
+        float R, gZ, gY, gX;
+        align_volume_pixel(vals, ent, tile, w, black, pair, fz, warped, wgrad, gp, M, K, NPt, T, &R, &gZ, &gY, &gX);
+        const float tv = targets[gp], wv = weights ? weights[gp] : 1.f;
+        float rw = __builtin_nanf("");
+        if (scored && align_finite(tv) && align_finite(R) && align_finite(gZ) && align_finite(gY) && align_finite(gX) && align_finite(wv) && wv > 0.f) {
+            const int i = px / tw, j = px - i * tw;
+            const double wd = (double)wv, gr = g * (double)R, mm = gr + b, di = (double)i, dj = (double)j;
+            const double r = mm - (double)tv, gz = g * (double)gZ, gy = g * (double)gY, gx = g * (double)gX;
+            double wl = wd, wq = wd;
+            if constexpr (ROBUST) align_robust_factors(wd, r, s, &wl, &wq, &rw);
+            const double wlr = wl * r, wqr = wq * r, wr2 = 2.0 * wqr;
+            double J[11];
+            J[0] = gz * di, J[1] = gz * dj, J[2] = gz;
+            J[3] = gy * di, J[4] = gy * dj, J[5] = gy;
+            J[6] = gx * di, J[7] = gx * dj, J[8] = gx;
+            J[9] = (double)R, J[10] = 1.0;
+            acc[0] += 1.0;
+            acc[1] += wd;
+            acc[2] += wlr * r;
+            int t = 14;
+#pragma unroll
+            for (int a = 0; a < 11; ++a) {
+                acc[3 + a] += wr2 * J[a];
+                const double wj = wq * J[a];
+#pragma unroll
+                for (int c = a; c < 11; ++c, ++t) acc[t] += wj * J[c];
+            }
+        }
+        if constexpr (ROBUST) {
+            if (rweight) rweight[gp] = rw;
+        }
+    }
+    align_block_reduce<ALIGN_VOLUME_SUMS_W>(acc, red, partials);
+}
+
 // weights (m, Mt) and intensity (m, 2) may be null: every weight 1, (g, b) = (1, 0).  partials (m chunks, ALIGN_VOLUME_SUMS_W).  The grid and every
 // other argument: align_volume_partial_kernel's
 __global__ __launch_bounds__(256) void align_volume_partial_w_kernel(const float* __restrict__ vals, const int* __restrict__ ent, const int* __restrict__ tile,
@@ -30,69 +98,8 @@ __global__ __launch_bounds__(256) void align_volume_partial_w_kernel(const float
                                                                      const float* __restrict__ weights, const float* __restrict__ intensity,
                                                                      float* __restrict__ warped, float* __restrict__ wgrad, double* __restrict__ partials, int m,
                                                                      int Mt, int tw, int K, int NPt, int T, int chunks) {
-#pragma clang fp contract(off)
-    __shared__ double red[ALIGN_VOLUME_SUMS_W][4];
-    const int q = blockIdx.x / chunks, chunk = blockIdx.x - q * chunks;
-    const int lo = chunk * ALIGN_CHUNK, hi = lo + ALIGN_CHUNK < Mt ? lo + ALIGN_CHUNK : Mt;
-    const size_t M = (size_t)m * Mt;
-    const double g = intensity ? (double)intensity[(size_t)q * 2] : 1.0, b = intensity ? (double)intensity[(size_t)q * 2 + 1] : 0.0;
-    double acc[ALIGN_VOLUME_SUMS_W];
-#pragma unroll
-    for (int a = 0; a < ALIGN_VOLUME_SUMS_W; ++a) acc[a] = 0.0;
-    for (int px = lo + threadIdx.x; px < hi; px += 256) {
-        const size_t gp = (size_t)q * Mt + px;
-        const int z0 = pair[gp];
-        float pl[3], gZ;
-        if (z0 < 0) {  // invalid Z: NaN in every plane, as resample_volume_blend_kernel writes it
-            pl[0] = pl[1] = pl[2] = gZ = __builtin_nanf("");
-        } else {
-            const float f = fz[gp], a0 = 1.0f - f;
-            const int* e0 = ent + 2 * gp * K;
-            const int* tl = tile + gp * K;
-            const float* ww = w + gp * K;
-            const int *b0 = black + (size_t)z0 * NPt, *b1 = black + (size_t)(z0 + 1) * NPt;
-            gZ = 0.f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float* v = vals + (size_t)c * T;
-                const float R0 = volume_slice_blend(v, e0, tl, ww, b0, K);
-                const float R1 = volume_slice_blend(v, e0 + K, tl, ww, b1, K);
-                pl[c] = f == 0.f ? R0 : f == 1.f ? R1 : __builtin_fmaf(f, R1, a0 * R0);
-                if (c == 0) gZ = R1 - R0;
-            }
-        }
-        const float R = pl[0], gY = pl[1], gX = pl[2];
-        if (warped) warped[gp] = R;
-        if (wgrad) {
-            wgrad[gp] = gZ;
-            wgrad[M + gp] = gY;
-            wgrad[2 * M + gp] = gX;
-        }
-        const float tv = targets[gp], wv = weights ? weights[gp] : 1.f;
-        if (align_finite(tv) && align_finite(R) && align_finite(gZ) && align_finite(gY) && align_finite(gX) && align_finite(wv) && wv > 0.f) {
-            const int i = px / tw, j = px - i * tw;
-            const double wd = (double)wv, gr = g * (double)R, mm = gr + b, di = (double)i, dj = (double)j;
-            const double r = mm - (double)tv, gz = g * (double)gZ, gy = g * (double)gY, gx = g * (double)gX;
-            const double wr = wd * r, wr2 = 2.0 * wr;
-            double J[11];
-            J[0] = gz * di, J[1] = gz * dj, J[2] = gz;
-            J[3] = gy * di, J[4] = gy * dj, J[5] = gy;
-            J[6] = gx * di, J[7] = gx * dj, J[8] = gx;
-            J[9] = (double)R, J[10] = 1.0;
-            acc[0] += 1.0;
-            acc[1] += wd;
-            acc[2] += wr * r;
-            int s = 14;
-#pragma unroll
-            for (int a = 0; a < 11; ++a) {
-                acc[3 + a] += wr2 * J[a];
-                const double wj = wd * J[a];
-#pragma unroll
-                for (int c = a; c < 11; ++c, ++s) acc[s] += wj * J[c];
-            }
-        }
-    }
-    align_block_reduce<ALIGN_VOLUME_SUMS_W>(acc, red, partials);
+    align_volume_partial_w_body<false>(vals, ent, tile, w, black, pair, fz, targets, weights, intensity, nullptr, warped, wgrad, nullptr, partials, m, Mt, tw, K, NPt, T,
+                                       chunks);
 }
 
 // sums[q, a] = the target's partial records added in index order
@@ -220,30 +227,14 @@ __global__ __launch_bounds__(256) void align_volume_step_w_kernel(AlignVolumeSol
         for (int a = 0; a < 9; ++a) trial[a] = (float)((double)p.best[(size_t)q * 9 + a] + d[a]);
         dg = EST ? d[N - 2] : 0.0, db = EST ? d[N - 1] : 0.0;
     } else {
-        // B (N x Q): align_volume_step_kernel's 9 x 6 block, then B[9][6] = B[10][7] = 1 where the intensity is estimated
+        // B (N x Q): the map's nine over the motion's six; estimating, (g, b) over themselves
         constexpr int Q = EST ? 8 : 6;
         double B[N][Q];
-#pragma unroll
-        for (int a = 0; a < N; ++a)
-#pragma unroll
-            for (int k = 0; k < Q; ++k) B[a][k] = 0.0;
         {
-            double rb[12], pl[12], vi[3], vj[3], vo[3];
+            double rb[12], pl[12];
 #pragma unroll
             for (int a = 0; a < 12; ++a) rb[a] = p.rigid_best[(size_t)q * 12 + a], pl[a] = p.planes[(size_t)q * 12 + a];
-            align_rigid_vectors3(rb, pl, vi, vj, vo);
-#pragma unroll
-            for (int col = 0; col < 3; ++col) {
-                const double v0 = col == 0 ? vi[0] : col == 1 ? vj[0] : vo[0];
-                const double v1 = col == 0 ? vi[1] : col == 1 ? vj[1] : vo[1];
-                const double v2 = col == 0 ? vi[2] : col == 1 ? vj[2] : vo[2];
-                // e_0 x v = (0, -v2, v1);  e_1 x v = (v2, 0, -v0);  e_2 x v = (-v1, v0, 0)
-                B[col][1] = v2 / p.spacing, B[col][2] = (-v1) / p.spacing;
-                B[3 + col][0] = -v2, B[3 + col][2] = v0;
-                B[6 + col][0] = v1, B[6 + col][1] = -v0;
-            }
-            B[2][3] = 1.0 / p.spacing, B[5][4] = 1.0, B[8][5] = 1.0;
-            if (EST) B[N - 2][Q - 2] = 1.0, B[N - 1][Q - 1] = 1.0;
+            align_rigid_jacobian3<N, Q>(rb, pl, p.spacing, B);
         }
         double A[Q][Q], rhs[Q], d[Q];
 #pragma unroll
@@ -289,29 +280,10 @@ __global__ __launch_bounds__(256) void align_volume_step_w_kernel(AlignVolumeSol
         }
         ok = align_ldl_solve<Q>(A, rhs, d);
         __asm__ volatile("" ::: "memory");
-        // Cayley: a = d[0:3] / 2, Cay = ((1 - a.a) I + 2 a a^T + 2 [a]x) / (1 + a.a);  Rot' = Cay Rot, u' = u + d[3:6]
-        const double a0 = d[0] / 2.0, a1 = d[1] / 2.0, a2 = d[2] / 2.0;
-        const double q0 = a0 * a0, q1 = a1 * a1, q2 = a2 * a2;
-        const double q01 = q0 + q1, aa = q01 + q2;
-        const double den = 1.0 + aa, sc = 1.0 - aa;
-        const double t0 = 2.0 * a0, t1 = 2.0 * a1, t2 = 2.0 * a2;
-        double C[3][3];
-        C[0][0] = (sc + t0 * a0) / den, C[0][1] = (t0 * a1 - t2) / den, C[0][2] = (t0 * a2 + t1) / den;
-        C[1][0] = (t1 * a0 + t2) / den, C[1][1] = (sc + t1 * a1) / den, C[1][2] = (t1 * a2 - t0) / den;
-        C[2][0] = (t2 * a0 - t1) / den, C[2][1] = (t2 * a1 + t0) / den, C[2][2] = (sc + t2 * a2) / den;
         double rb[12], pl[12], rt[12];
 #pragma unroll
         for (int a = 0; a < 12; ++a) rb[a] = p.rigid_best[(size_t)q * 12 + a], pl[a] = p.planes[(size_t)q * 12 + a];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const double p0 = C[r][0] * rb[c], p1 = C[r][1] * rb[3 + c], p2 = C[r][2] * rb[6 + c];
-                const double s = p0 + p1;
-                rt[3 * r + c] = s + p2;
-            }
-#pragma unroll
-        for (int a = 0; a < 3; ++a) rt[9 + a] = rb[9 + a] + d[3 + a];
+        align_cayley_update(d, rb, rt);
         align_rigid_map3(rt, pl, p.spacing, trial);
 #pragma unroll
         for (int a = 0; a < 12; ++a) p.rigid_trial[(size_t)q * 12 + a] = rt[a];

@@ -224,10 +224,11 @@ int align_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t
 int align_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int32_t th, int32_t tw) {
     int rc = align_check(h, n, height, width, th, tw);
     if (rc) return rc;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    if (!msiren::align_pixels_fit(n, (int64_t)th * tw, K, msiren::ALIGN_SUMS_W))
+    Geom g;
+    (void)geom_check(h, height, width, &g);  // (align_check passed it)
+    if (!msiren::align_pixels_fit(n, (int64_t)th * tw, g.K, msiren::ALIGN_SUMS_W))
         return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld slices x %d x %d target pixels x %d covering tiles (20 n th tw K must stay below 2^30)",
-                    (long long)n, th, tw, K);
+                    (long long)n, th, tw, g.K);
     return 0;
 }
 
@@ -249,10 +250,11 @@ int align_volume_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, 
 int align_volume_w_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw) {
     int rc = align_volume_check(h, n, height, width, m, th, tw);
     if (rc) return rc;
-    const int KA = (h->S + h->I - 1) / h->I, K = KA * KA;
-    if (!msiren::align_volume_pixels_fit(m, (int64_t)th * tw, K, msiren::ALIGN_VOLUME_SUMS_W))
+    Geom g;
+    (void)geom_check(h, height, width, &g);  // (align_volume_check passed it)
+    if (!msiren::align_volume_pixels_fit(m, (int64_t)th * tw, g.K, msiren::ALIGN_VOLUME_SUMS_W))
         return fail(MSIREN_E_INVALID, "too many pixels for one call: %lld targets x %d x %d pixels x %d covering tiles (32 m th tw K + 8 m th tw with 640 bytes per chunk of 1024 pixels must stay below 2^30)",
-                    (long long)m, th, tw, K);
+                    (long long)m, th, tw, g.K);
     return 0;
 }
 
@@ -454,21 +456,30 @@ static void solve_params(SP& sp, char* base, const msiren::SolveLayout& s, const
     sp.down = o.down, sp.up = o.up, sp.lam_min = o.lam_min, sp.lam_max = o.lam_max;
 }
 
-// the loop behind the family's init kernel: evaluation k at the trial maps, then `step` over the units as one profile entry `name`
-template <typename SP>
-static int solve_loop(msiren_handle h, const Call& c, const AlignPlan& a, SP& sp, int iterations, void (*step)(SP), const char* name) {
+// the loop behind a family's init kernel with the step stage as a callable: evaluation k at the trial maps, then `stage(k, last)` as one profile
+// entry `name`
+template <typename Stage>
+static int solve_loop_staged(msiren_handle h, const Call& c, const AlignPlan& a, const float* trial, double* sums, int iterations, const char* name, Stage stage) {
     int rc;
-    hipStream_t st = h->sc[c.stream].s;
     for (int k = 0; k < iterations; ++k) {
-        if ((rc = align_evaluate(h, c, a, sp.trial, const_cast<double*>(sp.sums), nullptr, nullptr))) return rc;
+        if ((rc = align_evaluate(h, c, a, trial, sums, nullptr, nullptr))) return rc;
         hipEvent_t e1 = nullptr;
-        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-        sp.k = k, sp.last = k == iterations - 1;
-        hipLaunchKernelGGL(step, dim3((unsigned)((a.units + 255) / 256)), dim3(256), 0, st, sp);
-        HIPCHK(hipGetLastError());
+        if ((rc = profile_begin(h, c.stream, &e1)) || (rc = stage(k, k == iterations - 1))) return rc;
         if ((rc = profile_end(h, c.stream, e1, a.units, name))) return rc;
     }
     return 0;
+}
+
+// that loop with one kernel `step` over the units as its stage
+template <typename SP>
+static int solve_loop(msiren_handle h, const Call& c, const AlignPlan& a, SP& sp, int iterations, void (*step)(SP), const char* name) {
+    hipStream_t st = h->sc[c.stream].s;
+    return solve_loop_staged(h, c, a, sp.trial, const_cast<double*>(sp.sums), iterations, name, [&](int k, bool last) {
+        sp.k = k, sp.last = last;
+        hipLaunchKernelGGL(step, dim3((unsigned)((a.units + 255) / 256)), dim3(256), 0, st, sp);
+        HIPCHK(hipGetLastError());
+        return 0;
+    });
 }
 
 // align_solve_check: every refusal that needs no device pointer (the host-pointer form asks it before it stages anything)
@@ -637,20 +648,8 @@ int align_volume_solve_w(msiren_handle h, const Call& c, const float* images_dev
 }
 
 // ---- the grouped rigid solve (kernels: align_group.hip.h): align_volume_solve_w's loop with the step stage for groups of
-// consecutive targets under one rigid state per group.  Prologue, bins, trunk and the 80-sum reduce are the weighted volume family's.
-// the loop behind an init kernel with the step stage as a callable: evaluation k at the trial maps, then `stage(k, last)` as one profile entry `name`
-template <typename Stage>
-static int solve_loop_staged(msiren_handle h, const Call& c, const AlignPlan& a, const float* trial, double* sums, int iterations, const char* name, Stage stage) {
-    int rc;
-    for (int k = 0; k < iterations; ++k) {
-        if ((rc = align_evaluate(h, c, a, trial, sums, nullptr, nullptr))) return rc;
-        hipEvent_t e1 = nullptr;
-        if ((rc = profile_begin(h, c.stream, &e1)) || (rc = stage(k, k == iterations - 1))) return rc;
-        if ((rc = profile_end(h, c.stream, e1, a.units, name))) return rc;
-    }
-    return 0;
-}
-
+// consecutive targets under one rigid state per group.  Prologue, bins, trunk and the 80-sum reduce are the weighted volume family's; the loop is
+// solve_loop_staged with the four step kernels as its stage.
 // every refusal that needs no device pointer: what align_volume_solve_w_check refuses in rigid mode, then the groups (group_start is a host array)
 int align_volume_solve_group_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_group_opts* o,
                                    const int32_t* group_start, int64_t G, const void* planes, const void* rigid_in, const void* maps_out, const void* intensity_out,
