@@ -41,7 +41,8 @@ extern "C" {
  * read as a volume under 3 x 3 maps); msiren_align_volume_w(_dev), msiren_align_volume_solve_w(_dev) and msiren_align_volume_solve_w_opts (the same two
  * with a per-pixel weight and a per-target gain and bias); msiren_align_volume_solve_group(_dev) and msiren_align_volume_solve_group_opts (groups of
  * consecutive targets aligned to the volume under one shared rigid motion per group); msiren_align_volume_r(_dev) and
- * msiren_align_volume_solve_group_r(_dev) (the weighted volume cost and the grouped solve under a Geman-McClure loss with one scale per target).
+ * msiren_align_volume_solve_group_r(_dev) (the weighted volume cost and the grouped solve under a Geman-McClure loss with one scale per target);
+ * msiren_fuse_targets(_dev) and msiren_fuse_opts (aligned target slices gathered back onto the stack's voxel grid).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -815,6 +816,52 @@ MSIREN_API int msiren_align_volume_solve_group_r_dev(msiren_handle h, const floa
                                                      float* intensity_out_dev /* (m, 2) */, double* rigid_out_dev /* (G, 12) or NULL */,
                                                      double* report_dev /* (G, 7) */, double* target_report_dev /* (m, 3) or NULL */,
                                                      double* trace_dev /* (iterations, G, 15) or NULL */);
+
+/* Build-defined: the aligned targets put back onto the stack's voxel grid -- a motion-corrected (n, H, W) stack from what the
+ * volume alignment calls return.  No images, no trunk, no committed weights: a gather over the targets per output voxel.
+ *     targets (m, th, tw) float32, th, tw >= 2;  maps (m, 9) float32 = (z0, z1, tz, y0, y1, ty, x0, x1, tx), msiren_align_volume's convention (Z in
+ *     slice units, (Y, X) in pixels);  weights (m, th, tw) float32 or NULL (all 1);  intensity (m, 2) float32 = (g, b) or NULL ((1, 0)): T ~ g R + b
+ *     opts (HOST memory in both forms): spacing (pixels per slice), thickness (half-width of the through-plane window, in pixels), min_coverage
+ *     volume (n, H, W) float32;  coverage (n, H, W) float32 or NULL;  flags (m) int32 or NULL
+ * All arithmetic is fp64 + - * /, one rounding per operation, no fused multiply-add, in exactly these associations.  Per target q (float32 entries
+ * widened first):
+ *     a = (z0 spacing, y0, x0)    b = (z1 spacing, y1, x1)    t = (tz spacing, ty, tx)
+ *     G11 = ((a0 a0) + (a1 a1)) + (a2 a2)    G12 = ((a0 b0) + (a1 b1)) + (a2 b2)    G22 = ((b0 b0) + (b1 b1)) + (b2 b2)
+ *     det = (G11 G22) - (G12 G12)    tt = thickness thickness    dt = det tt
+ *     c = ((a1 b2) - (a2 b1), (a2 b0) - (a0 b2), (a0 b1) - (a1 b0))
+ *     flags: MSIREN_FUSE_DEGENERATE (1) a map entry not finite, or not (det > 0), or det not finite;  MSIREN_FUSE_BAD_INTENSITY (2) g or b not finite,
+ *     or g == 0.  A flagged target contributes nothing.
+ * Per output voxel (z, y, x), v = ((double)z spacing, y, x), num = den = 0.0, for q ascending:
+ *     p = v - t    pa = ((a0 p0) + (a1 p1)) + (a2 p2), pb with b, cp with c
+ *     i = ((G22 pa) - (G12 pb)) / det    j = ((G11 pb) - (G12 pa)) / det    k = 1.0 - ((cp cp) / dt)
+ *     q contributes iff flags == 0 and k > 0 and 0 <= i <= th - 1 and 0 <= j <= tw - 1 (a NaN fails every comparison)
+ *     i0 = min(floor i, th - 2), fi = i - i0;  j0, fj likewise;  sn = sd = 0.0;  taps (0,0), (0,1), (1,0), (1,1) in this order with
+ *     beta = (1 - fi) (1 - fj), (1 - fi) fj, fi (1 - fj), fi fj:  T = target[q, i0 + di, j0 + dj], w the weight there; the tap is valid iff T is finite and
+ *     w is finite and > 0;  valid: bw = beta w, sn += bw (((double)T - b) / g), sd += bw
+ *     num += k sn;  den += k sd
+ *     volume = (float)(num / den) if den > min_coverage, else NaN;  coverage = (float)den
+ * k is a quadratic (Welch) window in the distance to the target's plane: no square root, no exp, so mri_inr_amd/fuse.py: fuse_on_host (numpy) gives
+ * the same bits.  With thickness = spacing an unmoved target on an integer Z has k = 1 on its own slice and 0 on its neighbours.  m_targets = 0 is
+ * valid: every voxel NaN, every coverage 0.
+ * MSIREN_E_INVALID before any launch, naming the argument: opts->struct_size; spacing or thickness not finite or not > 0; min_coverage NaN or
+ * negative; th or tw < 2 with m > 0; n, height or width < 1; n height width or m th tw at or above 2^30; a null targets, maps, opts or volume with
+ * m > 0; a device pointer that is not 4-byte aligned.  The handle need not hold committed weights.
+ * Under msiren_profile_enable: one entry per call, "fuse_kernels" (the per-target set-up and the gather). */
+#define MSIREN_FUSE_DEGENERATE 1
+#define MSIREN_FUSE_BAD_INTENSITY 2
+typedef struct {
+    int32_t struct_size;      /* sizeof(msiren_fuse_opts) */
+    int32_t reserved;         /* 0 */
+    double spacing, thickness, min_coverage;
+} msiren_fuse_opts;
+MSIREN_API int msiren_fuse_targets(msiren_handle h, const float* targets_host, int64_t m_targets, int32_t th, int32_t tw, const float* maps_host /* (m, 9) */,
+                                   const float* weights_host /* (m, th, tw) or NULL */, const float* intensity_host /* (m, 2) or NULL */,
+                                   const msiren_fuse_opts* opts, int64_t n_slices, int32_t height, int32_t width, float* volume_host /* (n, H, W) */,
+                                   float* coverage_host /* (n, H, W) or NULL */, int32_t* flags_host /* (m) or NULL */);
+MSIREN_API int msiren_fuse_targets_dev(msiren_handle h, const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw, const float* maps_dev /* (m, 9) */,
+                                       const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */,
+                                       const msiren_fuse_opts* opts /* host */, int64_t n_slices, int32_t height, int32_t width,
+                                       float* volume_dev /* (n, H, W) */, float* coverage_dev /* (n, H, W) or NULL */, int32_t* flags_dev /* (m) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

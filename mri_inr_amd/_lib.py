@@ -128,6 +128,17 @@ class AlignVolumeSolveGroupOpts(C.Structure):
     ]
 
 
+class FuseOpts(C.Structure):
+    """msiren_fuse_opts"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("reserved", C.c_int32),
+        ("spacing", C.c_double),
+        ("thickness", C.c_double),
+        ("min_coverage", C.c_double),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -220,6 +231,8 @@ PROTOTYPES = {
                                                     _vp, _vp, _vp, _vp, _vp]),
     "msiren_align_volume_solve_group_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_fuse_targets": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp]),
+    "msiren_fuse_targets_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

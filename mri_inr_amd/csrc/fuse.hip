@@ -1,0 +1,81 @@
+// msiren_fuse_targets(_dev) (include/msiren.h): the aligned targets of the volume alignment calls gathered back onto the
+// stack's voxel grid.  Kernels: fuse.hip.h; what the call refuses, its tiling and its scratch: fuse_plan.h.  No images, no trunk: the handle need not
+// hold committed weights.
+#include "fuse.hip.h"
+#include "fuse_plan.h"
+#include "host_buffers.h"
+#include "host_ctx.h"
+
+using namespace mh;
+
+static_assert(msiren::kFuseTile == msiren::FUSE_TILE && msiren::kFuseRecord == msiren::FUSE_RECORD, "fuse_plan.h and the kernels disagree");
+static_assert(msiren::FUSE_DEGENERATE == MSIREN_FUSE_DEGENERATE && msiren::FUSE_BAD_INTENSITY == MSIREN_FUSE_BAD_INTENSITY, "the header and the kernels disagree");
+static_assert(sizeof(msiren_fuse_opts) == 32, "msiren_fuse_opts is 32 bytes");
+
+namespace {
+
+int fuse_refusal(const msiren::FuseArgs& a) {
+    char msg[256];
+    return msiren::fuse_check(a, msg, sizeof msg) ? 0 : fail(MSIREN_E_INVALID, "%s", msg);
+}
+
+// the two kernels on the call's stream, one profile entry; every pointer is the device's, `a` has passed fuse_check
+int fuse_on_stream(msiren_ctx* h, const Call& c, const msiren::FuseArgs& a) {
+    int rc;
+    auto& sc = h->sc[c.stream];
+    const msiren::FuseLayout lay = msiren::fuse_layout(a.m);
+    if (lay.total && (rc = ensure(h, sc.ragged, lay.total))) return rc;
+    double* const rec = a.m > 0 ? (double*)((char*)sc.ragged.p + lay.records) : nullptr;
+    const double spacing = a.opts ? a.opts->spacing : 1.0, thickness = a.opts ? a.opts->thickness : 1.0, min_coverage = a.opts ? a.opts->min_coverage : 0.0;
+    const int64_t voxels = a.n * a.H * a.W;
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+    if (a.m > 0) {
+        hipLaunchKernelGGL(msiren::fuse_setup_kernel, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, sc.s, (const float*)a.maps, (const float*)a.intensity, spacing,
+                           thickness, (int)a.m, rec, (int*)a.flags);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(msiren::fuse_gather_kernel, dim3((unsigned)msiren::fuse_tiles(a.n, a.H, a.W)), dim3(256), 0, sc.s, (const float*)a.targets, (const float*)a.weights,
+                       (const double*)rec, (int)a.m, a.th, a.tw, a.H, a.W, (int)msiren::fuse_tiles_x(a.W), (int)msiren::fuse_tiles_y(a.H), spacing, min_coverage,
+                       (float*)a.volume, (float*)a.coverage);
+    HIPCHK(hipGetLastError());
+    return profile_end(h, c.stream, e1, voxels, "fuse_kernels");
+}
+
+}  // namespace
+
+extern "C" {
+
+int msiren_fuse_targets_dev(msiren_handle h, const float* targets_dev, int64_t m, int32_t th, int32_t tw, const float* maps_dev, const float* weights_dev,
+                            const float* intensity_dev, const msiren_fuse_opts* opts, int64_t n, int32_t height, int32_t width, float* volume_dev, float* coverage_dev,
+                            int32_t* flags_dev) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    const msiren::FuseArgs a{targets_dev, m, th, tw, maps_dev, weights_dev, intensity_dev, opts, n, height, width, volume_dev, coverage_dev, flags_dev, true};
+    if ((rc = fuse_refusal(a))) return rc;  // (before the stream rotates)
+    if (!volume_dev && !coverage_dev) return 0;  // (m = 0 without an output)
+    return fuse_on_stream(h, dev_call(h), a);
+}
+
+int msiren_fuse_targets(msiren_handle h, const float* targets_host, int64_t m, int32_t th, int32_t tw, const float* maps_host, const float* weights_host,
+                        const float* intensity_host, const msiren_fuse_opts* opts, int64_t n, int32_t height, int32_t width, float* volume_host, float* coverage_host,
+                        int32_t* flags_host) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    const msiren::FuseArgs host{targets_host, m, th, tw, maps_host, weights_host, intensity_host, opts, n, height, width, volume_host, coverage_host, flags_host, false};
+    if ((rc = fuse_refusal(host))) return rc;
+    if (!volume_host && !coverage_host) return 0;
+    const Call c = make_call(h, true);
+    const size_t nt = (size_t)(m > 0 ? m * th * tw : 0) * sizeof(float), nv = (size_t)n * height * width * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)m * 9 * sizeof(float), HOST_COPY), i_w = io.in(weights_host, nt, HOST_COPY);
+    const int i_gb = io.in(intensity_host, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_v = io.out(volume_host, nv, HOST_IN_PLACE), o_c = io.out(coverage_host, nv, HOST_IN_PLACE), o_f = io.out(flags_host, (size_t)m * sizeof(int32_t), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    const msiren::FuseArgs dev{io.src<float>(i_t), m, th, tw, io.src<float>(i_m), io.src<float>(i_w), io.src<float>(i_gb), opts, n, height, width, io.dst<float>(o_v),
+                               io.dst<float>(o_c), io.dst<int32_t>(o_f), true};
+    if ((rc = fuse_on_stream(h, c, dev))) return rc;
+    return io.finish();
+}
+
+}  // extern "C"

@@ -24,6 +24,9 @@
 //                          The whole of these families lives here: checks, pipelines on the call's stream, host-pointer forms, entry points,
 //                          and the only inclusion of their six kernel headers
 //     align_plan.h         the scratch layouts and size limits of those calls: pure functions, no HIP (tests/test_align_plan.py)
+//     fuse.hip             msiren_fuse_targets*: the aligned targets of the volume alignment calls gathered back onto the stack's voxel grid
+//                          (kernels: fuse.hip.h); what it refuses, its tiling and scratch: fuse_plan.h, pure functions, no HIP
+//                          (tests/test_fuse_reference.py)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1297,6 +1297,46 @@ class ModulatedSiren:
                                                                tr.ctypes.data if trace else None))
         return ag.solve_result_g(out, gout, rout, report, trep, tr)
 
+    def fuse_targets(self, targets, maps, shape, spacing, *, thickness=None, weights=None, intensity=None, min_coverage=0.0, coverage=False):
+        """The aligned targets put back onto the stack's voxel grid -> ``fuse.FuseResult``: targets (m, th, tw), ``maps`` (m, 9) and ``intensity``
+        (m, 2) or None exactly the ``.maps`` and ``.intensity`` of any ``SolveResultV`` / ``VW`` / ``G``, ``shape`` = (n, H, W) the output grid,
+        ``spacing`` pixels per slice, ``thickness`` the half-width in pixels of the quadratic through-plane window (None: ``spacing``), ``weights``
+        (m, th, tw) or None (all 1; a weight that is zero, negative or not finite, and a pixel that is not finite, leave their tap out).  Every voxel
+        is the normalised sum of window x bilinear weight x pixel weight x (T - b) / g over the targets that reach it, NaN where that coverage is
+        not above ``min_coverage``; ``coverage``: return it too (build-defined; msiren_fuse_targets); bit for bit what
+        ``fuse.fuse_on_host`` gives.  The robust call's ``rweight`` may be multiplied into ``weights`` to keep rejected pixels out of the stack.  No
+        images and no weights of the model are involved: the result can go back into ``reconstruct`` / ``align_volume_*`` as ``images``."""
+        from . import fuse
+
+        def f32(x):
+            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+
+        self._ensure_handle()
+        t, mp = f32(targets), f32(maps)
+        if t.ndim != 3:
+            raise ValueError(f"expected targets (m, th, tw), got shape {t.shape}")
+        m, th, tw = t.shape
+        if mp.shape != (m, 9):
+            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
+        w = None if weights is None else f32(weights)
+        if w is not None and w.shape != t.shape:
+            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
+        gb = None if intensity is None else f32(intensity)
+        if gb is not None and gb.shape != (m, 2):
+            raise ValueError(f"expected intensity of shape ({m}, 2), got {gb.shape}")
+        if len(shape) != 3:
+            raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
+        n, Hh, Ww = (int(s) for s in shape)
+        o = _lib.FuseOpts(C.sizeof(_lib.FuseOpts), 0, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage))
+        ok = n > 0 and Hh > 0 and Ww > 0  # (the library refuses the others: nothing is allocated for them here)
+        vol = np.full((n, Hh, Ww) if ok else (0, 0, 0), np.nan, np.float32)
+        cov = np.zeros(vol.shape, np.float32) if coverage else None
+        flags = np.zeros(m, np.int32)
+        _lib.check(self._lib.msiren_fuse_targets(self._h, t.ctypes.data if m else None, m, th, tw, mp.ctypes.data if m else None, None if w is None or not m else w.ctypes.data,
+                                                 None if gb is None or not m else gb.ctypes.data, C.byref(o), n, Hh, Ww, vol.ctypes.data, cov.ctypes.data if coverage else None,
+                                                 flags.ctypes.data if m else None))
+        return fuse.FuseResult(vol, cov, flags)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
