@@ -42,7 +42,8 @@ extern "C" {
  * with a per-pixel weight and a per-target gain and bias); msiren_align_volume_solve_group(_dev) and msiren_align_volume_solve_group_opts (groups of
  * consecutive targets aligned to the volume under one shared rigid motion per group); msiren_align_volume_r(_dev) and
  * msiren_align_volume_solve_group_r(_dev) (the weighted volume cost and the grouped solve under a Geman-McClure loss with one scale per target);
- * msiren_fuse_targets(_dev) and msiren_fuse_opts (aligned target slices gathered back onto the stack's voxel grid).
+ * msiren_fuse_targets(_dev) and msiren_fuse_opts (aligned target slices gathered back onto the stack's voxel grid); msiren_project_volume(_dev) (the
+ * way back: a stack gathered onto the targets' lattices with the same weights, with the residual against given targets and four sums per target).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -862,6 +863,43 @@ MSIREN_API int msiren_fuse_targets_dev(msiren_handle h, const float* targets_dev
                                        const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */,
                                        const msiren_fuse_opts* opts /* host */, int64_t n_slices, int32_t height, int32_t width,
                                        float* volume_dev /* (n, H, W) */, float* coverage_dev /* (n, H, W) or NULL */, int32_t* flags_dev /* (m) or NULL */);
+
+/* Build-defined: the way back from msiren_fuse_targets -- a stack gathered onto the lattices of m targets under the same maps,
+ * with exactly the weights of the fusion: what each target should look like, given the stack.  The forward operator of slice-to-volume
+ * reconstruction (msiren_fuse_targets is its normalised adjoint).  No images, no trunk, no committed weights.
+ *     volume (n, H, W) float32;  maps (m, 9), intensity (m, 2) or NULL, opts (HOST memory in both forms): msiren_fuse_targets' arguments
+ *     targets (m, th, tw) float32 or NULL;  weights (m, th, tw) float32 or NULL (all 1), only with targets
+ *     simulated (m, th, tw) float32;  coverage (m, th, tw) float32 or NULL;  residual (m, th, tw) float32 or NULL and stats (m, 4) float64 or NULL,
+ *     only with targets;  flags (m) int32 or NULL
+ * All arithmetic is fp64 + - * /, one rounding per operation, no fused multiply-add.  The per-target record a, b, t, G11, G12, G22, det, dt, c, g, b,
+ * flags is msiren_fuse_targets', unchanged.  For target q and voxel v = ((double)z spacing, y, x) the quantities p, pa, pb, cp, i, j, k, the contribution
+ * test (flags == 0, k > 0, 0 <= i <= th - 1, 0 <= j <= tw - 1), i0, j0, fi, fj and the four beta are msiren_fuse_targets' expressions, character for
+ * character: the two calls see the same bits.  A voxel is VALID iff volume[z, y, x] is finite.
+ * Per target pixel (q, pi, pj): num = den = 0.0; over the voxels in ascending flat index (z, then y, then x), for each valid voxel that contributes to
+ * q and has (pi, pj) among its four taps (i0 + di, j0 + dj) (distinct pixels: a voxel adds at most one term to a pixel):
+ *     kb = k beta_tap        num += kb (double)V        den += kb
+ *     coverage = (float)den        simulated = (float)((g (num / den)) + b) if den > min_coverage, else NaN             (T ~ g R + b)
+ * A flagged target has simulated NaN and coverage 0 everywhere.  A volume that is NaN everywhere and m_targets = 0 are valid.
+ * With targets:
+ *     residual = (float)((double)T - (double)simulated), NaN where either is not finite;  a pixel COUNTS iff residual is finite and w is finite and > 0
+ *     stats[q] = (count, sum w, sum w r, sum (w r) r) over the pixels that count, r the float32 residual widened, in this order: per column j the sum
+ *     over the rows i ascending starting from 0.0, then the column sums added for j ascending starting from 0.0
+ * mri_inr_amd/fuse.py: project_on_host and project_stats_on_host (numpy) give the same bits.
+ * MSIREN_E_INVALID before any launch, naming the argument: everything msiren_fuse_targets refuses of opts, th, tw, n, height, width and the two
+ * products; a null volume, maps, opts or simulated with m > 0; weights, residual or stats without targets; a device pointer that is not 4-byte
+ * aligned, a device stats that is not 8-byte aligned.  Under msiren_profile_enable: one entry per call, "project_kernels". */
+MSIREN_API int msiren_project_volume(msiren_handle h, const float* volume_host /* (n, H, W) */, int64_t n_slices, int32_t height, int32_t width,
+                                     const float* maps_host /* (m, 9) */, const float* intensity_host /* (m, 2) or NULL */, const msiren_fuse_opts* opts,
+                                     int64_t m_targets, int32_t th, int32_t tw, const float* targets_host /* (m, th, tw) or NULL */,
+                                     const float* weights_host /* (m, th, tw) or NULL */, float* simulated_host /* (m, th, tw) */,
+                                     float* coverage_host /* (m, th, tw) or NULL */, float* residual_host /* (m, th, tw) or NULL */,
+                                     double* stats_host /* (m, 4) or NULL */, int32_t* flags_host /* (m) or NULL */);
+MSIREN_API int msiren_project_volume_dev(msiren_handle h, const float* volume_dev /* (n, H, W) */, int64_t n_slices, int32_t height, int32_t width,
+                                         const float* maps_dev /* (m, 9) */, const float* intensity_dev /* (m, 2) or NULL */, const msiren_fuse_opts* opts /* host */,
+                                         int64_t m_targets, int32_t th, int32_t tw, const float* targets_dev /* (m, th, tw) or NULL */,
+                                         const float* weights_dev /* (m, th, tw) or NULL */, float* simulated_dev /* (m, th, tw) */,
+                                         float* coverage_dev /* (m, th, tw) or NULL */, float* residual_dev /* (m, th, tw) or NULL */,
+                                         double* stats_dev /* (m, 4) or NULL */, int32_t* flags_dev /* (m) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

@@ -1,8 +1,12 @@
 // msiren_fuse_targets(_dev) (include/msiren.h): the aligned targets of the volume alignment calls gathered back onto the
 // stack's voxel grid.  Kernels: fuse.hip.h; what the call refuses, its tiling and its scratch: fuse_plan.h.  No images, no trunk: the handle need not
 // hold committed weights.
+// msiren_project_volume(_dev): the way back, the stack gathered onto the targets' lattices with the same weights.  Kernels:
+// project.hip.h (fuse_setup_kernel is shared: this is the one unit that includes fuse.hip.h); refusals, tiling, scratch and the box: project_plan.h.
 #include "fuse.hip.h"
 #include "fuse_plan.h"
+#include "project.hip.h"
+#include "project_plan.h"
 #include "host_buffers.h"
 #include "host_ctx.h"
 
@@ -11,6 +15,7 @@ using namespace mh;
 static_assert(msiren::kFuseTile == msiren::FUSE_TILE && msiren::kFuseRecord == msiren::FUSE_RECORD, "fuse_plan.h and the kernels disagree");
 static_assert(msiren::FUSE_DEGENERATE == MSIREN_FUSE_DEGENERATE && msiren::FUSE_BAD_INTENSITY == MSIREN_FUSE_BAD_INTENSITY, "the header and the kernels disagree");
 static_assert(sizeof(msiren_fuse_opts) == 32, "msiren_fuse_opts is 32 bytes");
+static_assert(msiren::kProjectTile == msiren::PROJECT_TILE && msiren::kProjectSums == 4, "project_plan.h and the kernels disagree");
 
 namespace {
 
@@ -42,9 +47,75 @@ int fuse_on_stream(msiren_ctx* h, const Call& c, const msiren::FuseArgs& a) {
     return profile_end(h, c.stream, e1, voxels, "fuse_kernels");
 }
 
+int project_refusal(const msiren::ProjectArgs& a) {
+    char msg[256];
+    return msiren::project_check(a, msg, sizeof msg) ? 0 : fail(MSIREN_E_INVALID, "%s", msg);
+}
+
+// set-up, gather and (with targets) the residual and the sums on the call's stream, one profile entry; every pointer is the device's, `a` has passed
+// project_check and a.m > 0
+int project_on_stream(msiren_ctx* h, const Call& c, const msiren::ProjectArgs& a) {
+    int rc;
+    auto& sc = h->sc[c.stream];
+    const msiren::ProjectLayout lay = msiren::project_layout(a.m, a.tw, a.stats != nullptr);
+    if ((rc = ensure(h, sc.ragged, lay.total))) return rc;
+    double* const rec = (double*)((char*)sc.ragged.p + lay.records);
+    double* const columns = a.stats ? (double*)((char*)sc.ragged.p + lay.columns) : nullptr;
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+    hipLaunchKernelGGL(msiren::fuse_setup_kernel, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, sc.s, (const float*)a.maps, (const float*)a.intensity, a.opts->spacing,
+                       a.opts->thickness, (int)a.m, rec, (int*)a.flags);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(msiren::project_gather_kernel, dim3((unsigned)msiren::project_tiles(a.m, a.th, a.tw)), dim3(256), 0, sc.s, (const float*)a.volume, (const double*)rec,
+                       a.th, a.tw, (int)a.n, a.H, a.W, (int)msiren::project_tiles_x(a.tw), (int)msiren::project_tiles_y(a.th), a.opts->spacing, a.opts->thickness,
+                       a.opts->min_coverage, (float*)a.simulated, (float*)a.coverage);
+    HIPCHK(hipGetLastError());
+    if (a.targets && (a.residual || a.stats)) {
+        hipLaunchKernelGGL(msiren::project_stats_kernel, dim3((unsigned)a.m), dim3(256), 0, sc.s, (const float*)a.targets, (const float*)a.weights, (const float*)a.simulated,
+                           a.th, a.tw, columns, (float*)a.residual, (double*)a.stats);
+        HIPCHK(hipGetLastError());
+    }
+    return profile_end(h, c.stream, e1, a.m * a.th * a.tw, "project_kernels");
+}
+
 }  // namespace
 
 extern "C" {
+
+int msiren_project_volume_dev(msiren_handle h, const float* volume_dev, int64_t n, int32_t height, int32_t width, const float* maps_dev, const float* intensity_dev,
+                              const msiren_fuse_opts* opts, int64_t m, int32_t th, int32_t tw, const float* targets_dev, const float* weights_dev, float* simulated_dev,
+                              float* coverage_dev, float* residual_dev, double* stats_dev, int32_t* flags_dev) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    const msiren::ProjectArgs a{volume_dev, n, height, width, maps_dev, intensity_dev, opts, m, th, tw, targets_dev, weights_dev, simulated_dev, coverage_dev, residual_dev,
+                                stats_dev, flags_dev, true};
+    if ((rc = project_refusal(a))) return rc;  // (before the stream rotates)
+    if (m == 0) return 0;                      // (no pixel: nothing to write)
+    return project_on_stream(h, dev_call(h), a);
+}
+
+int msiren_project_volume(msiren_handle h, const float* volume_host, int64_t n, int32_t height, int32_t width, const float* maps_host, const float* intensity_host,
+                          const msiren_fuse_opts* opts, int64_t m, int32_t th, int32_t tw, const float* targets_host, const float* weights_host, float* simulated_host,
+                          float* coverage_host, float* residual_host, double* stats_host, int32_t* flags_host) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    const msiren::ProjectArgs host{volume_host, n, height, width, maps_host, intensity_host, opts, m, th, tw, targets_host, weights_host, simulated_host, coverage_host,
+                                   residual_host, stats_host, flags_host, false};
+    if ((rc = project_refusal(host))) return rc;
+    if (m == 0) return 0;
+    const Call c = make_call(h, true);
+    const size_t nt = (size_t)m * th * tw * sizeof(float), nv = (size_t)n * height * width * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_v = io.in(volume_host, nv, HOST_COPY), i_m = io.in(maps_host, (size_t)m * 9 * sizeof(float), HOST_COPY);
+    const int i_gb = io.in(intensity_host, (size_t)m * 2 * sizeof(float), HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY), i_w = io.in(weights_host, nt, HOST_COPY);
+    const int o_s = io.out(simulated_host, nt, HOST_COPY), o_c = io.out(coverage_host, nt, HOST_IN_PLACE), o_r = io.out(residual_host, nt, HOST_IN_PLACE);
+    const int o_st = io.out(stats_host, (size_t)m * 4 * sizeof(double), HOST_COPY), o_f = io.out(flags_host, (size_t)m * sizeof(int32_t), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    const msiren::ProjectArgs dev{io.src<float>(i_v), n, height, width, io.src<float>(i_m), io.src<float>(i_gb), opts, m, th, tw, io.src<float>(i_t), io.src<float>(i_w),
+                                  io.dst<float>(o_s), io.dst<float>(o_c), io.dst<float>(o_r), io.dst<double>(o_st), io.dst<int32_t>(o_f), true};
+    if ((rc = project_on_stream(h, c, dev))) return rc;
+    return io.finish();
+}
 
 int msiren_fuse_targets_dev(msiren_handle h, const float* targets_dev, int64_t m, int32_t th, int32_t tw, const float* maps_dev, const float* weights_dev,
                             const float* intensity_dev, const msiren_fuse_opts* opts, int64_t n, int32_t height, int32_t width, float* volume_dev, float* coverage_dev,

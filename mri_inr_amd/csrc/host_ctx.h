@@ -27,6 +27,8 @@
 //     fuse.hip             msiren_fuse_targets*: the aligned targets of the volume alignment calls gathered back onto the stack's voxel grid
 //                          (kernels: fuse.hip.h); what it refuses, its tiling and scratch: fuse_plan.h, pure functions, no HIP
 //                          (tests/test_fuse_reference.py)
+//                          and msiren_project_volume*: the way back, a stack gathered onto the targets' lattices (kernels: project.hip.h; refusals,
+//                          tiling, scratch and the box of voxels per pixel: project_plan.h, tests/test_project_reference.py)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1337,6 +1337,56 @@ class ModulatedSiren:
                                                  flags.ctypes.data if m else None))
         return fuse.FuseResult(vol, cov, flags)
 
+    def project_volume(self, volume, maps, shape, spacing, *, thickness=None, intensity=None, min_coverage=0.0, targets=None, weights=None, coverage=False,
+                       residual=False, stats=False):
+        """The way back from ``fuse_targets`` -> ``fuse.ProjectResult``: the stack ``volume`` (n, H, W) gathered onto the lattices ``shape`` = (th, tw)
+        of the m targets of ``maps`` (m, 9), with exactly the weights of the fusion (``spacing``, ``thickness``, ``intensity``, ``min_coverage`` as
+        there): ``simulated`` is what each target should look like given the stack, g R + b of the normalised sum, NaN where the ``coverage`` (returned
+        on request) is not above ``min_coverage``.  With ``targets`` (m, th, tw) and ``weights`` (m, th, tw) or None (all 1): ``residual`` = targets -
+        simulated and ``stats`` (m, 4) = (count, sum w, sum w r, sum (w r) r) per target, on request (build-defined, DESIGN.md section 5.18;
+        msiren_project_volume); bit for bit what ``fuse.project_on_host`` and ``fuse.project_stats_on_host`` give.  No images and no weights of the
+        model are involved."""
+        from . import fuse
+
+        def f32(x):
+            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+
+        self._ensure_handle()
+        vol, mp = f32(volume), f32(maps)
+        if vol.ndim != 3:
+            raise ValueError(f"expected volume (n, H, W), got shape {vol.shape}")
+        if mp.ndim != 2 or mp.shape[1] != 9:
+            raise ValueError(f"expected maps of shape (m, 9), got {mp.shape}")
+        if len(shape) != 2:
+            raise ValueError(f"expected shape = (th, tw), got {shape!r}")
+        m, (th, tw) = len(mp), (int(s) for s in shape)
+        gb = None if intensity is None else f32(intensity)
+        if gb is not None and gb.shape != (m, 2):
+            raise ValueError(f"expected intensity of shape ({m}, 2), got {gb.shape}")
+        t = None if targets is None else f32(targets)
+        if t is None and (weights is not None or residual or stats):
+            raise ValueError("weights, residual and stats need targets")
+        if t is not None and t.shape != (m, th, tw):
+            raise ValueError(f"expected targets of shape {(m, th, tw)}, got {t.shape}")
+        w = None if weights is None else f32(weights)
+        if w is not None and w.shape != (m, th, tw):
+            raise ValueError(f"expected weights of shape {(m, th, tw)}, got {w.shape}")
+        n, Hh, Ww = vol.shape
+        o = _lib.FuseOpts(C.sizeof(_lib.FuseOpts), 0, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage))
+        ok = th > 0 and tw > 0  # (the library refuses the others: nothing is allocated for them here)
+        sim = np.full((m, th, tw) if ok else (m, 0, 0), np.nan, np.float32)
+        cov = np.zeros(sim.shape, np.float32) if coverage else None
+        res = np.full(sim.shape, np.nan, np.float32) if residual else None
+        st = np.zeros((m, 4), np.float64) if stats else None
+        flags = np.zeros(m, np.int32)
+
+        def ptr(x):
+            return x.ctypes.data if x is not None and m else None
+
+        _lib.check(self._lib.msiren_project_volume(self._h, vol.ctypes.data if vol.size else None, n, Hh, Ww, ptr(mp), ptr(gb), C.byref(o), m, th, tw, ptr(t), ptr(w), ptr(sim),
+                                                   ptr(cov), ptr(res), ptr(st), ptr(flags)))
+        return fuse.ProjectResult(sim, cov, res, st, flags)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
