@@ -43,7 +43,8 @@ extern "C" {
  * consecutive targets aligned to the volume under one shared rigid motion per group); msiren_align_volume_r(_dev) and
  * msiren_align_volume_solve_group_r(_dev) (the weighted volume cost and the grouped solve under a Geman-McClure loss with one scale per target);
  * msiren_fuse_targets(_dev) and msiren_fuse_opts (aligned target slices gathered back onto the stack's voxel grid); msiren_project_volume(_dev) (the
- * way back: a stack gathered onto the targets' lattices with the same weights, with the residual against given targets and four sums per target).
+ * way back: a stack gathered onto the targets' lattices with the same weights, with the residual against given targets and four sums per target);
+ * msiren_solve_volume(_dev) and msiren_solve_opts (the stack that best explains all targets: regularised conjugate gradients on those two operators).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -900,6 +901,57 @@ MSIREN_API int msiren_project_volume_dev(msiren_handle h, const float* volume_de
                                          const float* weights_dev /* (m, th, tw) or NULL */, float* simulated_dev /* (m, th, tw) */,
                                          float* coverage_dev /* (m, th, tw) or NULL */, float* residual_dev /* (m, th, tw) or NULL */,
                                          double* stats_dev /* (m, 4) or NULL */, int32_t* flags_dev /* (m) or NULL */);
+
+/* Build-defined: the stack that best explains all targets at once -- `iterations` steps of conjugate gradients, in one device
+ * call without a host synchronisation inside the loop, on the weighted, regularised least-squares problem
+ *     F(x) = 1/2 sum over the active pixels of ((w g) g) (tau - (P x))^2  +  1/2 lambda sum over the edges of c_e (x_u - x_v)^2
+ * i.e. on the normal equations (Pt Omega P + lambda L) x = Pt Omega tau, with P msiren_project_volume's row-normalised gather, tau = ((double)T - b) / g
+ * and the edges the 6-neighbour pairs with both ends in the support, c = 1 in plane and c = 1.0 / (spacing spacing) through plane.  No images, no
+ * trunk, no committed weights.
+ *     targets, m, th, tw, maps, weights, intensity, n, height, width: msiren_fuse_targets' arguments;  opts (HOST memory in both forms)
+ *     start (n, H, W) float32 or NULL: the first iterate; NULL: msiren_fuse_targets' volume of the same arguments (fuse_gather_kernel's bits, widened)
+ *     volume (n, H, W) float32;  coverage (n, H, W) float32 or NULL: msiren_fuse_targets' coverage;  history (iterations + 1, 2) float64 or NULL;
+ *     flags (m) int32 or NULL;  stopped_at (1) int32 or NULL
+ * All arithmetic is fp64 + - * /, one rounding per operation, no fused multiply-add.  Records, flags, p, pa, pb, cp, i, j, k, the contribution test, i0,
+ * j0, fi, fj and the four beta are msiren_fuse_targets' expressions, character for character.
+ *   The SUPPORT S is the set of voxels where the start is finite; x_0 = (double)start there.  Every vector below is 0.0 outside S.
+ *   D[q, pi, pj] = msiren_project_volume's den with "valid" read as "in S".  A pixel is ACTIVE iff its target is unflagged, T is finite, w is finite and
+ *   > 0, and D > min_coverage.  Wt = ((double)w g) g.  D and the active pixels are computed once.
+ *   FORWARD u = P v: num as msiren_project_volume's with the fp64 entry of v in place of (double)V, over S, in that order; u = num / D on the active
+ *   pixels, 0.0 elsewhere.
+ *   TRANSPOSE Pt y: per voxel of S, acc = 0.0, for q ascending under the contribution test: sn = 0.0; for the four taps in tap order, if the tap's
+ *   pixel is active: sn += beta (y_p / D_p);  acc += k sn.
+ *   LAPLACIAN (L v)_u: s = 0.0; for the neighbours u' = z-, z+, y-, y+, x-, x+ in this order that are in the grid and in S: s += c (v_u - v_u').
+ *   A v = (Pt (Wt (P v))) + (lambda (L v)).
+ *   INNER PRODUCT <a, b>: the products a b on S, 0.0 elsewhere; per slice per column the sum down the rows from 0.0, then the columns ascending from
+ *   0.0; then the slices ascending from 0.0.
+ *   r = (Pt (Wt tau)) - (A x_0), p = r, rho = <r, r>.  Iteration k = 0 .. iterations - 1: q = A p, gamma = <p, q>.  If the solve has stopped, or
+ *   rho == 0, or gamma is not finite, or not gamma > 0: the solve stops (stopped_at = k the first time) and x, r, p, rho stay.  Else alpha = rho / gamma,
+ *   x = x + (alpha p), r = r - (alpha q), rho' = <r, r>, p = r + ((rho' / rho) p), rho = rho'.
+ *   volume = (float)x on S, NaN elsewhere.  history[k] = (rho_k, gamma_k), gamma NaN in the last row and from the stop on.  stopped_at = -1 if the
+ *   solve never stopped.  iterations = 0 with start NULL returns msiren_fuse_targets' bits.
+ * mri_inr_amd/solve_volume.py: solve_volume_on_host (numpy) gives the same bits.  m_targets = 0 is valid: with start NULL the support is empty, every
+ * voxel NaN and, with iterations > 0, stopped_at = 0.
+ * MSIREN_E_INVALID before any launch, naming the argument: a null opts or volume; opts->struct_size; everything msiren_fuse_targets refuses;
+ * iterations < 0 or > 1024; lambda NaN, negative or infinite; a device pointer that is not 4-byte aligned, a device history that is not 8-byte
+ * aligned.  Under msiren_profile_enable: one entry per call, "solve_volume_kernels". */
+typedef struct {
+    int32_t struct_size;      /* sizeof(msiren_solve_opts) */
+    int32_t iterations;       /* 0 .. 1024 */
+    double spacing, thickness, min_coverage, lambda;
+} msiren_solve_opts;
+MSIREN_API int msiren_solve_volume(msiren_handle h, const float* targets_host, int64_t m_targets, int32_t th, int32_t tw, const float* maps_host /* (m, 9) */,
+                                   const float* weights_host /* (m, th, tw) or NULL */, const float* intensity_host /* (m, 2) or NULL */,
+                                   const msiren_solve_opts* opts, int64_t n_slices, int32_t height, int32_t width, const float* start_host /* (n, H, W) or NULL */,
+                                   float* volume_host /* (n, H, W) */, float* coverage_host /* (n, H, W) or NULL */,
+                                   double* history_host /* (iterations + 1, 2) or NULL */, int32_t* flags_host /* (m) or NULL */,
+                                   int32_t* stopped_at_host /* (1) or NULL */);
+MSIREN_API int msiren_solve_volume_dev(msiren_handle h, const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw, const float* maps_dev /* (m, 9) */,
+                                       const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */,
+                                       const msiren_solve_opts* opts /* host */, int64_t n_slices, int32_t height, int32_t width,
+                                       const float* start_dev /* (n, H, W) or NULL */, float* volume_dev /* (n, H, W) */, float* coverage_dev /* (n, H, W) or NULL */,
+                                       double* history_dev /* (iterations + 1, 2) or NULL */, int32_t* flags_dev /* (m) or NULL */,
+                                       int32_t* stopped_at_dev /* (1) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

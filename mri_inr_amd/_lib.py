@@ -139,6 +139,18 @@ class FuseOpts(C.Structure):
     ]
 
 
+class SolveOpts(C.Structure):
+    """msiren_solve_opts"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("iterations", C.c_int32),
+        ("spacing", C.c_double),
+        ("thickness", C.c_double),
+        ("min_coverage", C.c_double),
+        ("lam", C.c_double),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -235,6 +247,8 @@ PROTOTYPES = {
     "msiren_fuse_targets_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp]),
     "msiren_project_volume": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_project_volume_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_solve_volume": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(SolveOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_solve_volume_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(SolveOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

@@ -1387,6 +1387,56 @@ class ModulatedSiren:
                                                    ptr(cov), ptr(res), ptr(st), ptr(flags)))
         return fuse.ProjectResult(sim, cov, res, st, flags)
 
+    def solve_volume(self, targets, maps, shape, spacing, *, iterations, lam=0.0, thickness=None, weights=None, intensity=None, min_coverage=0.0, start=None,
+                     coverage=False, history=False):
+        """The stack that best explains all aligned targets at once -> ``solve_volume.SolveVolumeResult``: ``iterations`` steps of conjugate gradients,
+        in one device call, on 1/2 sum w g g (tau - P x)^2 + 1/2 ``lam`` sum over the 6-neighbour edges of c (x_u - x_v)^2, with P ``project_volume``'s
+        row-normalised gather, tau = (T - b) / g, and c = 1 in plane, 1 / spacing^2 through plane.  targets, maps, shape = (n, H, W), spacing,
+        thickness, weights, intensity and min_coverage as in ``fuse_targets``; ``start`` (n, H, W) or None: the fusion.  The support is the finite
+        voxels of the start; the volume is NaN elsewhere.  ``coverage``: the fusion's coverage too; ``history``: (iterations + 1, 2) = (<r, r>,
+        <p, A p>) per iteration too.  ``stopped_at``: the iteration at which the solve broke down (rho == 0, or gamma not finite or not > 0), else -1.
+        Build-defined (msiren_solve_volume); bit for bit what ``solve_volume.solve_volume_on_host`` gives.  No images and no
+        weights of the model are involved."""
+        from . import solve_volume as sv
+
+        def f32(x):
+            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+
+        self._ensure_handle()
+        t, mp = f32(targets), f32(maps)
+        if t.ndim != 3:
+            raise ValueError(f"expected targets (m, th, tw), got shape {t.shape}")
+        m, th, tw = t.shape
+        if mp.shape != (m, 9):
+            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
+        w = None if weights is None else f32(weights)
+        if w is not None and w.shape != t.shape:
+            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
+        gb = None if intensity is None else f32(intensity)
+        if gb is not None and gb.shape != (m, 2):
+            raise ValueError(f"expected intensity of shape ({m}, 2), got {gb.shape}")
+        if len(shape) != 3:
+            raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
+        n, Hh, Ww = (int(s) for s in shape)
+        st = None if start is None else f32(start)
+        if st is not None and st.shape != (n, Hh, Ww):
+            raise ValueError(f"expected start of shape {(n, Hh, Ww)}, got {st.shape}")
+        iterations = int(iterations)
+        o = _lib.SolveOpts(C.sizeof(_lib.SolveOpts), iterations, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage), float(lam))
+        ok = n > 0 and Hh > 0 and Ww > 0  # (the library refuses the others: nothing is allocated for them here)
+        vol = np.full((n, Hh, Ww) if ok else (0, 0, 0), np.nan, np.float32)
+        cov = np.zeros(vol.shape, np.float32) if coverage else None
+        hist = np.full((max(iterations, 0) + 1, 2), np.nan, np.float64) if history else None
+        flags = np.zeros(m, np.int32)
+        stopped = np.full(1, -1, np.int32)
+
+        def ptr(x):
+            return x.ctypes.data if x is not None and m else None
+
+        _lib.check(self._lib.msiren_solve_volume(self._h, ptr(t), m, th, tw, ptr(mp), ptr(w), ptr(gb), C.byref(o), n, Hh, Ww, st.ctypes.data if st is not None and st.size else None,
+                                                 vol.ctypes.data, cov.ctypes.data if coverage else None, hist.ctypes.data if history else None, ptr(flags), stopped.ctypes.data))
+        return sv.SolveVolumeResult(vol, cov, hist, flags, int(stopped[0]))
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
