@@ -2,32 +2,58 @@
 // stack's voxel grid.  Kernels: fuse.hip.h; what the call refuses, its tiling and its scratch: fuse_plan.h.  No images, no trunk: the handle need not
 // hold committed weights.
 // msiren_project_volume(_dev): the way back, the stack gathered onto the targets' lattices with the same weights.  Kernels:
-// project.hip.h (fuse_setup_kernel is shared: this is the one unit that includes fuse.hip.h); refusals, tiling, scratch and the box: project_plan.h.
+// project.hip.h; refusals, scratch and the box: project_plan.h.
 // msiren_solve_volume(_dev): conjugate gradients on those two operators, the stack that best explains all targets.  Kernels:
-// solve_volume.hip.h (fuse_setup_kernel and fuse_gather_kernel are reused as they are); refusals, scratch and the launch plan: solve_volume_plan.h.
-#include "fuse.hip.h"
-#include "fuse_plan.h"
-#include "project.hip.h"
-#include "project_plan.h"
-#include "solve_volume.hip.h"
-#include "solve_volume_plan.h"
+// solve_volume.hip.h; refusals, scratch and the launch plan: solve_volume_plan.h.
+// The three calls share the record of fuse_setup_kernel, the tiling and the two loops (fuse_visit_targets, project_visit_voxels), and on this side
+// the refusal, the checked launch and the launches of the set-up and of the fusion below.
+#include "solve_volume.hip.h"  // (and through it project.hip.h, fuse.hip.h and the three plans)
 #include "host_buffers.h"
 #include "host_ctx.h"
 
 using namespace mh;
 
-static_assert(msiren::kFuseTile == msiren::FUSE_TILE && msiren::kFuseRecord == msiren::FUSE_RECORD, "fuse_plan.h and the kernels disagree");
-static_assert(msiren::FUSE_DEGENERATE == MSIREN_FUSE_DEGENERATE && msiren::FUSE_BAD_INTENSITY == MSIREN_FUSE_BAD_INTENSITY, "the header and the kernels disagree");
 static_assert(sizeof(msiren_fuse_opts) == 32, "msiren_fuse_opts is 32 bytes");
-static_assert(msiren::kProjectTile == msiren::PROJECT_TILE && msiren::kProjectSums == 4, "project_plan.h and the kernels disagree");
+static_assert(msiren::kProjectSums == 4, "project_stats_kernel parks four sums per column");
 static_assert(sizeof(msiren_solve_opts) == 40, "msiren_solve_opts is 40 bytes");
-static_assert(msiren::SOLVE_TILE == msiren::kFuseTile && msiren::SOLVE_TILE == msiren::kProjectTile, "the solve's gathers use the tilings of fuse_plan.h and project_plan.h");
 
 namespace {
 
-int fuse_refusal(const msiren::FuseArgs& a) {
+// 0, or MSIREN_E_INVALID with the words of `check` (fuse_check, project_check, solve_check)
+template <class Args>
+int refusal(bool (*check)(const Args&, char*, size_t), const Args& a) {
     char msg[256];
-    return msiren::fuse_check(a, msg, sizeof msg) ? 0 : fail(MSIREN_E_INVALID, "%s", msg);
+    return check(a, msg, sizeof msg) ? 0 : fail(MSIREN_E_INVALID, "%s", msg);
+}
+
+// Kernels onto one stream in workgroups of 256, every launch checked: after one that failed nothing more is launched and `rc` is its code
+struct Launcher {
+    hipStream_t s;
+    int rc = 0;
+    template <class... P, class... A>
+    void operator()(void (*kernel)(P...), dim3 grid, A... args) {
+        if (!rc) rc = launch(kernel, grid, args...);
+    }
+
+private:
+    template <class... P, class... A>
+    int launch(void (*kernel)(P...), dim3 grid, A... args) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+};
+
+// the records of m > 0 targets into `rec`, [flags]
+void launch_setup(Launcher& go, const void* maps, const void* intensity, double spacing, double thickness, int64_t m, double* rec, const void* flags) {
+    if (m > 0) go(msiren::fuse_setup_kernel, dim3((unsigned)((m + 255) / 256)), (const float*)maps, (const float*)intensity, spacing, thickness, (int)m, rec, (int*)flags);
+}
+
+// msiren_fuse_targets' gather: [volume], [coverage] (n, H, W)
+void launch_fusion(Launcher& go, const void* targets, const void* weights, const double* rec, int64_t m, int32_t th, int32_t tw, int64_t n, int32_t H, int32_t W,
+                   double spacing, double min_coverage, float* volume, float* coverage) {
+    go(msiren::fuse_gather_kernel, dim3((unsigned)msiren::fuse_tiles(n, H, W)), (const float*)targets, (const float*)weights, rec, (int)m, th, tw, H, W,
+       (int)msiren::fuse_tiles_x(W), (int)msiren::fuse_tiles_y(H), spacing, min_coverage, volume, coverage);
 }
 
 // the two kernels on the call's stream, one profile entry; every pointer is the device's, `a` has passed fuse_check
@@ -38,24 +64,12 @@ int fuse_on_stream(msiren_ctx* h, const Call& c, const msiren::FuseArgs& a) {
     if (lay.total && (rc = ensure(h, sc.ragged, lay.total))) return rc;
     double* const rec = a.m > 0 ? (double*)((char*)sc.ragged.p + lay.records) : nullptr;
     const double spacing = a.opts ? a.opts->spacing : 1.0, thickness = a.opts ? a.opts->thickness : 1.0, min_coverage = a.opts ? a.opts->min_coverage : 0.0;
-    const int64_t voxels = a.n * a.H * a.W;
     hipEvent_t e1 = nullptr;
     if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-    if (a.m > 0) {
-        hipLaunchKernelGGL(msiren::fuse_setup_kernel, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, sc.s, (const float*)a.maps, (const float*)a.intensity, spacing,
-                           thickness, (int)a.m, rec, (int*)a.flags);
-        HIPCHK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(msiren::fuse_gather_kernel, dim3((unsigned)msiren::fuse_tiles(a.n, a.H, a.W)), dim3(256), 0, sc.s, (const float*)a.targets, (const float*)a.weights,
-                       (const double*)rec, (int)a.m, a.th, a.tw, a.H, a.W, (int)msiren::fuse_tiles_x(a.W), (int)msiren::fuse_tiles_y(a.H), spacing, min_coverage,
-                       (float*)a.volume, (float*)a.coverage);
-    HIPCHK(hipGetLastError());
-    return profile_end(h, c.stream, e1, voxels, "fuse_kernels");
-}
-
-int project_refusal(const msiren::ProjectArgs& a) {
-    char msg[256];
-    return msiren::project_check(a, msg, sizeof msg) ? 0 : fail(MSIREN_E_INVALID, "%s", msg);
+    Launcher go{sc.s};
+    launch_setup(go, a.maps, a.intensity, spacing, thickness, a.m, rec, a.flags);
+    launch_fusion(go, a.targets, a.weights, rec, a.m, a.th, a.tw, a.n, a.H, a.W, spacing, min_coverage, (float*)a.volume, (float*)a.coverage);
+    return go.rc ? go.rc : profile_end(h, c.stream, e1, a.n * a.H * a.W, "fuse_kernels");
 }
 
 // set-up, gather and (with targets) the residual and the sums on the call's stream, one profile entry; every pointer is the device's, `a` has passed
@@ -67,26 +81,17 @@ int project_on_stream(msiren_ctx* h, const Call& c, const msiren::ProjectArgs& a
     if ((rc = ensure(h, sc.ragged, lay.total))) return rc;
     double* const rec = (double*)((char*)sc.ragged.p + lay.records);
     double* const columns = a.stats ? (double*)((char*)sc.ragged.p + lay.columns) : nullptr;
+    const msiren_fuse_opts& o = *a.opts;
     hipEvent_t e1 = nullptr;
     if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-    hipLaunchKernelGGL(msiren::fuse_setup_kernel, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, sc.s, (const float*)a.maps, (const float*)a.intensity, a.opts->spacing,
-                       a.opts->thickness, (int)a.m, rec, (int*)a.flags);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(msiren::project_gather_kernel, dim3((unsigned)msiren::project_tiles(a.m, a.th, a.tw)), dim3(256), 0, sc.s, (const float*)a.volume, (const double*)rec,
-                       a.th, a.tw, (int)a.n, a.H, a.W, (int)msiren::project_tiles_x(a.tw), (int)msiren::project_tiles_y(a.th), a.opts->spacing, a.opts->thickness,
-                       a.opts->min_coverage, (float*)a.simulated, (float*)a.coverage);
-    HIPCHK(hipGetLastError());
-    if (a.targets && (a.residual || a.stats)) {
-        hipLaunchKernelGGL(msiren::project_stats_kernel, dim3((unsigned)a.m), dim3(256), 0, sc.s, (const float*)a.targets, (const float*)a.weights, (const float*)a.simulated,
-                           a.th, a.tw, columns, (float*)a.residual, (double*)a.stats);
-        HIPCHK(hipGetLastError());
-    }
-    return profile_end(h, c.stream, e1, a.m * a.th * a.tw, "project_kernels");
-}
-
-int solve_refusal(const msiren::SolveArgs& a) {
-    char msg[256];
-    return msiren::solve_check(a, msg, sizeof msg) ? 0 : fail(MSIREN_E_INVALID, "%s", msg);
+    Launcher go{sc.s};
+    launch_setup(go, a.maps, a.intensity, o.spacing, o.thickness, a.m, rec, a.flags);
+    go(msiren::project_gather_kernel, dim3((unsigned)msiren::project_tiles(a.m, a.th, a.tw)), (const float*)a.volume, (const double*)rec, a.th, a.tw, (int)a.n, a.H, a.W,
+       (int)msiren::project_tiles_x(a.tw), (int)msiren::project_tiles_y(a.th), o.spacing, o.thickness, o.min_coverage, (float*)a.simulated, (float*)a.coverage);
+    if (a.targets && (a.residual || a.stats))
+        go(msiren::project_stats_kernel, dim3((unsigned)a.m), (const float*)a.targets, (const float*)a.weights, (const float*)a.simulated, a.th, a.tw, columns,
+           (float*)a.residual, (double*)a.stats);
+    return go.rc ? go.rc : profile_end(h, c.stream, e1, a.m * a.th * a.tw, "project_kernels");
 }
 
 // the whole solve on the call's stream, one profile entry; every pointer is the device's, `a` has passed solve_check.  The sequence of launches
@@ -105,7 +110,7 @@ int solve_on_stream(msiren_ctx* h, const Call& c, const msiren::SolveArgs& a) {
     const msiren_solve_opts& o = *a.opts;
     const double cz = 1.0 / (o.spacing * o.spacing);
     const int n = (int)a.n, H = a.H, W = a.W, m = (int)a.m, voxels = n * H * W;
-    const dim3 wg(256), tiles((unsigned)fuse_tiles(a.n, H, W)), pixels((unsigned)(m > 0 ? project_tiles(a.m, a.th, a.tw) : 0));
+    const dim3 tiles((unsigned)fuse_tiles(a.n, H, W)), pixels((unsigned)(m > 0 ? project_tiles(a.m, a.th, a.tw) : 0));
     const dim3 pointwise((unsigned)solve_pointwise_blocks(a.n, H, W)), dots((unsigned)solve_dot_blocks(a.n, W));
     const int tx = (int)fuse_tiles_x(W), ty = (int)fuse_tiles_y(H), ptx = (int)project_tiles_x(a.tw), pty = (int)project_tiles_y(a.th);
     float* const volume = (float*)a.volume;
@@ -113,46 +118,37 @@ int solve_on_stream(msiren_ctx* h, const Call& c, const msiren::SolveArgs& a) {
     double* const history = (double*)a.history;
     hipEvent_t e1 = nullptr;
     if ((rc = profile_begin(h, c.stream, &e1))) return rc;
-#define MSIREN_SOLVE_LAUNCH(kernel, grid, ...)                              \
-    do {                                                                    \
-        hipLaunchKernelGGL(kernel, grid, wg, 0, sc.s, __VA_ARGS__);         \
-        HIPCHK(hipGetLastError());                                          \
-    } while (0)
-    auto forward = [&](const double* v) -> int {  // z = (Wt (P v)) / D
-        if (m > 0) MSIREN_SOLVE_LAUNCH(solve_forward_kernel, pixels, v, (const double*)rec, (const double*)D, (const double*)Wt, a.th, a.tw, n, H, W, ptx, pty, o.spacing, o.thickness, zz);
-        return 0;
+    Launcher go{sc.s};
+    auto forward = [&](const double* v) {  // z = (Wt (P v)) / D
+        if (m > 0) go(solve_forward_kernel, pixels, v, (const double*)rec, (const double*)D, (const double*)Wt, a.th, a.tw, n, H, W, ptx, pty, o.spacing, o.thickness, zz);
     };
-    auto transpose = [&](const double* v, double* out) -> int {  // out = Pt z [+ lambda L v]
-        MSIREN_SOLVE_LAUNCH(solve_transpose_kernel, tiles, (const double*)zz, (const double*)rec, sup, v, m, a.th, a.tw, n, H, W, tx, ty, o.spacing, o.lambda, cz, out);
-        return 0;
+    auto transpose = [&](const double* v, double* out) {  // out = Pt z [+ lambda L v]
+        go(solve_transpose_kernel, tiles, (const double*)zz, (const double*)rec, sup, v, m, a.th, a.tw, n, H, W, tx, ty, o.spacing, o.lambda, cz, out);
     };
-    auto dot = [&](const double* u, const double* v, int mode, int it) -> int {
-        MSIREN_SOLVE_LAUNCH(solve_dot_kernel, dots, u, v, sup, n, H, W, columns);
-        MSIREN_SOLVE_LAUNCH(solve_reduce_kernel, dim3(1), (const double*)columns, n, W, mode, it, slices, state, history);
-        return 0;
+    auto dot = [&](const double* u, const double* v, int mode, int it) {
+        go(solve_dot_kernel, dots, u, v, sup, n, H, W, columns);
+        go(solve_reduce_kernel, dim3(1), (const double*)columns, n, W, mode, it, slices, state, history);
     };
-    if (m > 0) MSIREN_SOLVE_LAUNCH(fuse_setup_kernel, dim3((unsigned)((m + 255) / 256)), (const float*)a.maps, (const float*)a.intensity, o.spacing, o.thickness, m, rec, (int*)a.flags);
-    if (!a.start || a.coverage)  // the start and / or the coverage: msiren_fuse_targets' gather, untouched
-        MSIREN_SOLVE_LAUNCH(fuse_gather_kernel, tiles, (const float*)a.targets, (const float*)a.weights, (const double*)rec, m, a.th, a.tw, H, W, tx, ty, o.spacing, o.min_coverage,
-                            a.start ? (float*)nullptr : volume, (float*)a.coverage);
-    MSIREN_SOLVE_LAUNCH(solve_start_kernel, pointwise, sup, voxels, x);
+    launch_setup(go, a.maps, a.intensity, o.spacing, o.thickness, a.m, rec, a.flags);
+    if (!a.start || a.coverage)  // the start and / or the coverage: msiren_fuse_targets' gather
+        launch_fusion(go, a.targets, a.weights, rec, a.m, a.th, a.tw, a.n, H, W, o.spacing, o.min_coverage, a.start ? (float*)nullptr : volume, (float*)a.coverage);
+    go(solve_start_kernel, pointwise, sup, voxels, x);
     if (m > 0)
-        MSIREN_SOLVE_LAUNCH(solve_coverage_kernel, pixels, sup, (const float*)a.targets, (const float*)a.weights, (const double*)rec, a.th, a.tw, n, H, W, ptx, pty, o.spacing,
-                            o.thickness, o.min_coverage, D, Wt, zz);
-    if ((rc = transpose(nullptr, r))) return rc;                     // r = Pt Omega tau
-    if ((rc = forward(x)) || (rc = transpose(x, q))) return rc;      // q = A x
-    MSIREN_SOLVE_LAUNCH(solve_residual_kernel, pointwise, (const double*)q, voxels, r, p);
-    if ((rc = dot(r, r, SOLVE_REDUCE_FIRST, 0))) return rc;
+        go(solve_coverage_kernel, pixels, sup, (const float*)a.targets, (const float*)a.weights, (const double*)rec, a.th, a.tw, n, H, W, ptx, pty, o.spacing, o.thickness,
+           o.min_coverage, D, Wt, zz);
+    transpose(nullptr, r);  // r = Pt Omega tau
+    forward(x), transpose(x, q);  // q = A x
+    go(solve_residual_kernel, pointwise, (const double*)q, voxels, r, p);
+    dot(r, r, SOLVE_REDUCE_FIRST, 0);
     for (int it = 0; it < o.iterations; ++it) {
-        if ((rc = forward(p)) || (rc = transpose(p, q))) return rc;  // q = A p
-        if ((rc = dot(p, q, SOLVE_REDUCE_GAMMA, it))) return rc;
-        MSIREN_SOLVE_LAUNCH(solve_update_xr_kernel, pointwise, (const double*)state, sup, (const double*)p, (const double*)q, voxels, x, r);
-        if ((rc = dot(r, r, SOLVE_REDUCE_RHO, it))) return rc;
-        MSIREN_SOLVE_LAUNCH(solve_update_p_kernel, pointwise, (const double*)state, sup, (const double*)r, voxels, p);
+        forward(p), transpose(p, q);  // q = A p
+        dot(p, q, SOLVE_REDUCE_GAMMA, it);
+        go(solve_update_xr_kernel, pointwise, (const double*)state, sup, (const double*)p, (const double*)q, voxels, x, r);
+        dot(r, r, SOLVE_REDUCE_RHO, it);
+        go(solve_update_p_kernel, pointwise, (const double*)state, sup, (const double*)r, voxels, p);
     }
-    MSIREN_SOLVE_LAUNCH(solve_store_kernel, pointwise, (const double*)x, (const double*)state, sup, voxels, volume, (int*)a.stopped_at);
-#undef MSIREN_SOLVE_LAUNCH
-    return profile_end(h, c.stream, e1, (int64_t)voxels, "solve_volume_kernels");
+    go(solve_store_kernel, pointwise, (const double*)x, (const double*)state, sup, voxels, volume, (int*)a.stopped_at);
+    return go.rc ? go.rc : profile_end(h, c.stream, e1, (int64_t)voxels, "solve_volume_kernels");
 }
 
 }  // namespace
@@ -166,7 +162,7 @@ int msiren_solve_volume_dev(msiren_handle h, const float* targets_dev, int64_t m
     if (rc) return rc;
     const msiren::SolveArgs a{targets_dev, m, th, tw, maps_dev, weights_dev, intensity_dev, opts, n, height, width, start_dev, volume_dev, coverage_dev, history_dev, flags_dev,
                               stopped_at_dev, true};
-    if ((rc = solve_refusal(a))) return rc;  // (before the stream rotates)
+    if ((rc = refusal(msiren::solve_check, a))) return rc;  // (before the stream rotates)
     return solve_on_stream(h, dev_call(h), a);
 }
 
@@ -177,7 +173,7 @@ int msiren_solve_volume(msiren_handle h, const float* targets_host, int64_t m, i
     if (rc) return rc;
     const msiren::SolveArgs host{targets_host, m, th, tw, maps_host, weights_host, intensity_host, opts, n, height, width, start_host, volume_host, coverage_host, history_host,
                                  flags_host, stopped_at_host, false};
-    if ((rc = solve_refusal(host))) return rc;
+    if ((rc = refusal(msiren::solve_check, host))) return rc;
     const Call c = make_call(h, true);
     const size_t nt = (size_t)(m > 0 ? m * th * tw : 0) * sizeof(float), nv = (size_t)n * height * width * sizeof(float);
     SyncHostCall io(h, c.stream);
@@ -201,7 +197,7 @@ int msiren_project_volume_dev(msiren_handle h, const float* volume_dev, int64_t 
     if (rc) return rc;
     const msiren::ProjectArgs a{volume_dev, n, height, width, maps_dev, intensity_dev, opts, m, th, tw, targets_dev, weights_dev, simulated_dev, coverage_dev, residual_dev,
                                 stats_dev, flags_dev, true};
-    if ((rc = project_refusal(a))) return rc;  // (before the stream rotates)
+    if ((rc = refusal(msiren::project_check, a))) return rc;  // (before the stream rotates)
     if (m == 0) return 0;                      // (no pixel: nothing to write)
     return project_on_stream(h, dev_call(h), a);
 }
@@ -213,7 +209,7 @@ int msiren_project_volume(msiren_handle h, const float* volume_host, int64_t n, 
     if (rc) return rc;
     const msiren::ProjectArgs host{volume_host, n, height, width, maps_host, intensity_host, opts, m, th, tw, targets_host, weights_host, simulated_host, coverage_host,
                                    residual_host, stats_host, flags_host, false};
-    if ((rc = project_refusal(host))) return rc;
+    if ((rc = refusal(msiren::project_check, host))) return rc;
     if (m == 0) return 0;
     const Call c = make_call(h, true);
     const size_t nt = (size_t)m * th * tw * sizeof(float), nv = (size_t)n * height * width * sizeof(float);
@@ -235,7 +231,7 @@ int msiren_fuse_targets_dev(msiren_handle h, const float* targets_dev, int64_t m
     int rc = check(h, false);
     if (rc) return rc;
     const msiren::FuseArgs a{targets_dev, m, th, tw, maps_dev, weights_dev, intensity_dev, opts, n, height, width, volume_dev, coverage_dev, flags_dev, true};
-    if ((rc = fuse_refusal(a))) return rc;  // (before the stream rotates)
+    if ((rc = refusal(msiren::fuse_check, a))) return rc;  // (before the stream rotates)
     if (!volume_dev && !coverage_dev) return 0;  // (m = 0 without an output)
     return fuse_on_stream(h, dev_call(h), a);
 }
@@ -246,7 +242,7 @@ int msiren_fuse_targets(msiren_handle h, const float* targets_host, int64_t m, i
     int rc = check(h, false);
     if (rc) return rc;
     const msiren::FuseArgs host{targets_host, m, th, tw, maps_host, weights_host, intensity_host, opts, n, height, width, volume_host, coverage_host, flags_host, false};
-    if ((rc = fuse_refusal(host))) return rc;
+    if ((rc = refusal(msiren::fuse_check, host))) return rc;
     if (!volume_host && !coverage_host) return 0;
     const Call c = make_call(h, true);
     const size_t nt = (size_t)(m > 0 ? m * th * tw : 0) * sizeof(float), nv = (size_t)n * height * width * sizeof(float);

@@ -2,20 +2,15 @@
 // gather -- per target pixel the normalised sum of window x bilinear weight x voxel over the voxels that have the pixel among their four taps, with
 // exactly the weights of msiren_fuse_targets.  The rule is include/msiren.h's, restated in numpy by mri_inr_amd/fuse.py (project_on_host,
 // project_stats_on_host): fp64 + - * /, contraction off, one rounding per operation -- the two agree bit for bit.  The per-target record is
-// fuse_setup_kernel's (fuse.hip.h), and p, pa, pb, cp, i, j, k, i0, j0, fi, fj and the four beta are fuse_gather_kernel's expressions.
+// fuse_setup_kernel's (fuse.hip.h), and p, pa, pb, cp, i, j, k, i0, j0, fi, fj and the four beta are fuse_visit_targets' expressions.
 //
-//   gather   project_gather_kernel   one workgroup of 256 per 16 x 16 tile of one target's pixels, one thread per pixel; the record of q is read with
-//                                    a wave-uniform index (scalar loads).  Each thread visits the box of voxels around its own point x = t + a pi + b pj
-//                                    (project_plan.h: project_box, with the proof), z, then y, then x ascending: the rule's order.  The trip counts
-//                                    are the target's, the same in every lane; the first index is the lane's, clipped to the grid.  num and den stay in
-//                                    registers; no LDS, no atomics, no barrier; pixels of a ragged tile outside (th, tw) store nothing
+//   gather   project_gather_kernel   one workgroup of 256 per 16 x 16 tile of one target's pixels, one thread per pixel (fuse_tile_lane); the record of q is
+//                                    read with a wave-uniform index (scalar loads).  Each thread visits the voxels around its own point through
+//                                    project_visit_voxels, shared with solve_volume.hip.h's two forward gathers.  num and den stay in registers; no
+//                                    LDS, no atomics, no barrier; pixels of a ragged tile outside (th, tw) store nothing
 //   stats    project_stats_kernel    one workgroup per target: thread tid sums the columns tid, tid + 256, ... down the rows (coalesced across the
 //                                    lanes), parks the four sums per column in the stream's scratch, and after a barrier threads 0 .. 3 add one
 //                                    quantity each over the columns ascending; [residual] is written on the way
-// Why the box is invisible in the output: a voxel outside it does not have the pixel among its taps or fails the window (project_plan.h), so the rule
-// adds no term for it; num and den start at +0.0 and see exactly the terms of the rule in the rule's order.  Inside the loop the window is tested as
-// cp cp < dt in front of the divisions: for dt > 0, fl(x / dt) < 1 iff x < dt (below dt the quotient is at most 1 - 2^-53, which is a double), so that
-// is k > 0 bit for bit (a NaN fails both).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,27 +19,22 @@
 
 namespace msiren {
 
-constexpr int PROJECT_TILE = 16;  // project_plan.h: kProjectTile
-
-// volume (n, H, W), rec (m, FUSE_RECORD) -> simulated (m, th, tw), coverage (m, th, tw) or null.  grid: tiles_y tiles_x m workgroups, the tile's column fastest
-__global__ __launch_bounds__(256) void project_gather_kernel(const float* __restrict__ volume, const double* __restrict__ rec, int th, int tw, int n, int H, int W,
-                                                             int tiles_x, int tiles_y, double spacing, double thickness, double min_coverage,
-                                                             float* __restrict__ simulated, float* __restrict__ coverage) {
+// The voxels that can add a term to pixel (pi, pj) of the target with record r, for project_gather_kernel, solve_coverage_kernel and
+// solve_forward_kernel: the box of voxels around the pixel's own point x = t + a pi + b pj (project_plan.h: project_box, with the proof), z, then y, then x
+// ascending: the rule's order.  The trip counts are the target's, the same in every lane; the first index is the lane's, clipped to the grid.
+// takes(at) says whether the voxel at flat index `at` takes part (asked behind the window test, so it may load); term(at, kb) receives every (voxel,
+// tap) pair of the rule, kb = k beta: the window times the bilinear weight the pixel has among the voxel's four taps.
+// Why the box is invisible in what the callers sum: a voxel outside it does not have the pixel among its taps or fails the window (project_plan.h), so
+// the rule has no term for it; a sum that starts at +0.0 sees exactly the terms of the rule in the rule's order.  Inside the loop the window is tested
+// as cp cp < dt in front of the divisions: for dt > 0, fl(x / dt) < 1 iff x < dt (below dt the quotient is at most 1 - 2^-53, which is a double), so
+// that is k > 0 bit for bit (a NaN fails both).
+template <class Takes, class Term>
+__device__ __forceinline__ void project_visit_voxels(const double* r, int pi, int pj, int th, int tw, int n, int H, int W, double spacing, double thickness, Takes takes,
+                                                     Term term) {
 #pragma clang fp contract(off)
-    const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, q = blockIdx.x / (tiles_x * tiles_y);
-    const int pj = bx * PROJECT_TILE + (threadIdx.x & (PROJECT_TILE - 1)), pi = by * PROJECT_TILE + (threadIdx.x / PROJECT_TILE);
-    const bool inside = pi < th && pj < tw;
-    const size_t at = ((size_t)q * th + (inside ? pi : 0)) * tw + (inside ? pj : 0);
-    const double* r = rec + (size_t)q * FUSE_RECORD;  // wave-uniform: scalar loads
-    if (r[19] != 0.0) {                               // a flagged target: NaN, coverage 0
-        if (inside) {
-            simulated[at] = __builtin_nanf("");
-            if (coverage) coverage[at] = 0.f;
-        }
-        return;
-    }
-    const double a0 = r[0], a1 = r[1], a2 = r[2], b0 = r[3], b1 = r[4], b2 = r[5], t0 = r[6], t1 = r[7], t2 = r[8];
-    const double G11 = r[9], G12 = r[10], G22 = r[11], det = r[12], dt = r[13], c0 = r[14], c1 = r[15], c2 = r[16];
+    const double a0 = r[FUSE_A], a1 = r[FUSE_A + 1], a2 = r[FUSE_A + 2], b0 = r[FUSE_B], b1 = r[FUSE_B + 1], b2 = r[FUSE_B + 2];
+    const double t0 = r[FUSE_T], t1 = r[FUSE_T + 1], t2 = r[FUSE_T + 2];
+    const double G11 = r[FUSE_G11], G12 = r[FUSE_G12], G22 = r[FUSE_G22], det = r[FUSE_DET], dt = r[FUSE_DT], c0 = r[FUSE_C], c1 = r[FUSE_C + 1], c2 = r[FUSE_C + 2];
     // ---- the box: radii and trip counts are the target's, the first index is the lane's ----
     double R[3];
     const bool boxed = project_box(r, thickness, spacing, n, H, W, R);
@@ -54,7 +44,6 @@ __global__ __launch_bounds__(256) void project_gather_kernel(const float* __rest
     const int y0 = project_base((t1 + a1 * dpi) + b1 * dpj, R[1], H, ny);
     const int x0 = project_base((t2 + a2 * dpi) + b2 * dpj, R[2], W, nx);
     const double th1 = (double)(th - 1), tw1 = (double)(tw - 1), th2 = (double)(th - 2), tw2 = (double)(tw - 2);
-    double num = 0.0, den = 0.0;
     for (int dz = 0; dz < nz; ++dz) {
         const int z = z0 + dz;  // 0 <= z0 and z0 + nz <= n (project_base): every index is inside the grid
         const double p0 = ((double)z * spacing) - t0;
@@ -63,14 +52,13 @@ __global__ __launch_bounds__(256) void project_gather_kernel(const float* __rest
             const int y = y0 + dy;
             const double p1 = (double)y - t1;
             const double fa = ea + (a1 * p1), fb = eb + (b1 * p1), fc = ec + (c1 * p1);
-            const float* row = volume + ((size_t)z * H + y) * W;
+            const size_t row = ((size_t)z * H + y) * W;
             for (int dx = 0; dx < nx; ++dx) {
                 const int x = x0 + dx;
                 const double p2 = (double)x - t2;
                 const double cp = fc + (c2 * p2), cc = cp * cp;
-                if (!(cc < dt)) continue;  // k <= 0 (header comment)
-                const float V = row[x];
-                if (!__builtin_isfinite(V)) continue;
+                if (!(cc < dt)) continue;  // k <= 0 (above)
+                if (!takes(row + x)) continue;
                 const double pa = fa + (a2 * p2), pb = fb + (b2 * p2);
                 const double i = ((G22 * pa) - (G12 * pb)) / det, j = ((G11 * pb) - (G12 * pa)) / det;
                 const double k = 1.0 - (cc / dt);
@@ -80,16 +68,40 @@ __global__ __launch_bounds__(256) void project_gather_kernel(const float* __rest
                     if ((di == 0.0 || di == 1.0) && (dj == 0.0 || dj == 1.0)) {
                         const double fi = i - fi0, fj = j - fj0, gi = 1.0 - fi, gj = 1.0 - fj;
                         const double beta = (di == 0.0 ? gi : fi) * (dj == 0.0 ? gj : fj);
-                        const double kb = k * beta;
-                        num += kb * (double)V;
-                        den += kb;
+                        term(row + x, k * beta);
                     }
                 }
             }
         }
     }
+}
+
+// volume (n, H, W), rec (m, kFuseRecord) -> simulated (m, th, tw), coverage (m, th, tw) or null.  grid: tiles_y tiles_x m workgroups (fuse_tile_lane)
+__global__ __launch_bounds__(256) void project_gather_kernel(const float* __restrict__ volume, const double* __restrict__ rec, int th, int tw, int n, int H, int W,
+                                                             int tiles_x, int tiles_y, double spacing, double thickness, double min_coverage,
+                                                             float* __restrict__ simulated, float* __restrict__ coverage) {
+#pragma clang fp contract(off)
+    const FuseTileLane l = fuse_tile_lane(tiles_x, tiles_y);
+    const int q = l.outer, pi = l.row, pj = l.col;
+    const bool inside = pi < th && pj < tw;
+    const size_t at = ((size_t)q * th + (inside ? pi : 0)) * tw + (inside ? pj : 0);
+    const double* r = rec + (size_t)q * kFuseRecord;  // wave-uniform: scalar loads
+    if (r[FUSE_FLAGS] != 0.0) {                       // a flagged target: NaN, coverage 0
+        if (inside) {
+            simulated[at] = __builtin_nanf("");
+            if (coverage) coverage[at] = 0.f;
+        }
+        return;
+    }
+    double num = 0.0, den = 0.0;
+    project_visit_voxels(
+        r, pi, pj, th, tw, n, H, W, spacing, thickness, [&](size_t v) { return __builtin_isfinite(volume[v]); },
+        [&](size_t v, double kb) {
+            num += kb * (double)volume[v];
+            den += kb;
+        });
     if (inside) {
-        const double g = r[17], bias = r[18];
+        const double g = r[FUSE_GAIN], bias = r[FUSE_BIAS];
         simulated[at] = den > min_coverage ? (float)((g * (num / den)) + bias) : __builtin_nanf("");
         if (coverage) coverage[at] = (float)den;
     }

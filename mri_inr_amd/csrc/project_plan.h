@@ -30,7 +30,7 @@
 
 namespace msiren {
 
-constexpr int kProjectTile = 16;   // target pixels per tile edge (project.hip.h: PROJECT_TILE)
+constexpr int kProjectTile = kFuseTile;  // target pixels per tile edge: the targets' lattices are tiled as the voxel grid is
 constexpr int kProjectSums = 4;    // doubles per column: count, sum w, sum w r, sum (w r) r
 
 // the radii without padding, in voxels of each axis (axis 0 in slices): what the proof above calls R
@@ -75,14 +75,15 @@ struct ProjectLayout {
     size_t total;     // bytes of the call's block
 };
 inline ProjectLayout project_layout(int64_t m, int32_t tw, bool stats) {
-    const size_t rec = (size_t)(m > 0 ? m : 0) * kFuseRecord * sizeof(double);
+    const size_t rec = fuse_records_bytes(m);
     const size_t col = stats && m > 0 ? (size_t)m * (size_t)tw * kProjectSums * sizeof(double) : 0;
     return ProjectLayout{0, rec, rec + col};
 }
 
-inline int64_t project_tiles_y(int32_t th) { return ((int64_t)th + kProjectTile - 1) / kProjectTile; }
-inline int64_t project_tiles_x(int32_t tw) { return ((int64_t)tw + kProjectTile - 1) / kProjectTile; }
-inline int64_t project_tiles(int64_t m, int32_t th, int32_t tw) { return m * project_tiles_y(th) * project_tiles_x(tw); }
+// fuse_plan.h's tile counts under the names of the lattice they count here
+inline int64_t project_tiles_y(int32_t th) { return fuse_tiles_y(th); }
+inline int64_t project_tiles_x(int32_t tw) { return fuse_tiles_x(tw); }
+inline int64_t project_tiles(int64_t m, int32_t th, int32_t tw) { return fuse_tiles(m, th, tw); }
 
 // What one call is given.  `device`: the pointers are device pointers, whose alignment is checked.
 struct ProjectArgs {
@@ -100,9 +101,7 @@ struct ProjectArgs {
 // true: the call is accepted.  false: `msg` names the argument that is refused.
 inline bool project_check(const ProjectArgs& a, char* msg, size_t cap) {
 #define MSIREN_PROJECT_REFUSE(...) return std::snprintf(msg, cap, __VA_ARGS__), false
-    // what msiren_fuse_targets refuses of the options and the sizes, in its words (a stand-in pointer where this call has its own null checks)
-    const FuseArgs f{a.m > 0 ? "" : nullptr, a.m, a.th, a.tw, a.m > 0 ? "" : nullptr, nullptr, nullptr, a.opts, a.n, a.H, a.W, a.m > 0 ? "" : nullptr, nullptr, nullptr, false};
-    if (!fuse_check(f, msg, cap)) return false;
+    if (!fuse_check_sizes(a.m, a.th, a.tw, a.opts, a.n, a.H, a.W, msg, cap)) return false;
     if (a.m > 0 && !a.volume) MSIREN_PROJECT_REFUSE("null argument (volume)");
     if (a.m > 0 && !a.maps) MSIREN_PROJECT_REFUSE("null argument (maps)");
     if (a.m > 0 && !a.simulated) MSIREN_PROJECT_REFUSE("null argument (simulated)");

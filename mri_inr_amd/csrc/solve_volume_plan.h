@@ -24,7 +24,7 @@ struct SolveLayout {
     size_t total;                                                  // bytes of the call's block
 };
 inline SolveLayout solve_layout(int64_t m, int32_t th, int32_t tw, int64_t n, int32_t H, int32_t W) {
-    const size_t rec = (size_t)(m > 0 ? m : 0) * kFuseRecord * sizeof(double);
+    const size_t rec = fuse_records_bytes(m);
     const size_t vox = (size_t)n * (size_t)H * (size_t)W * sizeof(double), pix = m > 0 ? (size_t)m * (size_t)th * (size_t)tw * sizeof(double) : 0;
     const size_t col = (size_t)n * (size_t)W * sizeof(double), sl = (size_t)n * sizeof(double);
     SolveLayout l;

@@ -4,7 +4,7 @@ back onto the stack's voxel grid, and the rule's normative restatement ``fuse_on
 Everything here is numpy fp64, ELEMENTWISE, in the associations of include/msiren.h -- no ``@``, ``dot``, ``cross`` or ``sum``, whose order of
 operations is numpy's business -- so the device equals ``fuse_on_host`` bit for bit.  The rule is cut into the small functions below (the window,
 the in-plane coordinates, the base index, a tap's validity, weight and value) so that a test can replace one of them by a wrong one and see its
-checks fail.  Below them the way back, ``ModulatedSiren.project_volume`` (section 5.18; msiren_project_volume): ``project_on_host`` and
+checks fail; ``voxel_taps`` is the one statement of which voxels reach which taps of a target, for the fusion, the projection and the solve.  Below them the way back, ``ModulatedSiren.project_volume`` (section 5.18; msiren_project_volume): ``project_on_host`` and
 ``project_stats_on_host``, cut up in the same way."""
 import collections
 
@@ -88,35 +88,20 @@ def fuse_on_host(targets, maps, shape, spacing, *, thickness=None, weights=None,
     wt = np.ones(tg.shape, np.float32) if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
     spacing = np.float64(spacing)
     r = target_records(maps, intensity, spacing, spacing if thickness is None else thickness)
-    v0 = (np.arange(n, dtype=np.float64) * spacing).reshape(n, 1, 1)
-    vy = np.arange(H, dtype=np.float64).reshape(1, H, 1)
-    vx = np.arange(W, dtype=np.float64).reshape(1, 1, W)
     num, den = np.zeros((n, H, W), np.float64), np.zeros((n, H, W), np.float64)
-    th1, tw1 = np.float64(th - 1), np.float64(tw - 1)
+    everywhere = np.ones((n, H, W), bool)
     with np.errstate(all="ignore"):
         for q in range(m):
-            if r.flags[q]:
+            taps = None if r.flags[q] else voxel_taps(r, q, everywhere, (n, H, W), (th, tw), spacing)
+            if taps is None:
                 continue
-            a, b, c = [x[q] for x in r.a], [x[q] for x in r.b], [x[q] for x in r.c]
-            p0, p1, p2 = v0 - r.t[0][q], vy - r.t[1][q], vx - r.t[2][q]
-            pa = ((a[0] * p0) + (a[1] * p1)) + (a[2] * p2)
-            pb = ((b[0] * p0) + (b[1] * p1)) + (b[2] * p2)
-            cp = ((c[0] * p0) + (c[1] * p1)) + (c[2] * p2)
-            i, j = in_plane(pa, pb, r.G11[q], r.G12[q], r.G22[q], r.det[q])
-            k = window(cp, r.dt[q])
-            at = np.nonzero((k > 0) & (i >= 0) & (i <= th1) & (j >= 0) & (j <= tw1))  # a NaN fails every comparison
-            if not len(at[0]):
-                continue
-            i, j, k = i[at], j[at], k[at]
-            fi0, fj0 = base_index(i, th), base_index(j, tw)
-            fi, fj = i - fi0, j - fj0
-            gi, gj = 1.0 - fi, 1.0 - fj
-            i0, j0 = fi0.astype(np.int64), fj0.astype(np.int64)
+            at, k, pixel, beta = taps
+            Tq, wq = tg[q].ravel(), wt[q].ravel()
             sn, sd = np.zeros(len(k), np.float64), np.zeros(len(k), np.float64)
-            for di, dj, beta in ((0, 0, gi * gj), (0, 1, gi * fj), (1, 0, fi * gj), (1, 1, fi * fj)):
-                T, w = tg[q][i0 + di, j0 + dj], wt[q][i0 + di, j0 + dj]
+            for tap in range(4):
+                T, w = Tq[pixel[:, tap]], wq[pixel[:, tap]]
                 ok = tap_valid(T, w)
-                bw = tap_weight(beta, w.astype(np.float64))
+                bw = tap_weight(beta[:, tap], w.astype(np.float64))
                 sn = sn + np.where(ok, bw * tap_value(T.astype(np.float64), r.bias[q], r.g[q]), 0.0)
                 sd = sd + np.where(ok, bw, 0.0)
             num[at] = num[at] + (k * sn)

@@ -32,6 +32,37 @@ def _is_torch(x) -> bool:
     return type(x).__module__.split(".")[0] == "torch"
 
 
+def _f32(x) -> np.ndarray:
+    """a tensor or an array -> contiguous float32 on the host"""
+    return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
+
+
+def _ptr(x, m):
+    """the address of a host array for a call with m targets: None for no array and for m == 0, where the library takes no per-target pointer"""
+    return x.ctypes.data if x is not None and m else None
+
+
+def _target_inputs(targets, maps, weights, intensity, shape):
+    """What fuse_targets, project_volume and solve_volume are given about the targets -> (targets or None, maps, weights or None, intensity or None)
+    as contiguous float32, checked against ``shape`` = (m, th, tw) or, where that is None, against targets' own shape"""
+    t, mp = None if targets is None else _f32(targets), _f32(maps)
+    if shape is None:
+        if t.ndim != 3:
+            raise ValueError(f"expected targets (m, th, tw), got shape {t.shape}")
+        shape = t.shape
+        if mp.shape != (shape[0], 9):
+            raise ValueError(f"expected maps of shape ({shape[0]}, 9), got {mp.shape}")
+    elif t is not None and t.shape != shape:
+        raise ValueError(f"expected targets of shape {shape}, got {t.shape}")
+    w = None if weights is None else _f32(weights)
+    if w is not None and w.shape != shape:
+        raise ValueError(f"expected weights of shape {shape}, got {w.shape}")
+    gb = None if intensity is None else _f32(intensity)
+    if gb is not None and gb.shape != (shape[0], 2):
+        raise ValueError(f"expected intensity of shape ({shape[0]}, 2), got {gb.shape}")
+    return t, mp, w, gb
+
+
 def _device_index(device) -> int | None:
     """'cuda', 'cuda:1', 1, torch.device('cuda', 1) -> ordinal; 'cpu' -> None."""
     if device is None:
@@ -563,9 +594,6 @@ class ModulatedSiren:
         c_dev = isinstance(coords, DeviceArray) or (c_t and coords.is_cuda)
         keep = []  # device arrays of this call stay alive until the sync below
 
-        def host_array(a):
-            return np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float32)
-
         def dev_ptr(a):
             if isinstance(a, DeviceArray):
                 return a.ptr
@@ -578,7 +606,7 @@ class ModulatedSiren:
                 torch.cuda.current_stream(a.device).synchronize()
                 keep.append(t)
                 return t.data_ptr()
-            h = host_array(a)
+            h = _f32(a)
             d = self.device_array(h.shape).copy_from(h)
             keep.append(d)
             return d.ptr
@@ -587,7 +615,7 @@ class ModulatedSiren:
         B = int(x.shape[batch_axis])
         shapes = [(B, Q), (2, B, Q)] if grad else [(B, Q)]
         if not (x_dev or c_dev):
-            a, c = host_array(x), host_array(coords)
+            a, c = _f32(x), _f32(coords)
             outs = []
             for shape in shapes:
                 o = self._pinned.array(shape, strict=False) if self._pin_outputs and B else None
@@ -709,9 +737,6 @@ class ModulatedSiren:
             return tuple(outs) if grad else outs[0]
         keep = []  # device arrays of this call stay alive until the sync below
 
-        def host_array(a):
-            return np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else a, dtype=np.float32)
-
         def dev_ptr(a, dtype=np.float32):
             if isinstance(a, DeviceArray):
                 return a.ptr
@@ -724,14 +749,14 @@ class ModulatedSiren:
                 torch.cuda.current_stream(a.device).synchronize()
                 keep.append(t)
                 return t.data_ptr()
-            hst = host_array(a) if dtype == np.float32 else a
+            hst = _f32(a) if dtype == np.float32 else a
             d = self.device_array(hst.shape)
             _lib.check(self._lib.msiren_memcpy_h2d(self._h, d.ptr, hst.ctypes.data, hst.nbytes))  # (4-byte elements either way)
             keep.append(d)
             return d.ptr
 
         if not (m_dev or c_dev or o_dev):
-            a, c = host_array(mods), host_array(coords)
+            a, c = _f32(mods), _f32(coords)
             outs = [np.empty(shape, dtype=np.float32) for shape in shapes]
             _lib.check(host_fn(self._h, c.ctypes.data, off.ctypes.data, a.ctypes.data, B, T, *[o.ctypes.data for o in outs]))
             if m_t:
@@ -942,19 +967,16 @@ class ModulatedSiren:
     @staticmethod
     def _align_w_inputs(images, targets, weights, intensity):
         """-> (images, targets, weights or None, intensity or None) as contiguous float32, shapes checked"""
-        def f32(x):
-            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
-
-        a, t = f32(images), f32(targets)
+        a, t = _f32(images), _f32(targets)
         if a.ndim != 3:
             raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
         n = a.shape[0]
         if t.ndim != 3 or t.shape[0] != n:
             raise ValueError(f"expected targets of shape ({n}, th, tw), got {t.shape}")
-        w = None if weights is None else f32(weights)
+        w = None if weights is None else _f32(weights)
         if w is not None and w.shape != t.shape:
             raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
-        gb = None if intensity is None else f32(intensity)
+        gb = None if intensity is None else _f32(intensity)
         if gb is not None and gb.shape != (n, 2):
             raise ValueError(f"expected intensity of shape ({n}, 2), got {gb.shape}")
         return a, t, w, gb
@@ -1113,14 +1135,11 @@ class ModulatedSiren:
     @staticmethod
     def _align_volume_w_inputs(images, targets, weights, intensity):
         """-> (images, targets, weights or None, intensity or None) as contiguous float32, shapes checked"""
-        def f32(x):
-            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
-
         a, t = ModulatedSiren._align_volume_inputs(images, targets)
-        w = None if weights is None else f32(weights)
+        w = None if weights is None else _f32(weights)
         if w is not None and w.shape != t.shape:
             raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
-        gb = None if intensity is None else f32(intensity)
+        gb = None if intensity is None else _f32(intensity)
         if gb is not None and gb.shape != (t.shape[0], 2):
             raise ValueError(f"expected intensity of shape ({t.shape[0]}, 2), got {gb.shape}")
         return a, t, w, gb
@@ -1308,22 +1327,9 @@ class ModulatedSiren:
         images and no weights of the model are involved: the result can go back into ``reconstruct`` / ``align_volume_*`` as ``images``."""
         from . import fuse
 
-        def f32(x):
-            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
-
         self._ensure_handle()
-        t, mp = f32(targets), f32(maps)
-        if t.ndim != 3:
-            raise ValueError(f"expected targets (m, th, tw), got shape {t.shape}")
+        t, mp, w, gb = _target_inputs(targets, maps, weights, intensity, None)
         m, th, tw = t.shape
-        if mp.shape != (m, 9):
-            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
-        w = None if weights is None else f32(weights)
-        if w is not None and w.shape != t.shape:
-            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
-        gb = None if intensity is None else f32(intensity)
-        if gb is not None and gb.shape != (m, 2):
-            raise ValueError(f"expected intensity of shape ({m}, 2), got {gb.shape}")
         if len(shape) != 3:
             raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
         n, Hh, Ww = (int(s) for s in shape)
@@ -1332,9 +1338,8 @@ class ModulatedSiren:
         vol = np.full((n, Hh, Ww) if ok else (0, 0, 0), np.nan, np.float32)
         cov = np.zeros(vol.shape, np.float32) if coverage else None
         flags = np.zeros(m, np.int32)
-        _lib.check(self._lib.msiren_fuse_targets(self._h, t.ctypes.data if m else None, m, th, tw, mp.ctypes.data if m else None, None if w is None or not m else w.ctypes.data,
-                                                 None if gb is None or not m else gb.ctypes.data, C.byref(o), n, Hh, Ww, vol.ctypes.data, cov.ctypes.data if coverage else None,
-                                                 flags.ctypes.data if m else None))
+        _lib.check(self._lib.msiren_fuse_targets(self._h, _ptr(t, m), m, th, tw, _ptr(mp, m), _ptr(w, m), _ptr(gb, m), C.byref(o), n, Hh, Ww, vol.ctypes.data,
+                                                 cov.ctypes.data if coverage else None, _ptr(flags, m)))
         return fuse.FuseResult(vol, cov, flags)
 
     def project_volume(self, volume, maps, shape, spacing, *, thickness=None, intensity=None, min_coverage=0.0, targets=None, weights=None, coverage=False,
@@ -1348,11 +1353,8 @@ class ModulatedSiren:
         model are involved."""
         from . import fuse
 
-        def f32(x):
-            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
-
         self._ensure_handle()
-        vol, mp = f32(volume), f32(maps)
+        vol, mp = _f32(volume), _f32(maps)
         if vol.ndim != 3:
             raise ValueError(f"expected volume (n, H, W), got shape {vol.shape}")
         if mp.ndim != 2 or mp.shape[1] != 9:
@@ -1360,17 +1362,9 @@ class ModulatedSiren:
         if len(shape) != 2:
             raise ValueError(f"expected shape = (th, tw), got {shape!r}")
         m, (th, tw) = len(mp), (int(s) for s in shape)
-        gb = None if intensity is None else f32(intensity)
-        if gb is not None and gb.shape != (m, 2):
-            raise ValueError(f"expected intensity of shape ({m}, 2), got {gb.shape}")
-        t = None if targets is None else f32(targets)
-        if t is None and (weights is not None or residual or stats):
+        if targets is None and (weights is not None or residual or stats):
             raise ValueError("weights, residual and stats need targets")
-        if t is not None and t.shape != (m, th, tw):
-            raise ValueError(f"expected targets of shape {(m, th, tw)}, got {t.shape}")
-        w = None if weights is None else f32(weights)
-        if w is not None and w.shape != (m, th, tw):
-            raise ValueError(f"expected weights of shape {(m, th, tw)}, got {w.shape}")
+        t, mp, w, gb = _target_inputs(targets, mp, weights, intensity, (m, th, tw))
         n, Hh, Ww = vol.shape
         o = _lib.FuseOpts(C.sizeof(_lib.FuseOpts), 0, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage))
         ok = th > 0 and tw > 0  # (the library refuses the others: nothing is allocated for them here)
@@ -1380,11 +1374,8 @@ class ModulatedSiren:
         st = np.zeros((m, 4), np.float64) if stats else None
         flags = np.zeros(m, np.int32)
 
-        def ptr(x):
-            return x.ctypes.data if x is not None and m else None
-
-        _lib.check(self._lib.msiren_project_volume(self._h, vol.ctypes.data if vol.size else None, n, Hh, Ww, ptr(mp), ptr(gb), C.byref(o), m, th, tw, ptr(t), ptr(w), ptr(sim),
-                                                   ptr(cov), ptr(res), ptr(st), ptr(flags)))
+        _lib.check(self._lib.msiren_project_volume(self._h, vol.ctypes.data if vol.size else None, n, Hh, Ww, _ptr(mp, m), _ptr(gb, m), C.byref(o), m, th, tw, _ptr(t, m), _ptr(w, m), _ptr(sim, m),
+                                                   _ptr(cov, m), _ptr(res, m), _ptr(st, m), _ptr(flags, m)))
         return fuse.ProjectResult(sim, cov, res, st, flags)
 
     def solve_volume(self, targets, maps, shape, spacing, *, iterations, lam=0.0, thickness=None, weights=None, intensity=None, min_coverage=0.0, start=None,
@@ -1399,26 +1390,13 @@ class ModulatedSiren:
         weights of the model are involved."""
         from . import solve_volume as sv
 
-        def f32(x):
-            return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
-
         self._ensure_handle()
-        t, mp = f32(targets), f32(maps)
-        if t.ndim != 3:
-            raise ValueError(f"expected targets (m, th, tw), got shape {t.shape}")
+        t, mp, w, gb = _target_inputs(targets, maps, weights, intensity, None)
         m, th, tw = t.shape
-        if mp.shape != (m, 9):
-            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
-        w = None if weights is None else f32(weights)
-        if w is not None and w.shape != t.shape:
-            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
-        gb = None if intensity is None else f32(intensity)
-        if gb is not None and gb.shape != (m, 2):
-            raise ValueError(f"expected intensity of shape ({m}, 2), got {gb.shape}")
         if len(shape) != 3:
             raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
         n, Hh, Ww = (int(s) for s in shape)
-        st = None if start is None else f32(start)
+        st = None if start is None else _f32(start)
         if st is not None and st.shape != (n, Hh, Ww):
             raise ValueError(f"expected start of shape {(n, Hh, Ww)}, got {st.shape}")
         iterations = int(iterations)
@@ -1430,11 +1408,8 @@ class ModulatedSiren:
         flags = np.zeros(m, np.int32)
         stopped = np.full(1, -1, np.int32)
 
-        def ptr(x):
-            return x.ctypes.data if x is not None and m else None
-
-        _lib.check(self._lib.msiren_solve_volume(self._h, ptr(t), m, th, tw, ptr(mp), ptr(w), ptr(gb), C.byref(o), n, Hh, Ww, st.ctypes.data if st is not None and st.size else None,
-                                                 vol.ctypes.data, cov.ctypes.data if coverage else None, hist.ctypes.data if history else None, ptr(flags), stopped.ctypes.data))
+        _lib.check(self._lib.msiren_solve_volume(self._h, _ptr(t, m), m, th, tw, _ptr(mp, m), _ptr(w, m), _ptr(gb, m), C.byref(o), n, Hh, Ww, st.ctypes.data if st is not None and st.size else None,
+                                                 vol.ctypes.data, cov.ctypes.data if coverage else None, hist.ctypes.data if history else None, _ptr(flags, m), stopped.ctypes.data))
         return sv.SolveVolumeResult(vol, cov, hist, flags, int(stopped[0]))
 
     def reconstruct_with_gradient(self, images, out_stride=None):

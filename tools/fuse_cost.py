@@ -25,33 +25,18 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from mri_inr_amd import ModulatedSiren, _lib, align_robust as ar, align_volume as av, fuse, synthetic as syn  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fuse_workload as fw  # noqa: E402
+from fuse_workload import GRID, MT, N, NS, SPACING  # noqa: E402
+from mri_inr_amd import _lib, fuse  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-N, NS, MT, SPACING, TILE = 320, 16, 64, 4.0, 16
-GRID = (NS, N, N)
+TILE = 16
 PEAK_FP64, PEAK_HBM = 78.6e12, 8.0e12
 
-m = ModulatedSiren(dim_in=2, dim_hidden=256, dim_out=1, num_layers=5, latent_dim=256, w0=1.0, w0_initial=30.0,
-                   use_bias=True, dropout=0.1, modulate=True, encoder_type="custom", encoder_path=None,
-                   outer_patch_size=32, inner_patch_size=16, siren_patch_size=24, device="cuda:0", activation="sine", precision="fp32")
-m.load_state_dict(syn.make_state_dict(seed=7, trained_like=True))
-m.to("cuda:0").eval()
+m = fw.model()
 lib, h = m._lib, m._h
-
-rng = np.random.default_rng(17)
-maps = np.zeros((MT, 9), np.float32)
-c0 = 0.5 * (N - 1)
-for q in range(MT):
-    ang, z0, z1 = rng.uniform(-0.02, 0.02), rng.uniform(-0.01, 0.01), rng.uniform(-0.01, 0.01)
-    c, s = np.cos(ang), np.sin(ang)
-    zc = -0.25 + q * (NS - 0.5) / (MT - 1)  # Z at the target's centre: -0.25 .. 15.25 slices
-    maps[q] = (z0, z1, zc - (z0 + z1) * c0, c, -s, c0 - (c - s) * c0 + rng.uniform(-2, 2), s, c, c0 - (s + c) * c0 + rng.uniform(-2, 2))
-i, j = np.mgrid[0:N, 0:N]
-targets = np.stack([syn.make_slice(q % NS, N, N) for q in range(MT)]).astype(np.float32)
-weights = np.tile((0.2 + 0.8 * np.exp(-(((i - 0.5 * N) / (0.6 * N)) ** 2 + ((j - 0.5 * N) / (0.6 * N)) ** 2))).astype(np.float32), (MT, 1, 1))
-gb = np.stack([np.linspace(0.8, 1.25, MT), np.linspace(-0.05, 0.1, MT)], axis=1).astype(np.float32)
-targets = (gb[:, :1, None] * targets + gb[:, 1:, None]).astype(np.float32)
+maps, targets, weights, gb = fw.workload()
 
 
 # ---- (b) the kernel's tile-level cull in numpy, and the pairs that contribute --------------------------------------------------------------------------
@@ -119,18 +104,8 @@ def call(w=True):
     _lib.check(lib.msiren_fuse_targets_dev(h, d_t.ptr, MT, N, N, d_m.ptr, d_w.ptr if w else None, d_gb.ptr, C.byref(o), NS, N, N, d_v.ptr, d_c.ptr, d_f.ptr))
 
 
-def profiled(w=True):
-    _lib.check(lib.msiren_profile_enable(h, 1))
-    call(w)
-    m.sync()
-    e = [e for e in m.profile_kernels() if e["kernel"] == "fuse_kernels"]
-    _lib.check(lib.msiren_profile_enable(h, 0))
-    assert len(e) == 1 and e[0]["launches"] == 1, e
-    return e[0]["ms_total"]
-
-
 call(), m.sync()  # warm-up: the scratch at its size
-ms = {key: [profiled(w) for _ in range(reps)] for key, w in (("weighted", True), ("unweighted", False))}
+ms = {key: [fw.profiled(m, lambda: call(w), "fuse_kernels") for _ in range(reps)] for key, w in (("weighted", True), ("unweighted", False))}
 call(), m.sync()
 dev_volume, dev_coverage, dev_flags = d_v.numpy(), d_c.numpy(), d_f.numpy().view(np.int32)
 stats = visits_and_contributions()
@@ -159,60 +134,18 @@ print(json.dumps({"fuse_on_host_s": round(host_s, 2), "device_equals_host_bit_fo
                   "host_over_device": round(host_s * 1e3 / float(np.median(ms["weighted"])), 1)}), flush=True)
 
 # ---- (e) robust alignment, then fusion with weights x rweight ------------------------------------------------------------------------------------------------
-DT, G, EVALS, TUNE = 16, 4, 12, 0.25
-SIZE = DT // G
-BLOCK = (slice(None), slice(100, 140), slice(120, 180))
-stack = np.stack([syn.make_slice(s, N, N) for s in range(NS)])
-planes = np.zeros((DT, 12))
-for q in range(DT):
-    first = SIZE * (q // SIZE)
-    zc = SPACING * (0.5 + (first + 0.5 * (SIZE - 1)) * (NS - 2.0) / (DT - 1))
-    planes[q] = np.concatenate([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [SPACING * (0.5 + q * (NS - 2.0) / (DT - 1)), 0.0, 0.0], [zc, c0, c0]])
-group_start = np.arange(0, DT + 1, SIZE, dtype=np.int32)
-group_of = np.repeat(np.arange(G), SIZE)
-
-
-def rotation_of(vec):
-    t = np.linalg.norm(vec)
-    k = vec / t
-    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
-    return np.eye(3) + np.sin(t) * K + (1.0 - np.cos(t)) * (K @ K)
-
-
-lin = np.linspace(-1.0, 1.0, G)
-rot_true = np.stack([rotation_of(np.deg2rad([0.1 * a, 0.1 * (0.5 - a), 0.5 * a + 0.01])) for a in lin])
-shift_true = np.stack([0.4 * lin, 0.8 * lin, -0.6 * lin], axis=1)
-truth = av.rigid_maps3(rot_true[group_of], shift_true[group_of], planes, SPACING)
-goal = m.align_volume_cost(stack, np.zeros((DT, N, N), np.float32), truth, warped=True).warped
-gbt = gb[:DT]
-goal_w = (gbt[:, :1, None] * goal + gbt[:, 1:, None]).astype(np.float32)
-goal_w[BLOCK] += 5.0
-open_w = weights[:DT].copy()
-open_w[BLOCK] = 1.0  # nothing masks the corruption
-kw = dict(weights=open_w, estimate_intensity=True, iterations=EVALS)
-quad = m.align_volume_solve_group(stack, goal_w, planes, SPACING, group_start, **kw)
-second = m.align_volume_solve_group_robust(stack, goal_w, planes, SPACING, group_start, ar.scale_from(quad, TUNE), rotation=quad.rotation, shift=quad.shift,
-                                           intensity=quad.intensity, **kw)
-rw = m.align_volume_cost_r(stack, goal_w, second.maps, ar.scale_from(quad, TUNE), weights=open_w, intensity=second.intensity, rweight=True).rweight
-clean_targets = (gbt[:, :1, None] * goal + gbt[:, 1:, None]).astype(np.float32)
-clean = m.fuse_targets(clean_targets, second.maps, GRID, SPACING, weights=open_w, intensity=second.intensity).volume.astype(np.float64)  # the targets without the + 5
+al = fw.robust_alignment(m, weights, gb)
+clean = m.fuse_targets(al.clean_targets, al.second.maps, GRID, SPACING, weights=al.open_w, intensity=al.second.intensity).volume.astype(np.float64)  # the targets without the + 5
 MIN_COVERAGE = 0.05
-inside = np.zeros(GRID, bool)
-inside[BLOCK] = True
 
 
 def errors(w, min_coverage):
-    res = m.fuse_targets(goal_w, second.maps, GRID, SPACING, weights=w, intensity=second.intensity, min_coverage=min_coverage)
-    e = np.abs(res.volume.astype(np.float64) - clean)
-    ok = np.isfinite(e)
-    return {"min_coverage": min_coverage, "covered_share": round(float(ok.mean()), 4), "mean_error_outside_the_block": float(e[ok & ~inside].mean()),
-            "mean_error_inside_the_block": float(e[ok & inside].mean()) if (ok & inside).any() else None, "covered_inside_the_block": int((ok & inside).sum()),
-            "voxels_inside_the_block": int(inside.sum())}
+    res = m.fuse_targets(al.goal_w, al.second.maps, GRID, SPACING, weights=w, intensity=al.second.intensity, min_coverage=min_coverage)
+    return {"min_coverage": min_coverage, **fw.errors(res.volume, clean, al.inside)}
 
 
-robust_w = open_w * np.nan_to_num(rw, nan=0.0)
-print(json.dumps({"demonstration": {"largest_map_error_after_the_robust_pass": float(np.abs(second.maps.astype(np.float64) - truth).max()),
-                                    "rweight_inside_the_block_max": float(np.nanmax(rw[BLOCK])), "rweight_outside_the_block_median": float(np.nanmedian(rw[:, :100])),
+print(json.dumps({"demonstration": {"largest_map_error_after_the_robust_pass": float(np.abs(al.second.maps.astype(np.float64) - al.truth).max()),
+                                    "rweight_inside_the_block_max": float(np.nanmax(al.rw[al.block])), "rweight_outside_the_block_median": float(np.nanmedian(al.rw[:, :100])),
                                     "error_against_the_fusion_of_the_uncorrupted_targets": {
-                                        "plain_weights": [errors(open_w, 0.0), errors(open_w, MIN_COVERAGE)],
-                                        "weights_times_rweight": [errors(robust_w, 0.0), errors(robust_w, MIN_COVERAGE)]}}}), flush=True)
+                                        "plain_weights": [errors(al.open_w, 0.0), errors(al.open_w, MIN_COVERAGE)],
+                                        "weights_times_rweight": [errors(al.robust_w, 0.0), errors(al.robust_w, MIN_COVERAGE)]}}}), flush=True)

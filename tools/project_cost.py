@@ -25,33 +25,18 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from mri_inr_amd import ModulatedSiren, _lib, fuse, synthetic as syn  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fuse_workload as fw  # noqa: E402
+from fuse_workload import GRID, MT, N, NS, SPACING  # noqa: E402
+from mri_inr_amd import _lib, fuse, synthetic as syn  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-N, NS, MT, SPACING = 320, 16, 64, 4.0
-GRID = (NS, N, N)
 PEAK_FP64, PEAK_HBM = 78.6e12, 8.0e12
 
-m = ModulatedSiren(dim_in=2, dim_hidden=256, dim_out=1, num_layers=5, latent_dim=256, w0=1.0, w0_initial=30.0,
-                   use_bias=True, dropout=0.1, modulate=True, encoder_type="custom", encoder_path=None,
-                   outer_patch_size=32, inner_patch_size=16, siren_patch_size=24, device="cuda:0", activation="sine", precision="fp32")
-m._ensure_handle()  # (no weights are committed: the call needs none)
+m = fw.model(committed=False)
 lib, h = m._lib, m._h
-
-rng = np.random.default_rng(17)
-maps = np.zeros((MT, 9), np.float32)
-c0 = 0.5 * (N - 1)
-for q in range(MT):
-    ang, z0, z1 = rng.uniform(-0.02, 0.02), rng.uniform(-0.01, 0.01), rng.uniform(-0.01, 0.01)
-    c, s = np.cos(ang), np.sin(ang)
-    zc = -0.25 + q * (NS - 0.5) / (MT - 1)  # Z at the target's centre: -0.25 .. 15.25 slices
-    maps[q] = (z0, z1, zc - (z0 + z1) * c0, c, -s, c0 - (c - s) * c0 + rng.uniform(-2, 2), s, c, c0 - (s + c) * c0 + rng.uniform(-2, 2))
-i, j = np.mgrid[0:N, 0:N]
+maps, targets, weights, gb = fw.workload()
 stack = np.stack([syn.make_slice(s, N, N) for s in range(NS)]).astype(np.float32)
-targets = np.stack([syn.make_slice(q % NS, N, N) for q in range(MT)]).astype(np.float32)
-weights = np.tile((0.2 + 0.8 * np.exp(-(((i - 0.5 * N) / (0.6 * N)) ** 2 + ((j - 0.5 * N) / (0.6 * N)) ** 2))).astype(np.float32), (MT, 1, 1))
-gb = np.stack([np.linspace(0.8, 1.25, MT), np.linspace(-0.05, 0.1, MT)], axis=1).astype(np.float32)
-targets = (gb[:, :1, None] * targets + gb[:, 1:, None]).astype(np.float32)
 
 
 # ---- (b) project_plan.h's box in numpy, and the pairs that contribute ------------------------------------------------------------------------------------
@@ -94,20 +79,10 @@ def fuse_call():
     _lib.check(lib.msiren_fuse_targets_dev(h, d_t.ptr, MT, N, N, d_m.ptr, d_w.ptr, d_gb.ptr, C.byref(o), NS, N, N, d_fv.ptr, d_fc.ptr, d_f.ptr))
 
 
-def profiled(fn, name):
-    _lib.check(lib.msiren_profile_enable(h, 1))
-    fn()
-    m.sync()
-    e = [e for e in m.profile_kernels() if e["kernel"] == name]
-    _lib.check(lib.msiren_profile_enable(h, 0))
-    assert len(e) == 1 and e[0]["launches"] == 1, e
-    return e[0]["ms_total"]
-
-
 d_fv, d_fc = m.device_array(GRID), m.device_array(GRID)
 call(True), fuse_call(), m.sync()  # warm-up: the scratch at its size
-ms = {"gather": [profiled(lambda: call(False), "project_kernels") for _ in range(reps)], "gather_and_stats": [profiled(lambda: call(True), "project_kernels") for _ in range(reps)],
-      "fuse_kernels": [profiled(fuse_call, "fuse_kernels") for _ in range(reps)]}
+ms = {"gather": [fw.profiled(m, lambda: call(False), "project_kernels") for _ in range(reps)], "gather_and_stats": [fw.profiled(m, lambda: call(True), "project_kernels") for _ in range(reps)],
+      "fuse_kernels": [fw.profiled(m, fuse_call, "fuse_kernels") for _ in range(reps)]}
 call(True), m.sync()
 dev = fuse.ProjectResult(d_s.numpy(), d_c.numpy(), d_r.numpy(), d_st.numpy().view(np.float64), d_f.numpy().view(np.int32))
 counts = tested_and_contributing()

@@ -24,33 +24,17 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-from mri_inr_amd import ModulatedSiren, _lib, align_robust as ar, align_volume as av, fuse, synthetic as syn  # noqa: E402
-from mri_inr_amd import solve_volume as sv  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import fuse_workload as fw  # noqa: E402
+from fuse_workload import GRID, MT, N, NS, SPACING  # noqa: E402
+from mri_inr_amd import _lib, solve_volume as sv  # noqa: E402
 
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 7
-N, NS, MT, SPACING, LAM = 320, 16, 64, 4.0, 0.01
-GRID = (NS, N, N)
+LAM = 0.01
 
-m = ModulatedSiren(dim_in=2, dim_hidden=256, dim_out=1, num_layers=5, latent_dim=256, w0=1.0, w0_initial=30.0,
-                   use_bias=True, dropout=0.1, modulate=True, encoder_type="custom", encoder_path=None,
-                   outer_patch_size=32, inner_patch_size=16, siren_patch_size=24, device="cuda:0", activation="sine", precision="fp32")
-m.load_state_dict(syn.make_state_dict(seed=7, trained_like=True))  # (only the alignment of (f) needs the weights)
-m.to("cuda:0").eval()
+m = fw.model()  # (only the alignment of (f) needs the weights)
 lib, h = m._lib, m._h
-
-rng = np.random.default_rng(17)
-maps = np.zeros((MT, 9), np.float32)
-c0 = 0.5 * (N - 1)
-for q in range(MT):
-    ang, z0, z1 = rng.uniform(-0.02, 0.02), rng.uniform(-0.01, 0.01), rng.uniform(-0.01, 0.01)
-    c, s = np.cos(ang), np.sin(ang)
-    zc = -0.25 + q * (NS - 0.5) / (MT - 1)  # Z at the target's centre: -0.25 .. 15.25 slices
-    maps[q] = (z0, z1, zc - (z0 + z1) * c0, c, -s, c0 - (c - s) * c0 + rng.uniform(-2, 2), s, c, c0 - (s + c) * c0 + rng.uniform(-2, 2))
-i, j = np.mgrid[0:N, 0:N]
-targets = np.stack([syn.make_slice(q % NS, N, N) for q in range(MT)]).astype(np.float32)
-weights = np.tile((0.2 + 0.8 * np.exp(-(((i - 0.5 * N) / (0.6 * N)) ** 2 + ((j - 0.5 * N) / (0.6 * N)) ** 2))).astype(np.float32), (MT, 1, 1))
-gb = np.stack([np.linspace(0.8, 1.25, MT), np.linspace(-0.05, 0.1, MT)], axis=1).astype(np.float32)
-targets = (gb[:, :1, None] * targets + gb[:, 1:, None]).astype(np.float32)
+maps, targets, weights, gb = fw.workload()
 
 # ---- (a), (b) the device -----------------------------------------------------------------------------------------------------------------------------------
 shape = (MT, N, N)
@@ -74,22 +58,12 @@ def project_call():
     _lib.check(lib.msiren_project_volume_dev(h, d_fv.ptr, NS, N, N, d_m.ptr, d_gb.ptr, C.byref(fo), MT, N, N, None, None, d_s.ptr, None, None, None, None))
 
 
-def profiled(fn, name):
-    _lib.check(lib.msiren_profile_enable(h, 1))
-    fn()
-    m.sync()
-    e = [e for e in m.profile_kernels() if e["kernel"] == name]
-    _lib.check(lib.msiren_profile_enable(h, 0))
-    assert len(e) == 1 and e[0]["launches"] == 1, e
-    return e[0]["ms_total"]
-
-
 fuse_call(), m.sync()
 d_fv = m.device_array(GRID).copy_from(d_v.numpy())  # the fusion: what the projection reads
 solve_call(10), project_call(), m.sync()            # warm-up: the scratch at its size
-ms = {f"solve_{k}": [profiled(lambda: solve_call(k), "solve_volume_kernels") for _ in range(reps)] for k in (0, 1, 10)}
-ms["project_kernels"] = [profiled(project_call, "project_kernels") for _ in range(reps)]
-ms["fuse_kernels"] = [profiled(fuse_call, "fuse_kernels") for _ in range(reps)]
+ms = {f"solve_{k}": [fw.profiled(m, lambda: solve_call(k), "solve_volume_kernels") for _ in range(reps)] for k in (0, 1, 10)}
+ms["project_kernels"] = [fw.profiled(m, project_call, "project_kernels") for _ in range(reps)]
+ms["fuse_kernels"] = [fw.profiled(m, fuse_call, "fuse_kernels") for _ in range(reps)]
 med = {k: float(np.median(v)) for k, v in ms.items()}
 per_iteration = (med["solve_10"] - med["solve_0"]) / 10
 parents = med["project_kernels"] + med["fuse_kernels"]
@@ -140,57 +114,16 @@ for thickness in sc.THICKNESSES:
 print(json.dumps({"mean_error_after_0_1_2_3_4_5_30_iterations": curves}), flush=True)
 
 # ---- (f) robust alignment, then the solve with weights x rweight -----------------------------------------------------------------------------------------------
-DT, G, EVALS, TUNE, ITER = 16, 4, 12, 0.25, 10
-SIZE = DT // G
-BLOCK = (slice(None), slice(100, 140), slice(120, 180))
-stack = np.stack([syn.make_slice(s, N, N) for s in range(NS)])
-planes = np.zeros((DT, 12))
-for q in range(DT):
-    first = SIZE * (q // SIZE)
-    zc = SPACING * (0.5 + (first + 0.5 * (SIZE - 1)) * (NS - 2.0) / (DT - 1))
-    planes[q] = np.concatenate([[0.0, 1.0, 0.0], [0.0, 0.0, 1.0], [SPACING * (0.5 + q * (NS - 2.0) / (DT - 1)), 0.0, 0.0], [zc, c0, c0]])
-group_start = np.arange(0, DT + 1, SIZE, dtype=np.int32)
-group_of = np.repeat(np.arange(G), SIZE)
-
-
-def rotation_of(vec):
-    a = np.linalg.norm(vec)
-    k = vec / a
-    K = np.array([[0.0, -k[2], k[1]], [k[2], 0.0, -k[0]], [-k[1], k[0], 0.0]])
-    return np.eye(3) + np.sin(a) * K + (1.0 - np.cos(a)) * (K @ K)
-
-
-lin = np.linspace(-1.0, 1.0, G)
-rot_true = np.stack([rotation_of(np.deg2rad([0.1 * a, 0.1 * (0.5 - a), 0.5 * a + 0.01])) for a in lin])
-shift_true = np.stack([0.4 * lin, 0.8 * lin, -0.6 * lin], axis=1)
-truth = av.rigid_maps3(rot_true[group_of], shift_true[group_of], planes, SPACING)
-goal = m.align_volume_cost(stack, np.zeros((DT, N, N), np.float32), truth, warped=True).warped
-gbt = gb[:DT]
-goal_w = (gbt[:, :1, None] * goal + gbt[:, 1:, None]).astype(np.float32)
-goal_w[BLOCK] += 5.0
-open_w = weights[:DT].copy()
-open_w[BLOCK] = 1.0  # nothing masks the corruption
-kw = dict(weights=open_w, estimate_intensity=True, iterations=EVALS)
-quad = m.align_volume_solve_group(stack, goal_w, planes, SPACING, group_start, **kw)
-second = m.align_volume_solve_group_robust(stack, goal_w, planes, SPACING, group_start, ar.scale_from(quad, TUNE), rotation=quad.rotation, shift=quad.shift,
-                                           intensity=quad.intensity, **kw)
-rw = m.align_volume_cost_r(stack, goal_w, second.maps, ar.scale_from(quad, TUNE), weights=open_w, intensity=second.intensity, rweight=True).rweight
-clean_targets = (gbt[:, :1, None] * goal + gbt[:, 1:, None]).astype(np.float32)
-skw = dict(iterations=ITER, lam=LAM, intensity=second.intensity)
-clean = m.solve_volume(clean_targets, second.maps, GRID, SPACING, weights=open_w, **skw).volume.astype(np.float64)  # the targets without the + 5
-inside = np.zeros(GRID, bool)
-inside[BLOCK] = True
+ITER = 10
+al = fw.robust_alignment(m, weights, gb)
+skw = dict(iterations=ITER, lam=LAM, intensity=al.second.intensity)
+clean = m.solve_volume(al.clean_targets, al.second.maps, GRID, SPACING, weights=al.open_w, **skw).volume.astype(np.float64)  # the targets without the + 5
 
 
 def errors(w):
-    res = m.solve_volume(goal_w, second.maps, GRID, SPACING, weights=w, **skw)
-    e = np.abs(res.volume.astype(np.float64) - clean)
-    ok = np.isfinite(e)
-    return {"covered_share": round(float(ok.mean()), 4), "mean_error_outside_the_block": float(e[ok & ~inside].mean()),
-            "mean_error_inside_the_block": float(e[ok & inside].mean()) if (ok & inside).any() else None, "covered_inside_the_block": int((ok & inside).sum()),
-            "voxels_inside_the_block": int(inside.sum()), "stopped_at": res.stopped_at}
+    res = m.solve_volume(al.goal_w, al.second.maps, GRID, SPACING, weights=w, **skw)
+    return {**fw.errors(res.volume, clean, al.inside), "stopped_at": res.stopped_at}
 
 
-robust_w = open_w * np.nan_to_num(rw, nan=0.0)
-print(json.dumps({"demonstration": {"iterations": ITER, "lambda": LAM, "largest_map_error_after_the_robust_pass": float(np.abs(second.maps.astype(np.float64) - truth).max()),
-                                    "error_against_the_solve_of_the_uncorrupted_targets": {"plain_weights": errors(open_w), "weights_times_rweight": errors(robust_w)}}}), flush=True)
+print(json.dumps({"demonstration": {"iterations": ITER, "lambda": LAM, "largest_map_error_after_the_robust_pass": float(np.abs(al.second.maps.astype(np.float64) - al.truth).max()),
+                                    "error_against_the_solve_of_the_uncorrupted_targets": {"plain_weights": errors(al.open_w), "weights_times_rweight": errors(al.robust_w)}}}), flush=True)
