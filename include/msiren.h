@@ -44,7 +44,8 @@ extern "C" {
  * msiren_align_volume_solve_group_r(_dev) (the weighted volume cost and the grouped solve under a Geman-McClure loss with one scale per target);
  * msiren_fuse_targets(_dev) and msiren_fuse_opts (aligned target slices gathered back onto the stack's voxel grid); msiren_project_volume(_dev) (the
  * way back: a stack gathered onto the targets' lattices with the same weights, with the residual against given targets and four sums per target);
- * msiren_solve_volume(_dev) and msiren_solve_opts (the stack that best explains all targets: regularised conjugate gradients on those two operators).
+ * msiren_solve_volume(_dev) and msiren_solve_opts (the stack that best explains all targets: regularised conjugate gradients on those two operators);
+ * msiren_solve_volume_r(_dev) and msiren_solve_r_opts (rounds of that solve, reweighted by a Geman-McClure loss with one annealed scale per target).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -952,6 +953,61 @@ MSIREN_API int msiren_solve_volume_dev(msiren_handle h, const float* targets_dev
                                        const float* start_dev /* (n, H, W) or NULL */, float* volume_dev /* (n, H, W) */, float* coverage_dev /* (n, H, W) or NULL */,
                                        double* history_dev /* (iterations + 1, 2) or NULL */, int32_t* flags_dev /* (m) or NULL */,
                                        int32_t* stopped_at_dev /* (1) or NULL */);
+
+/* Build-defined: msiren_solve_volume with outlier rejection -- `rounds` reweighting rounds in one device call without a host
+ * synchronisation.  Each round recomputes every pixel's Geman-McClure weight from the residual of the current iterate and runs `iterations` steps of
+ * msiren_solve_volume's conjugate gradients on the reweighted normal equations, warm-started from x in fp64.
+ *     targets, m, th, tw, maps, weights, intensity, n, height, width, start, volume, coverage, flags: msiren_solve_volume's arguments
+ *     scale (m) float64: per target, (c sigma)^2 in squared target-intensity units as in msiren_align_volume_r; +inf: the quadratic loss
+ *     opts (HOST memory in both forms): msiren_solve_opts' fields, rounds (0 .. 64, rounds iterations <= 1024) and anneal (finite, >= 1)
+ *     history (rounds, iterations + 1, 2) float64 or NULL;  stopped_at (rounds) int32 or NULL;  rweight (m, th, tw) float32 or NULL;
+ *     residual (m, th, tw) float32 or NULL (the _dev form only);  stats (m, 4) float64 or NULL
+ * All arithmetic is fp64 + - * /, one rounding per operation, no fused multiply-add.  The records, the flags, the support S, the start, D, the
+ * active pixels, tau, FORWARD, TRANSPOSE, LAPLACIAN, the INNER PRODUCT, the loop and its stop rule are msiren_solve_volume's, unchanged; Wt0 = ((double)w g) g
+ * is its Wt.
+ *   SCHEDULE (on the host, in fp64): c[rounds - 1] = 1.0, c[t] = c[t + 1] anneal.  The scale of target q in round t is s = scale[q] c[t].
+ *   REWEIGHTING PASS with the current x and a factor c, per active pixel of an unflagged target, num and D as in FORWARD:
+ *     u = num / D        sim = (g u) + b        e = (double)T - sim
+ *     a = (e e) / s      v = 1.0 + a            om = 1.0 / v            omega = om om;   if not (s > 0) (a NaN included): omega = +0.0
+ *     Wt = Wt0 omega     z = (Wt tau) / D       z' = (Wt u) / D
+ *   Wt, z and z' are +0.0 on a pixel that is not active.  s = +inf gives omega = 1.0 and Wt0's bits.  A non-finite omega is not special-cased: it
+ *   makes gamma non-finite and the round stops by msiren_solve_volume's rule.
+ *   ROUND t = 0 .. rounds - 1: the reweighting pass with c[t]; r = (Pt z) - ((Pt z') + (lambda (L x))), p = r, rho = <r, r>; the stop state is reset;
+ *   `iterations` steps of msiren_solve_volume's loop with this round's Wt.  history[t] is the round's (iterations + 1, 2) block, stopped_at[t] the
+ *   iteration at which the round stopped, or -1.
+ *   AFTER THE LAST ROUND, only if rweight, residual or stats is given: one more reweighting pass with the final x and c = 1.0.
+ *     rweight = (float)omega where the pixel is active and s > 0, NaN elsewhere;  residual = (float)e, NaN where the pixel is not active
+ *     stats[q] = (count, sum w, sum w omega, sum (((double)w om) e) e) over the active pixels of a target with s > 0, with w omega = (double)w (om om), in
+ *     msiren_project_volume's order: per column j the sum over the rows i ascending from 0.0, then the column sums for j ascending from 0.0.  A
+ *     flagged target and one whose s is not > 0 have a row of zeros.
+ *   volume = (float)x on S, NaN elsewhere.
+ * rounds = 1 with every scale +inf returns msiren_solve_volume's volume, history and stopped_at bit for bit; rounds = 0 or iterations = 0 returns the
+ * start; m_targets = 0 behaves as in msiren_solve_volume.  mri_inr_amd/solve_volume_robust.py: solve_volume_robust_on_host (numpy) gives the same bits.
+ * MSIREN_E_INVALID before any launch, naming the argument: opts->struct_size; everything msiren_solve_volume refuses; rounds < 0 or > 64; rounds
+ * iterations > 1024; anneal not finite or < 1; a null scale with m > 0; a device scale, stats or history that is not 8-byte aligned; a device rweight,
+ * residual or stopped_at that is not 4-byte aligned.  Under msiren_profile_enable: one entry per call, "solve_volume_r_kernels". */
+typedef struct {
+    int32_t struct_size;      /* sizeof(msiren_solve_r_opts) */
+    int32_t iterations;       /* per round, 0 .. 1024 */
+    int32_t rounds;           /* 0 .. 64, rounds iterations <= 1024 */
+    int32_t reserved;         /* 0 */
+    double spacing, thickness, min_coverage, lambda, anneal;
+} msiren_solve_r_opts;
+MSIREN_API int msiren_solve_volume_r(msiren_handle h, const float* targets_host, int64_t m_targets, int32_t th, int32_t tw, const float* maps_host /* (m, 9) */,
+                                     const float* weights_host /* (m, th, tw) or NULL */, const float* intensity_host /* (m, 2) or NULL */,
+                                     const double* scale_host /* (m) */, const msiren_solve_r_opts* opts, int64_t n_slices, int32_t height, int32_t width,
+                                     const float* start_host /* (n, H, W) or NULL */, float* volume_host /* (n, H, W) */,
+                                     float* coverage_host /* (n, H, W) or NULL */, double* history_host /* (rounds, iterations + 1, 2) or NULL */,
+                                     int32_t* flags_host /* (m) or NULL */, int32_t* stopped_at_host /* (rounds) or NULL */,
+                                     float* rweight_host /* (m, th, tw) or NULL */, double* stats_host /* (m, 4) or NULL */);
+MSIREN_API int msiren_solve_volume_r_dev(msiren_handle h, const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw, const float* maps_dev /* (m, 9) */,
+                                         const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */,
+                                         const double* scale_dev /* (m) */, const msiren_solve_r_opts* opts /* host */, int64_t n_slices, int32_t height,
+                                         int32_t width, const float* start_dev /* (n, H, W) or NULL */, float* volume_dev /* (n, H, W) */,
+                                         float* coverage_dev /* (n, H, W) or NULL */, double* history_dev /* (rounds, iterations + 1, 2) or NULL */,
+                                         int32_t* flags_dev /* (m) or NULL */, int32_t* stopped_at_dev /* (rounds) or NULL */,
+                                         float* rweight_dev /* (m, th, tw) or NULL */, float* residual_dev /* (m, th, tw) or NULL */,
+                                         double* stats_dev /* (m, 4) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

@@ -151,6 +151,21 @@ class SolveOpts(C.Structure):
     ]
 
 
+class SolveROpts(C.Structure):
+    """msiren_solve_r_opts"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("iterations", C.c_int32),
+        ("rounds", C.c_int32),
+        ("reserved", C.c_int32),
+        ("spacing", C.c_double),
+        ("thickness", C.c_double),
+        ("min_coverage", C.c_double),
+        ("lam", C.c_double),
+        ("anneal", C.c_double),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -249,6 +264,9 @@ PROTOTYPES = {
     "msiren_project_volume_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_solve_volume": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(SolveOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_solve_volume_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(SolveOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_solve_volume_r": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(SolveROpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_solve_volume_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(SolveROpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                            _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

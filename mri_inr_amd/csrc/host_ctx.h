@@ -31,6 +31,8 @@
 //                          tiling, scratch and the box of voxels per pixel: project_plan.h, tests/test_project_reference.py)
 //                          and msiren_solve_volume*: conjugate gradients on those two operators in one call (kernels: solve_volume.hip.h;
 //                          refusals, scratch and the launch plan: solve_volume_plan.h, tests/test_solve_volume_reference.py)
+//                          and msiren_solve_volume_r*: that solve in rounds reweighted by a Geman-McClure loss (kernels: solve_volume_r.hip.h;
+//                          refusals, scratch, the schedule and the launch plan: solve_volume_r_plan.h, tests/test_solve_volume_robust_reference.py)
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1412,6 +1412,48 @@ class ModulatedSiren:
                                                  vol.ctypes.data, cov.ctypes.data if coverage else None, hist.ctypes.data if history else None, _ptr(flags, m), stopped.ctypes.data))
         return sv.SolveVolumeResult(vol, cov, hist, flags, int(stopped[0]))
 
+    def solve_volume_robust(self, targets, maps, shape, spacing, scale, *, rounds, iterations, anneal=1.0, lam=0.0, thickness=None, weights=None, intensity=None,
+                            min_coverage=0.0, start=None, coverage=False, history=False, rweight=False, stats=False):
+        """``solve_volume`` with outlier rejection -> ``solve_volume_robust.SolveVolumeRobustResult``: ``rounds`` reweighting rounds in one device
+        call.  Each round recomputes every pixel's Geman-McClure weight omega = 1 / (1 + e^2 / s)^2 from the residual e = T - (g P x + b) of the
+        current iterate and runs ``iterations`` steps of ``solve_volume``'s conjugate gradients on the reweighted normal equations, warm-started from
+        x in fp64.  ``scale`` a scalar or (m,), (c sigma)^2 in squared target-intensity units as in ``align_volume_cost_r`` (+inf: the quadratic
+        loss); the scale of round t is ``scale`` x ``anneal``^(rounds - 1 - t): a graduated schedule that ends on ``scale``.  Every other argument as
+        in ``solve_volume``.  ``history``: (rounds, iterations + 1, 2) too; ``rweight``: the final omega per pixel (m, th, tw), NaN where the pixel
+        takes no part; ``stats``: (m, 4) = (count, sum w, sum w omega, sum w om e^2) per target -- sum w omega / sum w tells the rejected slices.
+        ``stopped_at`` (rounds,): per round the iteration at which it broke down, else -1.  Build-defined (DESIGN.md section 5.20;
+        msiren_solve_volume_r); bit for bit what ``solve_volume_robust.solve_volume_robust_on_host`` gives.  With rounds = 1 and scale +inf:
+        ``solve_volume``'s bits.  No images and no weights of the model are involved."""
+        from . import align_robust as ar, solve_volume_robust as svr
+
+        self._ensure_handle()
+        t, mp, w, gb = _target_inputs(targets, maps, weights, intensity, None)
+        m, th, tw = t.shape
+        if len(shape) != 3:
+            raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
+        n, Hh, Ww = (int(s) for s in shape)
+        st = None if start is None else _f32(start)
+        if st is not None and st.shape != (n, Hh, Ww):
+            raise ValueError(f"expected start of shape {(n, Hh, Ww)}, got {st.shape}")
+        s = ar.scales(scale, m)
+        rounds, iterations = int(rounds), int(iterations)
+        o = _lib.SolveROpts(C.sizeof(_lib.SolveROpts), iterations, rounds, 0, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage),
+                            float(lam), float(anneal))
+        ok = n > 0 and Hh > 0 and Ww > 0  # (the library refuses the others: nothing is allocated for them here)
+        vol = np.full((n, Hh, Ww) if ok else (0, 0, 0), np.nan, np.float32)
+        cov = np.zeros(vol.shape, np.float32) if coverage else None
+        nr = min(max(rounds, 0), 64)  # (the library refuses the others)
+        hist = np.full((nr, max(iterations, 0) + 1, 2), np.nan, np.float64) if history else None
+        flags = np.zeros(m, np.int32)
+        stopped = np.full(nr, -1, np.int32)
+        rw = np.full(t.shape, np.nan, np.float32) if rweight else None
+        sts = np.zeros((m, 4), np.float64) if stats else None
+
+        _lib.check(self._lib.msiren_solve_volume_r(self._h, _ptr(t, m), m, th, tw, _ptr(mp, m), _ptr(w, m), _ptr(gb, m), _ptr(s, m), C.byref(o), n, Hh, Ww,
+                                                   st.ctypes.data if st is not None and st.size else None, vol.ctypes.data, cov.ctypes.data if coverage else None,
+                                                   _ptr(hist, nr), _ptr(flags, m), _ptr(stopped, nr), _ptr(rw, m), _ptr(sts, m)))
+        return svr.SolveVolumeRobustResult(vol, cov, hist, flags, stopped, rw, sts)
+
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
         and the image gradient per OUTPUT pixel, grad[0] along the rows, grad[1] along the columns -- the fold-weighted average of the
