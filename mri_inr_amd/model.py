@@ -24,43 +24,9 @@ import numpy as np
 
 from . import _lib
 from . import synthetic
+from .registration import _Registration, _f32, _is_torch
 
 _ACT = {"sine": _lib.ACT_SINE, "morlet": _lib.ACT_MORLET}
-
-
-def _is_torch(x) -> bool:
-    return type(x).__module__.split(".")[0] == "torch"
-
-
-def _f32(x) -> np.ndarray:
-    """a tensor or an array -> contiguous float32 on the host"""
-    return np.ascontiguousarray(x.detach().cpu().numpy() if _is_torch(x) else x, dtype=np.float32)
-
-
-def _ptr(x, m):
-    """the address of a host array for a call with m targets: None for no array and for m == 0, where the library takes no per-target pointer"""
-    return x.ctypes.data if x is not None and m else None
-
-
-def _target_inputs(targets, maps, weights, intensity, shape):
-    """What fuse_targets, project_volume and solve_volume are given about the targets -> (targets or None, maps, weights or None, intensity or None)
-    as contiguous float32, checked against ``shape`` = (m, th, tw) or, where that is None, against targets' own shape"""
-    t, mp = None if targets is None else _f32(targets), _f32(maps)
-    if shape is None:
-        if t.ndim != 3:
-            raise ValueError(f"expected targets (m, th, tw), got shape {t.shape}")
-        shape = t.shape
-        if mp.shape != (shape[0], 9):
-            raise ValueError(f"expected maps of shape ({shape[0]}, 9), got {mp.shape}")
-    elif t is not None and t.shape != shape:
-        raise ValueError(f"expected targets of shape {shape}, got {t.shape}")
-    w = None if weights is None else _f32(weights)
-    if w is not None and w.shape != shape:
-        raise ValueError(f"expected weights of shape {shape}, got {w.shape}")
-    gb = None if intensity is None else _f32(intensity)
-    if gb is not None and gb.shape != (shape[0], 2):
-        raise ValueError(f"expected intensity of shape ({shape[0]}, 2), got {gb.shape}")
-    return t, mp, w, gb
 
 
 def _device_index(device) -> int | None:
@@ -185,8 +151,9 @@ class _PinnedPool:
                 self._lib.msiren_host_free(None, lst.pop())
 
 
-class ModulatedSiren:
-    """See module docstring.  Constructor signature: modulated_siren.py:349-368."""
+class ModulatedSiren(_Registration):
+    """See module docstring.  Constructor signature: modulated_siren.py:349-368.  The registration calls, ``resample`` to ``solve_volume_robust``,
+    are bound in ``registration.py``."""
 
     def __init__(self, dim_in, dim_hidden, dim_out, num_layers, latent_dim, w0, w0_initial, use_bias,
                  dropout, modulate, encoder_type, encoder_path, outer_patch_size, inner_patch_size,
@@ -797,662 +764,6 @@ class ModulatedSiren:
         """As sample_mods_ragged -> (values (T,), grad (2, T)): value and ``d SirenNet.forward / d coords`` per coordinate, grad[0] along
         ``coords[:, 0]`` (rows) -- the bits of ``sample_mods_grad`` patch by patch (msiren_sample_ragged_grad_mods)."""
         return self._sample_ragged(self._lib.msiren_sample_ragged_grad_mods, self._lib.msiren_sample_ragged_grad_mods_dev, mods, coords, offsets, True)
-
-    def _resample(self, images, points, grad, exact=True):
-        self._ensure_committed()
-        a = images.detach().cpu().numpy() if _is_torch(images) else np.asarray(images)
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        single = a.ndim == 2
-        if single:
-            a = a[None]
-        if a.ndim != 3:
-            raise ValueError(f"expected (n, H, W) images, got {a.shape}")
-        p = np.ascontiguousarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float32)
-        if p.ndim != 2 or p.shape[1] != 2:
-            raise ValueError(f"expected points of shape (M, 2), got {p.shape}")
-        n, Hh, Ww = a.shape
-        M = p.shape[0]
-        outs = [np.empty(shape, dtype=np.float32) for shape in (((n, M), (2, n, M)) if grad else ((n, M),))]
-        fn = self._lib.msiren_resample_slices_grad if grad else self._lib.msiren_resample_slices if exact else self._lib.msiren_resample_slices_native
-        _lib.check(fn(self._h, a.ctypes.data, n, Hh, Ww, p.ctypes.data, M, *[o.ctypes.data for o in outs]))
-        if single:
-            outs = [outs[0][0]] + [o[:, 0] for o in outs[1:]]
-        if _is_torch(images):
-            import torch
-
-            outs = [torch.from_numpy(o) for o in outs]
-        return tuple(outs) if grad else outs[0]
-
-    def resample(self, images, points, *, exact=True):
-        """images (n, Hh, Ww) or (Hh, Ww), points (M, 2) -> (n, M) or (M,): the reconstruction of ``reconstruct(images)`` read at real
-        positions ``points[m] = (Y, X)`` in reconstruction pixel coordinates (integer (Y, X): the centre of ``recon[Y, X]``), one point
-        set for all slices -- every covering tile's network evaluated at the point, blended with the fold's weights (build-defined,
-        DESIGN.md section 5.8; msiren_resample_slices).  The exact-fp32 trunk; ``exact=False``: the model's own trunk arithmetic
-        (msiren_resample_slices_native; sample_mods_ragged has the details).  NaN where no tile covers the point."""
-        return self._resample(images, points, False, exact)
-
-    def resample_with_gradient(self, images, points):
-        """As resample -> (values (n, M), grad (2, n, M)): grad per reconstruction pixel, grad[0] along the rows -- the weight-averaged
-        analytic gradients of the covering tiles, as ``reconstruct_with_gradient`` defines it (msiren_resample_slices_grad)."""
-        return self._resample(images, points, True)
-
-    def _resample_volume(self, images, points, grad, exact=True):
-        self._ensure_committed()
-        a = images.detach().cpu().numpy() if _is_torch(images) else np.asarray(images)
-        a = np.ascontiguousarray(a, dtype=np.float32)
-        if a.ndim != 3:
-            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
-        p = np.ascontiguousarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float32)
-        if p.ndim != 2 or p.shape[1] != 3:
-            raise ValueError(f"expected points of shape (M, 3), got {p.shape}")
-        n, Hh, Ww = a.shape
-        M = p.shape[0]
-        outs = [np.full(shape, np.nan, dtype=np.float32) for shape in (((M,), (3, M)) if grad else ((M,),))]  # (n = 0: no Z is valid, no call's work)
-        fn = self._lib.msiren_resample_volume_grad if grad else self._lib.msiren_resample_volume if exact else self._lib.msiren_resample_volume_native
-        _lib.check(fn(self._h, a.ctypes.data, n, Hh, Ww, p.ctypes.data, M, *[o.ctypes.data for o in outs]))
-        if _is_torch(images):
-            import torch
-
-            outs = [torch.from_numpy(o) for o in outs]
-        return tuple(outs) if grad else outs[0]
-
-    def resample_volume(self, images, points, *, exact=True):
-        """images (n, Hh, Ww), points (M, 3) -> (M,): the stack read as a volume at ``points[m] = (Z, Y, X)`` -- (Y, X) as in ``resample``,
-        Z in slice units (integer Z: slice Z), valid for 0 <= Z <= n - 1.  ``resample`` of the two slices either side of Z, blended
-        linearly in fp32; at an integer Z the bits of ``resample(images[Z], ...)`` (build-defined, DESIGN.md section 5.9;
-        msiren_resample_volume).  Two trunk evaluations per point and covering tile, whatever n is.  The exact-fp32 trunk;
-        ``exact=False``: the model's own trunk arithmetic (msiren_resample_volume_native).  NaN for an invalid Z, a non-finite (Y, X) or
-        a point no tile covers."""
-        return self._resample_volume(images, points, False, exact)
-
-    def resample_volume_with_gradient(self, images, points):
-        """As resample_volume -> (values (M,), grad (3, M)); n >= 2.  grad[0] per slice of Z: the fp32 difference of the two slices of
-        the segment that contains Z (at an interior integer the segment to its right); grad[1], grad[2] per reconstruction pixel along
-        rows and columns, ``resample_with_gradient``'s planes blended like the value (msiren_resample_volume_grad)."""
-        return self._resample_volume(images, points, True)
-
-    def resample_each(self, images, points, *, exact=True):
-        """images (n, Hh, Ww), points (n, M, 2) -> (n, M): every slice at its OWN point set in one call -- the volume call at integer Z,
-        so out[s] is the bits of ``resample(images[s], points[s], exact=exact)``."""
-        p = np.asarray(points.detach().cpu().numpy() if _is_torch(points) else points, dtype=np.float32)
-        n = len(images)
-        if p.ndim != 3 or p.shape[0] != n or p.shape[2] != 2:
-            raise ValueError(f"expected points of shape ({n}, M, 2), got {p.shape}")
-        M = p.shape[1]
-        zyx = np.empty((n, M, 3), np.float32)
-        zyx[:, :, 0] = np.arange(n, dtype=np.float32)[:, None]
-        zyx[:, :, 1:] = p
-        out = self._resample_volume(images, zyx.reshape(n * M, 3), False, exact)
-        return out.reshape(n, M)
-
-    def align_cost(self, images, targets, maps, *, warped=False, gradient=False):
-        """images (n, Hh, Ww), targets (n, th, tw), maps (n, 6) -> ``align.AlignResult``: every slice read on its target's lattice under its
-        own affine map (``align.map_points``: pixel (i, j) at Y = a00 i + a01 j + t0, X = a10 i + a11 j + t1 in reconstruction pixels) and
-        scored against the target on the device -- ``count`` valid pixels, ``cost`` = sum (R - T)^2, ``grad`` = d cost / d map (n, 6),
-        ``jtj`` (n, 6, 6) the Gauss-Newton matrix; R and its gradient are the bits of ``resample_with_gradient`` (build-defined, DESIGN.md
-        section 5.10; msiren_align_slices).  A NaN target pixel, an uncovered or non-finite point is left out.  fp64 sums in a fixed order:
-        the same bits run to run, alone or in a batch.  ``warped`` / ``gradient``: also return R (n, th, tw) / (gY, gX) (2, n, th, tw)."""
-        from . import align
-
-        self._ensure_committed()
-        a = np.ascontiguousarray(images.detach().cpu().numpy() if _is_torch(images) else images, dtype=np.float32)
-        t = np.ascontiguousarray(targets.detach().cpu().numpy() if _is_torch(targets) else targets, dtype=np.float32)
-        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        if a.ndim != 3:
-            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
-        n, Hh, Ww = a.shape
-        if t.ndim != 3 or t.shape[0] != n:
-            raise ValueError(f"expected targets of shape ({n}, th, tw), got {t.shape}")
-        if m.shape != (n, 6):
-            raise ValueError(f"expected maps of shape ({n}, 6), got {m.shape}")
-        th, tw = t.shape[1:]
-        sums = np.zeros((n, align.SUMS), np.float64)
-        w = np.full((n, th, tw), np.nan, np.float32) if warped else None
-        g = np.full((2, n, th, tw), np.nan, np.float32) if gradient else None
-        _lib.check(self._lib.msiren_align_slices(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, m.ctypes.data, sums.ctypes.data,
-                                                 w.ctypes.data if warped else None, g.ctypes.data if gradient else None))
-        return align.unpack(sums, w, g)
-
-    def _align_solve(self, images, targets, mode, maps, rigid, centre, iterations, damping, down, up, lam_min, lam_max, trace):
-        from . import align
-
-        self._ensure_committed()
-        a = np.ascontiguousarray(images.detach().cpu().numpy() if _is_torch(images) else images, dtype=np.float32)
-        t = np.ascontiguousarray(targets.detach().cpu().numpy() if _is_torch(targets) else targets, dtype=np.float32)
-        if a.ndim != 3:
-            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
-        n, Hh, Ww = a.shape
-        if t.ndim != 3 or t.shape[0] != n:
-            raise ValueError(f"expected targets of shape ({n}, th, tw), got {t.shape}")
-        if mode == align.AFFINE and maps.shape != (n, 6):
-            raise ValueError(f"expected maps of shape ({n}, 6), got {maps.shape}")
-        if mode == align.RIGID and rigid.shape != (n, 4):
-            raise ValueError(f"expected {n} angles and shifts of shape ({n}, 2), got a state of shape {rigid.shape}")
-        th, tw = t.shape[1:]
-        o = _lib.AlignSolveOpts(C.sizeof(_lib.AlignSolveOpts), mode, int(iterations), 0, float(damping), float(down), float(up), float(lam_min), float(lam_max),
-                                float(centre[0]), float(centre[1]))
-        out = np.zeros((n, 6), np.float32) if mode == align.RIGID else maps.copy()
-        rout = rigid.copy() if mode == align.RIGID else None
-        report = np.zeros((n, 6), np.float64)
-        tr = np.zeros((max(int(iterations), 0), n, 8), np.float64) if trace else None
-        _lib.check(self._lib.msiren_align_solve(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, C.byref(o), maps.ctypes.data if mode == align.AFFINE else None,
-                                                rigid.ctypes.data if mode == align.RIGID else None, out.ctypes.data, rout.ctypes.data if mode == align.RIGID else None,
-                                                report.ctypes.data, tr.ctypes.data if trace else None))
-        return align.solve_result(out, rout, report, tr)
-
-    def align_solve(self, images, targets, maps, *, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
-        """images (n, Hh, Ww), targets (n, th, tw), maps (n, 6) -> ``align.SolveResult``: every slice aligned to its target over the six
-        affine parameters, on the device -- ``align_cost``'s prologue once, then ``iterations`` evaluations with a Levenberg-Marquardt step
-        behind each (per slice: accept a lower mean cost and lower the damping by ``down``, reject and raise it by ``up``), no host
-        synchronisation in between (build-defined; msiren_align_solve).  ``maps`` of the result is the best map of
-        every slice; bit for bit what ``align.solve_on_host`` gives around ``align_cost``.  ``trace``: also the trial map, cost and count
-        of every evaluation (iterations, n, 8)."""
-        from . import align
-
-        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        return self._align_solve(images, targets, align.AFFINE, m, None, (0.0, 0.0), iterations, damping, down, up, lam_min, lam_max, trace)
-
-    def align_solve_rigid(self, images, targets, angle, shift, centre, *, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9,
-                          trace=False):
-        """As ``align_solve`` over rotation and in-plane shift: slice s starts at ``align.rigid_maps(angle, shift, centre)[s]`` (angle (n,)
-        radians, shift (n, 2), centre (2,) = (Y, X); cos, sin and shift are formed in fp64 here) and every trial is a rigid map about
-        ``centre`` (msiren_align_solve, mode 1).  ``angle`` and ``shift`` of the result are the best state's."""
-        from . import align
-
-        ang = np.atleast_1d(np.asarray(angle, dtype=np.float64))
-        sh = np.broadcast_to(np.asarray(shift, dtype=np.float64), (len(ang), 2))
-        rigid = np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang), sh[:, 0], sh[:, 1]], axis=1))
-        return self._align_solve(images, targets, align.RIGID, None, rigid, centre, iterations, damping, down, up, lam_min, lam_max, trace)
-
-    @staticmethod
-    def _align_w_inputs(images, targets, weights, intensity):
-        """-> (images, targets, weights or None, intensity or None) as contiguous float32, shapes checked"""
-        a, t = _f32(images), _f32(targets)
-        if a.ndim != 3:
-            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
-        n = a.shape[0]
-        if t.ndim != 3 or t.shape[0] != n:
-            raise ValueError(f"expected targets of shape ({n}, th, tw), got {t.shape}")
-        w = None if weights is None else _f32(weights)
-        if w is not None and w.shape != t.shape:
-            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
-        gb = None if intensity is None else _f32(intensity)
-        if gb is not None and gb.shape != (n, 2):
-            raise ValueError(f"expected intensity of shape ({n}, 2), got {gb.shape}")
-        return a, t, w, gb
-
-    def align_cost_w(self, images, targets, maps, *, weights=None, intensity=None, warped=False, gradient=False):
-        """``align_cost`` with a per-pixel weight and a per-slice gain and bias -> ``align.AlignResultW``: ``weights`` (n, th, tw) or None (all
-        1; a weight that is zero, negative or not finite masks its pixel), ``intensity`` (n, 2) = (g, b) or None ((1, 0)); ``cost`` = sum w (g R
-        + b - T)^2 over the valid pixels, ``wsum`` their weights, ``grad`` (n, 8) and ``jtj`` (n, 8, 8) over (a00, a01, t0, a10, a11, t1, g, b)
-        (build-defined; msiren_align_slices_w).  Without weights and intensity the shared entries are ``align_cost``'s
-        bits.  ``warped`` / ``gradient`` return R and (gY, gX) before gain and bias."""
-        from . import align
-
-        self._ensure_committed()
-        a, t, w, gb = self._align_w_inputs(images, targets, weights, intensity)
-        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        n, Hh, Ww = a.shape
-        if m.shape != (n, 6):
-            raise ValueError(f"expected maps of shape ({n}, 6), got {m.shape}")
-        th, tw = t.shape[1:]
-        sums = np.zeros((n, align.SUMS_W), np.float64)
-        wp = np.full((n, th, tw), np.nan, np.float32) if warped else None
-        g = np.full((2, n, th, tw), np.nan, np.float32) if gradient else None
-        _lib.check(self._lib.msiren_align_slices_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, m.ctypes.data, None if w is None else w.ctypes.data,
-                                                   None if gb is None else gb.ctypes.data, sums.ctypes.data, wp.ctypes.data if warped else None,
-                                                   g.ctypes.data if gradient else None))
-        return align.unpack_w(sums, wp, g)
-
-    def _align_solve_w(self, images, targets, mode, maps, rigid, centre, weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min, lam_max, trace):
-        from . import align
-
-        self._ensure_committed()
-        a, t, w, gb = self._align_w_inputs(images, targets, weights, intensity)
-        n, Hh, Ww = a.shape
-        if mode == align.AFFINE and maps.shape != (n, 6):
-            raise ValueError(f"expected maps of shape ({n}, 6), got {maps.shape}")
-        if mode == align.RIGID and rigid.shape != (n, 4):
-            raise ValueError(f"expected {n} angles and shifts of shape ({n}, 2), got a state of shape {rigid.shape}")
-        th, tw = t.shape[1:]
-        o = _lib.AlignSolveWOpts(C.sizeof(_lib.AlignSolveWOpts), mode, int(iterations), align.ESTIMATE if estimate_intensity else align.FIXED, float(damping), float(down),
-                                 float(up), float(lam_min), float(lam_max), float(centre[0]), float(centre[1]))
-        out = np.zeros((n, 6), np.float32) if mode == align.RIGID else maps.copy()
-        gout = np.tile(np.array([1.0, 0.0], np.float32), (n, 1)) if gb is None else gb.copy()
-        rout = rigid.copy() if mode == align.RIGID else None
-        report = np.zeros((n, 7), np.float64)
-        tr = np.zeros((max(int(iterations), 0), n, 11), np.float64) if trace else None
-        _lib.check(self._lib.msiren_align_solve_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, th, tw, C.byref(o), maps.ctypes.data if mode == align.AFFINE else None,
-                                                  rigid.ctypes.data if mode == align.RIGID else None, None if w is None else w.ctypes.data,
-                                                  None if gb is None else gb.ctypes.data, out.ctypes.data, gout.ctypes.data,
-                                                  rout.ctypes.data if mode == align.RIGID else None, report.ctypes.data, tr.ctypes.data if trace else None))
-        return align.solve_result_w(out, gout, rout, report, tr)
-
-    def align_solve_w(self, images, targets, maps, *, weights=None, intensity=None, estimate_intensity=True, iterations=12, damping=1e-3, down=0.1, up=10.0,
-                      lam_min=1e-9, lam_max=1e9, trace=False):
-        """``align_solve`` on ``align_cost_w`` -> ``align.SolveResultW``: every pixel weighted by ``weights`` (n, th, tw), the target modelled as
-        g R + b per slice from ``intensity`` (n, 2) (None: (1, 0)).  ``estimate_intensity``: (g, b) are solved for together with the map (8
-        parameters); False: they stay at their inputs (6).  The accept / reject rule compares cost / wsum (build-defined, DESIGN.md section 5.12;
-        msiren_align_solve_w); bit for bit what ``align.solve_on_host_w`` gives around ``align_cost_w``.  ``trace``: (iterations, n, 11)."""
-        from . import align
-
-        m = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        return self._align_solve_w(images, targets, align.AFFINE, m, None, (0.0, 0.0), weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min,
-                                   lam_max, trace)
-
-    def align_solve_rigid_w(self, images, targets, angle, shift, centre, *, weights=None, intensity=None, estimate_intensity=True, iterations=12, damping=1e-3, down=0.1,
-                            up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
-        """As ``align_solve_w`` over rotation and in-plane shift (``align_solve_rigid``'s arguments): 5 parameters with the intensity, 3 without."""
-        from . import align
-
-        ang = np.atleast_1d(np.asarray(angle, dtype=np.float64))
-        sh = np.broadcast_to(np.asarray(shift, dtype=np.float64), (len(ang), 2))
-        rigid = np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang), sh[:, 0], sh[:, 1]], axis=1))
-        return self._align_solve_w(images, targets, align.RIGID, None, rigid, centre, weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min,
-                                   lam_max, trace)
-
-    @staticmethod
-    def _align_volume_inputs(images, targets):
-        """-> (images, targets) as contiguous float32, shapes checked"""
-        a = np.ascontiguousarray(images.detach().cpu().numpy() if _is_torch(images) else images, dtype=np.float32)
-        t = np.ascontiguousarray(targets.detach().cpu().numpy() if _is_torch(targets) else targets, dtype=np.float32)
-        if a.ndim != 3:
-            raise ValueError(f"expected a stack of (n, H, W) images, got {a.shape}")
-        if t.ndim != 3:
-            raise ValueError(f"expected targets of shape (m, th, tw), got {t.shape}")
-        return a, t
-
-    def align_volume_cost(self, images, targets, maps, *, warped=False, gradient=False):
-        """images (n, Hh, Ww), n >= 2, targets (m, th, tw), maps (m, 9) -> ``align_volume.AlignResultV``: every target's lattice read in the stack
-        as a volume under its own 3 x 3 map (``align_volume.map_points3``: pixel (i, j) at Z = z0 i + z1 j + tz in slice units, Y = y0 i + y1 j + ty,
-        X = x0 i + x1 j + tx in reconstruction pixels) and scored against the target on the device -- ``count``, ``cost`` = sum (R - T)^2, ``grad``
-        (m, 9), ``jtj`` (m, 9, 9); R and its gradient are the bits of ``resample_volume_with_gradient`` (build-defined, DESIGN.md section 5.13;
-        msiren_align_volume).  m is independent of n.  ``warped`` / ``gradient``: also return R (m, th, tw) / (gZ, gY, gX) (3, m, th, tw)."""
-        from . import align_volume as av
-
-        self._ensure_committed()
-        a, t = self._align_volume_inputs(images, targets)
-        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        n, Hh, Ww = a.shape
-        m, th, tw = t.shape
-        if mp.shape != (m, 9):
-            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
-        sums = np.zeros((m, av.SUMS_V), np.float64)
-        w = np.full((m, th, tw), np.nan, np.float32) if warped else None
-        g = np.full((3, m, th, tw), np.nan, np.float32) if gradient else None
-        _lib.check(self._lib.msiren_align_volume(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, mp.ctypes.data, sums.ctypes.data,
-                                                 w.ctypes.data if warped else None, g.ctypes.data if gradient else None))
-        return av.unpack_v(sums, w, g)
-
-    def _align_volume_solve(self, images, targets, mode, maps, planes, rigid, spacing, iterations, damping, down, up, lam_min, lam_max, trace):
-        from . import align, align_volume as av
-
-        self._ensure_committed()
-        a, t = self._align_volume_inputs(images, targets)
-        n, Hh, Ww = a.shape
-        m, th, tw = t.shape
-        if mode == align.AFFINE and maps.shape != (m, 9):
-            raise ValueError(f"expected maps of shape ({m}, 9), got {maps.shape}")
-        if mode == align.RIGID and (planes.shape != (m, 12) or rigid.shape != (m, 12)):
-            raise ValueError(f"expected planes and states of shape ({m}, 12), got {planes.shape} and {rigid.shape}")
-        o = _lib.AlignVolumeSolveOpts(C.sizeof(_lib.AlignVolumeSolveOpts), mode, int(iterations), 0, float(damping), float(down), float(up), float(lam_min),
-                                      float(lam_max), float(spacing))
-        is_rigid = mode == align.RIGID
-        out = np.zeros((m, 9), np.float32) if is_rigid else maps.copy()
-        rout = rigid.copy() if is_rigid else None
-        report = np.zeros((m, 6), np.float64)
-        tr = np.zeros((max(int(iterations), 0), m, 11), np.float64) if trace else None
-        _lib.check(self._lib.msiren_align_volume_solve(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), None if is_rigid else maps.ctypes.data,
-                                                       planes.ctypes.data if is_rigid else None, rigid.ctypes.data if is_rigid else None, out.ctypes.data,
-                                                       rout.ctypes.data if is_rigid else None, report.ctypes.data, tr.ctypes.data if trace else None))
-        return av.solve_result_v(out, rout, report, tr)
-
-    def align_volume_solve(self, images, targets, maps, *, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
-        """images (n, Hh, Ww), targets (m, th, tw), maps (m, 9) -> ``align_volume.SolveResultV``: every target aligned to the volume over the nine
-        parameters of its map, on the device -- ``align_volume_cost``'s prologue once, then ``iterations`` evaluations with ``align_solve``'s
-        Levenberg-Marquardt step behind each, no host synchronisation (build-defined; msiren_align_volume_solve).  Bit for
-        bit what ``align_volume.solve_on_host_v`` gives around ``align_volume_cost``.  ``trace``: (iterations, m, 11)."""
-        from . import align
-
-        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        return self._align_volume_solve(images, targets, align.AFFINE, mp, None, None, 1.0, iterations, damping, down, up, lam_min, lam_max, trace)
-
-    def align_volume_solve_rigid(self, images, targets, planes, spacing, *, rotation=None, shift=None, iterations=12, damping=1e-3, down=0.1, up=10.0,
-                                 lam_min=1e-9, lam_max=1e9, trace=False):
-        """As ``align_volume_solve`` over a rigid motion of every target's nominal plane in physical space (6 parameters): ``planes`` (m, 12)
-        float64 = (e_i, e_j, o, c), the lattice's two step vectors, its origin and the rotation centre as (Z, Y, X) triples in pixel units; slices are
-        ``spacing`` pixels apart.  Starts at ``rotation`` (m, 3, 3) (None: the identity) and ``shift`` (m, 3) (None: zero); every trial map is
-        ``align_volume.rigid_maps3`` of the state (msiren_align_volume_solve, mode 1).  ``rotation`` and ``shift`` of the result are the best state's."""
-        from . import align
-
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
-        m = len(pl)
-        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (m, 3, 3)).reshape(m, 9)
-        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (m, 3))
-        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
-        return self._align_volume_solve(images, targets, align.RIGID, None, pl, rigid, spacing, iterations, damping, down, up, lam_min, lam_max, trace)
-
-    @staticmethod
-    def _align_volume_w_inputs(images, targets, weights, intensity):
-        """-> (images, targets, weights or None, intensity or None) as contiguous float32, shapes checked"""
-        a, t = ModulatedSiren._align_volume_inputs(images, targets)
-        w = None if weights is None else _f32(weights)
-        if w is not None and w.shape != t.shape:
-            raise ValueError(f"expected weights of shape {t.shape}, got {w.shape}")
-        gb = None if intensity is None else _f32(intensity)
-        if gb is not None and gb.shape != (t.shape[0], 2):
-            raise ValueError(f"expected intensity of shape ({t.shape[0]}, 2), got {gb.shape}")
-        return a, t, w, gb
-
-    def align_volume_cost_w(self, images, targets, maps, *, weights=None, intensity=None, warped=False, gradient=False):
-        """``align_volume_cost`` with a per-pixel weight and a per-target gain and bias -> ``align_volume.AlignResultVW``: ``weights`` (m, th, tw)
-        or None (all 1; a weight that is zero, negative or not finite masks its pixel), ``intensity`` (m, 2) = (g, b) or None ((1, 0)); ``cost`` =
-        sum w (g R + b - T)^2 over the valid pixels, ``wsum`` their weights, ``grad`` (m, 11) and ``jtj`` (m, 11, 11) over the map's nine
-        parameters, then g, b (build-defined; msiren_align_volume_w).  Without weights and intensity the shared entries
-        are ``align_volume_cost``'s bits.  ``warped`` / ``gradient`` return R and (gZ, gY, gX) before gain and bias."""
-        from . import align_volume as av
-
-        self._ensure_committed()
-        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
-        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        n, Hh, Ww = a.shape
-        m, th, tw = t.shape
-        if mp.shape != (m, 9):
-            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
-        sums = np.zeros((m, av.SUMS_VW), np.float64)
-        wp = np.full((m, th, tw), np.nan, np.float32) if warped else None
-        g = np.full((3, m, th, tw), np.nan, np.float32) if gradient else None
-        _lib.check(self._lib.msiren_align_volume_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, mp.ctypes.data, None if w is None else w.ctypes.data,
-                                                   None if gb is None else gb.ctypes.data, sums.ctypes.data, wp.ctypes.data if warped else None,
-                                                   g.ctypes.data if gradient else None))
-        return av.unpack_vw(sums, wp, g)
-
-    def _align_volume_solve_w(self, images, targets, mode, maps, planes, rigid, spacing, weights, intensity, estimate_intensity, iterations, damping, down, up, lam_min,
-                              lam_max, trace):
-        from . import align, align_volume as av
-
-        self._ensure_committed()
-        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
-        n, Hh, Ww = a.shape
-        m, th, tw = t.shape
-        if mode == align.AFFINE and maps.shape != (m, 9):
-            raise ValueError(f"expected maps of shape ({m}, 9), got {maps.shape}")
-        if mode == align.RIGID and (planes.shape != (m, 12) or rigid.shape != (m, 12)):
-            raise ValueError(f"expected planes and states of shape ({m}, 12), got {planes.shape} and {rigid.shape}")
-        o = _lib.AlignVolumeSolveWOpts(C.sizeof(_lib.AlignVolumeSolveWOpts), mode, int(iterations), av.ESTIMATE if estimate_intensity else av.FIXED, float(damping),
-                                       float(down), float(up), float(lam_min), float(lam_max), float(spacing))
-        is_rigid = mode == align.RIGID
-        out = np.zeros((m, 9), np.float32) if is_rigid else maps.copy()
-        gout = np.tile(np.array([1.0, 0.0], np.float32), (m, 1)) if gb is None else gb.copy()
-        rout = rigid.copy() if is_rigid else None
-        report = np.zeros((m, 7), np.float64)
-        tr = np.zeros((max(int(iterations), 0), m, 14), np.float64) if trace else None
-        _lib.check(self._lib.msiren_align_volume_solve_w(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), None if is_rigid else maps.ctypes.data,
-                                                         planes.ctypes.data if is_rigid else None, rigid.ctypes.data if is_rigid else None,
-                                                         None if w is None else w.ctypes.data, None if gb is None else gb.ctypes.data, out.ctypes.data,
-                                                         gout.ctypes.data, rout.ctypes.data if is_rigid else None, report.ctypes.data,
-                                                         tr.ctypes.data if trace else None))
-        return av.solve_result_vw(out, gout, rout, report, tr)
-
-    def align_volume_solve_w(self, images, targets, maps, *, weights=None, intensity=None, estimate_intensity=True, iterations=12, damping=1e-3, down=0.1, up=10.0,
-                             lam_min=1e-9, lam_max=1e9, trace=False):
-        """``align_volume_solve`` on ``align_volume_cost_w`` -> ``align_volume.SolveResultVW``: every pixel weighted by ``weights`` (m, th, tw), the
-        target modelled as g R + b per target from ``intensity`` (m, 2) (None: (1, 0)).  ``estimate_intensity``: (g, b) are solved for together
-        with the map (11 parameters); False: they stay at their inputs (9).  The accept / reject rule compares cost / wsum (build-defined,
-        DESIGN.md section 5.14; msiren_align_volume_solve_w); bit for bit what ``align_volume.solve_on_host_vw`` gives around
-        ``align_volume_cost_w``.  ``trace``: (iterations, m, 14)."""
-        from . import align
-
-        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        return self._align_volume_solve_w(images, targets, align.AFFINE, mp, None, None, 1.0, weights, intensity, estimate_intensity, iterations, damping, down, up,
-                                          lam_min, lam_max, trace)
-
-    def align_volume_solve_rigid_w(self, images, targets, planes, spacing, *, rotation=None, shift=None, weights=None, intensity=None, estimate_intensity=True,
-                                   iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
-        """As ``align_volume_solve_w`` over a rigid motion of every target's nominal plane (``align_volume_solve_rigid``'s arguments): 8 parameters
-        with the intensity, 6 without."""
-        from . import align
-
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
-        m = len(pl)
-        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (m, 3, 3)).reshape(m, 9)
-        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (m, 3))
-        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
-        return self._align_volume_solve_w(images, targets, align.RIGID, None, pl, rigid, spacing, weights, intensity, estimate_intensity, iterations, damping, down, up,
-                                          lam_min, lam_max, trace)
-
-    def align_volume_solve_group(self, images, targets, planes, spacing, groups, *, rotation=None, shift=None, weights=None, intensity=None, estimate_intensity=True,
-                                 iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
-        """``align_volume_solve_rigid_w`` for GROUPS of consecutive targets that moved together (stacks, interleaves): one rigid state per group, every
-        target with its own plane, weights and intensity -> ``align_group.SolveResultG``.  ``groups``: the (G + 1) offsets into the targets (first 0,
-        last m, strictly ascending) or a list of G group sizes.  ``rotation`` (G, 3, 3) (None: the identity) and ``shift`` (G, 3) (None: zero) are per
-        group.  A group is accepted or rejected on sum cost / sum wsum over its members; with ``estimate_intensity`` every member's (g, b) is solved
-        for jointly with the group's motion (6 + 2 size parameters, the 2 x 2 blocks eliminated exactly), a member without valid pixels is placed by
-        the others (build-defined; msiren_align_volume_solve_group); bit for bit what ``align_group.solve_on_host_g`` gives
-        around ``align_volume_cost_w``.  One PHYSICAL motion per group needs the same centre c in every member's plane (e_i, e_j, o, c): the state
-        moves a point p of a member to Rot (p - c) + c + shift with that member's c; the call does not check it.  ``trace``: (iterations, G, 15)."""
-        from . import align_group as ag, align_volume as av
-
-        self._ensure_committed()
-        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
-        n, Hh, Ww = a.shape
-        m, th, tw = t.shape
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
-        if pl.shape != (m, 12):
-            raise ValueError(f"expected planes of shape ({m}, 12), got {pl.shape}")
-        gs = np.ascontiguousarray(ag.group_offsets(groups, m), dtype=np.int32)
-        G = len(gs) - 1
-        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (G, 3, 3)).reshape(G, 9)
-        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (G, 3))
-        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
-        o = _lib.AlignVolumeSolveGroupOpts(C.sizeof(_lib.AlignVolumeSolveGroupOpts), int(iterations), av.ESTIMATE if estimate_intensity else av.FIXED, 0, float(damping),
-                                           float(down), float(up), float(lam_min), float(lam_max), float(spacing))
-        out = np.zeros((m, 9), np.float32)
-        gout = np.tile(np.array([1.0, 0.0], np.float32), (m, 1)) if gb is None else gb.copy()
-        rout, report, trep = rigid.copy(), np.zeros((G, 7), np.float64), np.zeros((m, 3), np.float64)
-        tr = np.zeros((max(int(iterations), 0), G, 15), np.float64) if trace else None
-        _lib.check(self._lib.msiren_align_volume_solve_group(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), gs.ctypes.data, G, pl.ctypes.data,
-                                                             rigid.ctypes.data, None if w is None else w.ctypes.data, None if gb is None else gb.ctypes.data,
-                                                             out.ctypes.data, gout.ctypes.data, rout.ctypes.data, report.ctypes.data, trep.ctypes.data,
-                                                             tr.ctypes.data if trace else None))
-        return ag.solve_result_g(out, gout, rout, report, trep, tr)
-
-    def align_volume_cost_r(self, images, targets, maps, scale, *, weights=None, intensity=None, warped=False, gradient=False, rweight=False):
-        """``align_volume_cost_w`` under a robust (Geman-McClure) loss -> ``align_robust.AlignResultR``: ``scale`` a scalar or (m,), s = (c sigma)^2 in
-        squared intensity units; ``cost`` = sum w r^2 / (1 + r^2 / s) over the valid pixels, ``grad`` its exact gradient, ``jtj`` the majoriser's
-        Gauss-Newton matrix, ``wsum`` the plain sum of the weights (build-defined; msiren_align_volume_r).  A target whose
-        scale is not > 0 has count 0; with scale +inf the sums are ``align_volume_cost_w``'s bits.  ``rweight``: (m, th, tw) float32, the factor
-        1 / (1 + r^2 / s)^2 of every valid pixel (towards 0: rejected), NaN elsewhere."""
-        from . import align_robust as ar, align_volume as av
-
-        self._ensure_committed()
-        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
-        mp = np.ascontiguousarray(maps.detach().cpu().numpy() if _is_torch(maps) else maps, dtype=np.float32)
-        n, Hh, Ww = a.shape
-        m, th, tw = t.shape
-        if mp.shape != (m, 9):
-            raise ValueError(f"expected maps of shape ({m}, 9), got {mp.shape}")
-        s = ar.scales(scale, m)
-        sums = np.zeros((m, av.SUMS_VW), np.float64)
-        wp = np.full((m, th, tw), np.nan, np.float32) if warped else None
-        g = np.full((3, m, th, tw), np.nan, np.float32) if gradient else None
-        rw = np.full((m, th, tw), np.nan, np.float32) if rweight else None
-        _lib.check(self._lib.msiren_align_volume_r(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, mp.ctypes.data, None if w is None else w.ctypes.data,
-                                                   None if gb is None else gb.ctypes.data, s.ctypes.data, sums.ctypes.data, wp.ctypes.data if warped else None,
-                                                   g.ctypes.data if gradient else None, rw.ctypes.data if rweight else None))
-        return ar.unpack_r(sums, wp, g, rw)
-
-    def align_volume_solve_group_robust(self, images, targets, planes, spacing, groups, scale, *, rotation=None, shift=None, weights=None, intensity=None,
-                                        estimate_intensity=True, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
-        """``align_volume_solve_group`` on ``align_volume_cost_r``: targets whose bad pixels come without a mask -> ``align_group.SolveResultG``.
-        ``scale`` a scalar or (m,), fixed for the call (``align_robust.scale_from`` gives one from a quadratic pass); every other argument, the step
-        rule and the result are ``align_volume_solve_group``'s, ``cost`` and the means the robust loss (build-defined, DESIGN.md section 5.16;
-        msiren_align_volume_solve_group_r); bit for bit what ``align_robust.solve_on_host_r`` gives around ``align_volume_cost_r``.  Groups of one
-        target each: the robust rigid solve per target.  With scale +inf: ``align_volume_solve_group``'s bits."""
-        from . import align_group as ag, align_robust as ar, align_volume as av
-
-        self._ensure_committed()
-        a, t, w, gb = self._align_volume_w_inputs(images, targets, weights, intensity)
-        n, Hh, Ww = a.shape
-        m, th, tw = t.shape
-        pl = np.ascontiguousarray(np.asarray(planes, dtype=np.float64).reshape(-1, 12))
-        if pl.shape != (m, 12):
-            raise ValueError(f"expected planes of shape ({m}, 12), got {pl.shape}")
-        s = ar.scales(scale, m)
-        gs = np.ascontiguousarray(ag.group_offsets(groups, m), dtype=np.int32)
-        G = len(gs) - 1
-        rot = np.broadcast_to(np.eye(3) if rotation is None else np.asarray(rotation, dtype=np.float64), (G, 3, 3)).reshape(G, 9)
-        sh = np.broadcast_to(np.zeros(3) if shift is None else np.asarray(shift, dtype=np.float64), (G, 3))
-        rigid = np.ascontiguousarray(np.concatenate([rot, sh], axis=1))
-        o = _lib.AlignVolumeSolveGroupOpts(C.sizeof(_lib.AlignVolumeSolveGroupOpts), int(iterations), av.ESTIMATE if estimate_intensity else av.FIXED, 0, float(damping),
-                                           float(down), float(up), float(lam_min), float(lam_max), float(spacing))
-        out = np.zeros((m, 9), np.float32)
-        gout = np.tile(np.array([1.0, 0.0], np.float32), (m, 1)) if gb is None else gb.copy()
-        rout, report, trep = rigid.copy(), np.zeros((G, 7), np.float64), np.zeros((m, 3), np.float64)
-        tr = np.zeros((max(int(iterations), 0), G, 15), np.float64) if trace else None
-        _lib.check(self._lib.msiren_align_volume_solve_group_r(self._h, a.ctypes.data, n, Hh, Ww, t.ctypes.data, m, th, tw, C.byref(o), gs.ctypes.data, G, pl.ctypes.data,
-                                                               rigid.ctypes.data, None if w is None else w.ctypes.data, None if gb is None else gb.ctypes.data,
-                                                               s.ctypes.data, out.ctypes.data, gout.ctypes.data, rout.ctypes.data, report.ctypes.data, trep.ctypes.data,
-                                                               tr.ctypes.data if trace else None))
-        return ag.solve_result_g(out, gout, rout, report, trep, tr)
-
-    def fuse_targets(self, targets, maps, shape, spacing, *, thickness=None, weights=None, intensity=None, min_coverage=0.0, coverage=False):
-        """The aligned targets put back onto the stack's voxel grid -> ``fuse.FuseResult``: targets (m, th, tw), ``maps`` (m, 9) and ``intensity``
-        (m, 2) or None exactly the ``.maps`` and ``.intensity`` of any ``SolveResultV`` / ``VW`` / ``G``, ``shape`` = (n, H, W) the output grid,
-        ``spacing`` pixels per slice, ``thickness`` the half-width in pixels of the quadratic through-plane window (None: ``spacing``), ``weights``
-        (m, th, tw) or None (all 1; a weight that is zero, negative or not finite, and a pixel that is not finite, leave their tap out).  Every voxel
-        is the normalised sum of window x bilinear weight x pixel weight x (T - b) / g over the targets that reach it, NaN where that coverage is
-        not above ``min_coverage``; ``coverage``: return it too (build-defined; msiren_fuse_targets); bit for bit what
-        ``fuse.fuse_on_host`` gives.  The robust call's ``rweight`` may be multiplied into ``weights`` to keep rejected pixels out of the stack.  No
-        images and no weights of the model are involved: the result can go back into ``reconstruct`` / ``align_volume_*`` as ``images``."""
-        from . import fuse
-
-        self._ensure_handle()
-        t, mp, w, gb = _target_inputs(targets, maps, weights, intensity, None)
-        m, th, tw = t.shape
-        if len(shape) != 3:
-            raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
-        n, Hh, Ww = (int(s) for s in shape)
-        o = _lib.FuseOpts(C.sizeof(_lib.FuseOpts), 0, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage))
-        ok = n > 0 and Hh > 0 and Ww > 0  # (the library refuses the others: nothing is allocated for them here)
-        vol = np.full((n, Hh, Ww) if ok else (0, 0, 0), np.nan, np.float32)
-        cov = np.zeros(vol.shape, np.float32) if coverage else None
-        flags = np.zeros(m, np.int32)
-        _lib.check(self._lib.msiren_fuse_targets(self._h, _ptr(t, m), m, th, tw, _ptr(mp, m), _ptr(w, m), _ptr(gb, m), C.byref(o), n, Hh, Ww, vol.ctypes.data,
-                                                 cov.ctypes.data if coverage else None, _ptr(flags, m)))
-        return fuse.FuseResult(vol, cov, flags)
-
-    def project_volume(self, volume, maps, shape, spacing, *, thickness=None, intensity=None, min_coverage=0.0, targets=None, weights=None, coverage=False,
-                       residual=False, stats=False):
-        """The way back from ``fuse_targets`` -> ``fuse.ProjectResult``: the stack ``volume`` (n, H, W) gathered onto the lattices ``shape`` = (th, tw)
-        of the m targets of ``maps`` (m, 9), with exactly the weights of the fusion (``spacing``, ``thickness``, ``intensity``, ``min_coverage`` as
-        there): ``simulated`` is what each target should look like given the stack, g R + b of the normalised sum, NaN where the ``coverage`` (returned
-        on request) is not above ``min_coverage``.  With ``targets`` (m, th, tw) and ``weights`` (m, th, tw) or None (all 1): ``residual`` = targets -
-        simulated and ``stats`` (m, 4) = (count, sum w, sum w r, sum (w r) r) per target, on request (build-defined, DESIGN.md section 5.18;
-        msiren_project_volume); bit for bit what ``fuse.project_on_host`` and ``fuse.project_stats_on_host`` give.  No images and no weights of the
-        model are involved."""
-        from . import fuse
-
-        self._ensure_handle()
-        vol, mp = _f32(volume), _f32(maps)
-        if vol.ndim != 3:
-            raise ValueError(f"expected volume (n, H, W), got shape {vol.shape}")
-        if mp.ndim != 2 or mp.shape[1] != 9:
-            raise ValueError(f"expected maps of shape (m, 9), got {mp.shape}")
-        if len(shape) != 2:
-            raise ValueError(f"expected shape = (th, tw), got {shape!r}")
-        m, (th, tw) = len(mp), (int(s) for s in shape)
-        if targets is None and (weights is not None or residual or stats):
-            raise ValueError("weights, residual and stats need targets")
-        t, mp, w, gb = _target_inputs(targets, mp, weights, intensity, (m, th, tw))
-        n, Hh, Ww = vol.shape
-        o = _lib.FuseOpts(C.sizeof(_lib.FuseOpts), 0, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage))
-        ok = th > 0 and tw > 0  # (the library refuses the others: nothing is allocated for them here)
-        sim = np.full((m, th, tw) if ok else (m, 0, 0), np.nan, np.float32)
-        cov = np.zeros(sim.shape, np.float32) if coverage else None
-        res = np.full(sim.shape, np.nan, np.float32) if residual else None
-        st = np.zeros((m, 4), np.float64) if stats else None
-        flags = np.zeros(m, np.int32)
-
-        _lib.check(self._lib.msiren_project_volume(self._h, vol.ctypes.data if vol.size else None, n, Hh, Ww, _ptr(mp, m), _ptr(gb, m), C.byref(o), m, th, tw, _ptr(t, m), _ptr(w, m), _ptr(sim, m),
-                                                   _ptr(cov, m), _ptr(res, m), _ptr(st, m), _ptr(flags, m)))
-        return fuse.ProjectResult(sim, cov, res, st, flags)
-
-    def solve_volume(self, targets, maps, shape, spacing, *, iterations, lam=0.0, thickness=None, weights=None, intensity=None, min_coverage=0.0, start=None,
-                     coverage=False, history=False):
-        """The stack that best explains all aligned targets at once -> ``solve_volume.SolveVolumeResult``: ``iterations`` steps of conjugate gradients,
-        in one device call, on 1/2 sum w g g (tau - P x)^2 + 1/2 ``lam`` sum over the 6-neighbour edges of c (x_u - x_v)^2, with P ``project_volume``'s
-        row-normalised gather, tau = (T - b) / g, and c = 1 in plane, 1 / spacing^2 through plane.  targets, maps, shape = (n, H, W), spacing,
-        thickness, weights, intensity and min_coverage as in ``fuse_targets``; ``start`` (n, H, W) or None: the fusion.  The support is the finite
-        voxels of the start; the volume is NaN elsewhere.  ``coverage``: the fusion's coverage too; ``history``: (iterations + 1, 2) = (<r, r>,
-        <p, A p>) per iteration too.  ``stopped_at``: the iteration at which the solve broke down (rho == 0, or gamma not finite or not > 0), else -1.
-        Build-defined (msiren_solve_volume); bit for bit what ``solve_volume.solve_volume_on_host`` gives.  No images and no
-        weights of the model are involved."""
-        from . import solve_volume as sv
-
-        self._ensure_handle()
-        t, mp, w, gb = _target_inputs(targets, maps, weights, intensity, None)
-        m, th, tw = t.shape
-        if len(shape) != 3:
-            raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
-        n, Hh, Ww = (int(s) for s in shape)
-        st = None if start is None else _f32(start)
-        if st is not None and st.shape != (n, Hh, Ww):
-            raise ValueError(f"expected start of shape {(n, Hh, Ww)}, got {st.shape}")
-        iterations = int(iterations)
-        o = _lib.SolveOpts(C.sizeof(_lib.SolveOpts), iterations, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage), float(lam))
-        ok = n > 0 and Hh > 0 and Ww > 0  # (the library refuses the others: nothing is allocated for them here)
-        vol = np.full((n, Hh, Ww) if ok else (0, 0, 0), np.nan, np.float32)
-        cov = np.zeros(vol.shape, np.float32) if coverage else None
-        hist = np.full((max(iterations, 0) + 1, 2), np.nan, np.float64) if history else None
-        flags = np.zeros(m, np.int32)
-        stopped = np.full(1, -1, np.int32)
-
-        _lib.check(self._lib.msiren_solve_volume(self._h, _ptr(t, m), m, th, tw, _ptr(mp, m), _ptr(w, m), _ptr(gb, m), C.byref(o), n, Hh, Ww, st.ctypes.data if st is not None and st.size else None,
-                                                 vol.ctypes.data, cov.ctypes.data if coverage else None, hist.ctypes.data if history else None, _ptr(flags, m), stopped.ctypes.data))
-        return sv.SolveVolumeResult(vol, cov, hist, flags, int(stopped[0]))
-
-    def solve_volume_robust(self, targets, maps, shape, spacing, scale, *, rounds, iterations, anneal=1.0, lam=0.0, thickness=None, weights=None, intensity=None,
-                            min_coverage=0.0, start=None, coverage=False, history=False, rweight=False, stats=False):
-        """``solve_volume`` with outlier rejection -> ``solve_volume_robust.SolveVolumeRobustResult``: ``rounds`` reweighting rounds in one device
-        call.  Each round recomputes every pixel's Geman-McClure weight omega = 1 / (1 + e^2 / s)^2 from the residual e = T - (g P x + b) of the
-        current iterate and runs ``iterations`` steps of ``solve_volume``'s conjugate gradients on the reweighted normal equations, warm-started from
-        x in fp64.  ``scale`` a scalar or (m,), (c sigma)^2 in squared target-intensity units as in ``align_volume_cost_r`` (+inf: the quadratic
-        loss); the scale of round t is ``scale`` x ``anneal``^(rounds - 1 - t): a graduated schedule that ends on ``scale``.  Every other argument as
-        in ``solve_volume``.  ``history``: (rounds, iterations + 1, 2) too; ``rweight``: the final omega per pixel (m, th, tw), NaN where the pixel
-        takes no part; ``stats``: (m, 4) = (count, sum w, sum w omega, sum w om e^2) per target -- sum w omega / sum w tells the rejected slices.
-        ``stopped_at`` (rounds,): per round the iteration at which it broke down, else -1.  Build-defined (DESIGN.md section 5.20;
-        msiren_solve_volume_r); bit for bit what ``solve_volume_robust.solve_volume_robust_on_host`` gives.  With rounds = 1 and scale +inf:
-        ``solve_volume``'s bits.  No images and no weights of the model are involved."""
-        from . import align_robust as ar, solve_volume_robust as svr
-
-        self._ensure_handle()
-        t, mp, w, gb = _target_inputs(targets, maps, weights, intensity, None)
-        m, th, tw = t.shape
-        if len(shape) != 3:
-            raise ValueError(f"expected shape = (n, H, W), got {shape!r}")
-        n, Hh, Ww = (int(s) for s in shape)
-        st = None if start is None else _f32(start)
-        if st is not None and st.shape != (n, Hh, Ww):
-            raise ValueError(f"expected start of shape {(n, Hh, Ww)}, got {st.shape}")
-        s = ar.scales(scale, m)
-        rounds, iterations = int(rounds), int(iterations)
-        o = _lib.SolveROpts(C.sizeof(_lib.SolveROpts), iterations, rounds, 0, float(spacing), float(spacing if thickness is None else thickness), float(min_coverage),
-                            float(lam), float(anneal))
-        ok = n > 0 and Hh > 0 and Ww > 0  # (the library refuses the others: nothing is allocated for them here)
-        vol = np.full((n, Hh, Ww) if ok else (0, 0, 0), np.nan, np.float32)
-        cov = np.zeros(vol.shape, np.float32) if coverage else None
-        nr = min(max(rounds, 0), 64)  # (the library refuses the others)
-        hist = np.full((nr, max(iterations, 0) + 1, 2), np.nan, np.float64) if history else None
-        flags = np.zeros(m, np.int32)
-        stopped = np.full(nr, -1, np.int32)
-        rw = np.full(t.shape, np.nan, np.float32) if rweight else None
-        sts = np.zeros((m, 4), np.float64) if stats else None
-
-        _lib.check(self._lib.msiren_solve_volume_r(self._h, _ptr(t, m), m, th, tw, _ptr(mp, m), _ptr(w, m), _ptr(gb, m), _ptr(s, m), C.byref(o), n, Hh, Ww,
-                                                   st.ctypes.data if st is not None and st.size else None, vol.ctypes.data, cov.ctypes.data if coverage else None,
-                                                   _ptr(hist, nr), _ptr(flags, m), _ptr(stopped, nr), _ptr(rw, m), _ptr(sts, m)))
-        return svr.SolveVolumeRobustResult(vol, cov, hist, flags, stopped, rw, sts)
 
     def reconstruct_with_gradient(self, images, out_stride=None):
         """images (n, Hh, Ww) or (Hh, Ww) -> (recon (n, nV*I', nH*I'), grad (2, n, nV*I', nH*I')): ``reconstruct`` on the exact-fp32 trunk
