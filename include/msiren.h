@@ -45,7 +45,9 @@ extern "C" {
  * msiren_fuse_targets(_dev) and msiren_fuse_opts (aligned target slices gathered back onto the stack's voxel grid); msiren_project_volume(_dev) (the
  * way back: a stack gathered onto the targets' lattices with the same weights, with the residual against given targets and four sums per target);
  * msiren_solve_volume(_dev) and msiren_solve_opts (the stack that best explains all targets: regularised conjugate gradients on those two operators);
- * msiren_solve_volume_r(_dev) and msiren_solve_r_opts (rounds of that solve, reweighted by a Geman-McClure loss with one annealed scale per target).
+ * msiren_solve_volume_r(_dev) and msiren_solve_r_opts (rounds of that solve, reweighted by a Geman-McClure loss with one annealed scale per target);
+ * msiren_align_stack_r(_dev) and msiren_align_stack_solve_group_r(_dev) (the robust volume cost and the grouped solve against a plain voxel stack read
+ * trilinearly: no images, no trunk, no weights).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -819,6 +821,63 @@ MSIREN_API int msiren_align_volume_solve_group_r_dev(msiren_handle h, const floa
                                                      float* intensity_out_dev /* (m, 2) */, double* rigid_out_dev /* (G, 12) or NULL */,
                                                      double* report_dev /* (G, 7) */, double* target_report_dev /* (m, 3) or NULL */,
                                                      double* trace_dev /* (iterations, G, 15) or NULL */);
+
+/* Build-defined: msiren_align_volume_r and msiren_align_volume_solve_group_r against a stack that is JUST VOXELS -- what
+ * msiren_fuse_targets and the msiren_solve_volume* calls return -- instead of the stack the network reconstructs.  No images, no prologue, no
+ * trunk, no committed weights: the handle alone.  This is the registration step of the outer loop reconstruct -> register -> reconstruct.
+ *     stack (n, height, width) float32, n, height, width >= 2;  targets (m, th, tw), maps (m, 9), weights, intensity, scale, sums, warped,
+ *     wgrad (3, m, th, tw), rweight exactly as in msiren_align_volume_r (the same map convention: Z in slice units, (Y, X) in pixels)
+ * The point (Z, Y, X) of pixel (i, j) is msiren_align_volume's, in fp32.  The read is trilinear, in fp64 from the fp32 numbers, + - * only, one
+ * rounding per operation, no fused multiply-add, in exactly this association.  A point is INSIDE iff 0 <= Z <= n - 1, 0 <= Y <= height - 1 and
+ * 0 <= X <= width - 1, compared in fp32 (the bounds are exact integers; a NaN fails):
+ *     z0 = min((int)floorf(Z), n - 2)    fz = (double)Z - z0    az = 1.0 - fz        (y0, fy, ay and x0, fx, ax likewise with height, width)
+ *     V[dz][dy][dx] = (double)stack[z0 + dz, y0 + dy, x0 + dx]
+ *     c[dz][dy] = (ax V[dz][dy][0]) + (fx V[dz][dy][1])        dx_[dz][dy] = V[dz][dy][1] - V[dz][dy][0]
+ *     e[dz] = (ay c[dz][0]) + (fy c[dz][1])    ex[dz] = (ay dx_[dz][0]) + (fy dx_[dz][1])    ey[dz] = c[dz][1] - c[dz][0]
+ *     R  = (float)((az e[0]) + (fz e[1]))      gX = (float)((az ex[0]) + (fz ex[1]))
+ *     gY = (float)((az ey[0]) + (fz ey[1]))    gZ = (float)(e[1] - e[0])
+ * A point outside gives NaN in all four.  A corner that is not finite is NOT special-cased: it makes the values non-finite through the arithmetic
+ * (0 x NaN included), so a pixel needs all eight corners finite -- on a stack with NaN holes (outside the support of msiren_solve_volume*) a pixel
+ * counts only where its whole cell is known.  At the upper faces the last cell is read with f = 1 (msiren_resample_volume's convention for Z).  The
+ * gradient is the derivative of the interpolant inside the cell that was read (gZ per slice, gY, gX per pixel).
+ * From (R, gZ, gY, gX) on the rule is msiren_align_volume_r's word for word: validity (s > 0 included), (g, b), J[11], the robust factors, the 80
+ * sums, their layout and summation order.  scale = +inf is the weighted square loss.  warped = R, wgrad = (gZ, gY, gX), rweight as there.
+ * mri_inr_amd/align_stack.py restates the call in Python floats and gives the same bits.
+ * msiren_align_stack_solve_group_r: msiren_align_volume_solve_group_r's loop, options, outputs, report and trace, every evaluation being the call
+ * above -- `iterations` x (the reduce -> the grouped step stage), no host synchronisation.
+ * MSIREN_E_INVALID with a message that names the argument, before any launch: a negative extent; m th tw >= 2^28; with work to do, n, height or
+ * width < 2, n height width >= 2^30 or an extent above 2^24 - 1; a null stack, targets, maps, scale or sums (the solve: what
+ * msiren_align_volume_solve_group_r refuses of its options, groups and outputs); device pointers not aligned (4 bytes: float arrays, 8: double
+ * arrays).  m = 0 or th tw = 0 does nothing.  Works on a handle whose weights were never committed.  Under msiren_profile_enable:
+ * "align_stack_reduce_kernels" (partial and combine as one entry) once per evaluation, "align_group_step_kernels" behind each in the solve;
+ * nothing of the prologue or the trunk. */
+MSIREN_API int msiren_align_stack_r(msiren_handle h, const float* stack_host /* (n, height, width) */, int64_t n_slices, int32_t height, int32_t width,
+                                    const float* targets_host, int64_t m_targets, int32_t th, int32_t tw, const float* maps_host /* (m, 9) */,
+                                    const float* weights_host /* (m, th, tw) or NULL */, const float* intensity_host /* (m, 2) or NULL */,
+                                    const double* scale_host /* (m) */, double* sums_host /* (m, 80) */, float* warped_host /* or NULL */,
+                                    float* wgrad_host /* (3, m, th, tw) or NULL */, float* rweight_host /* (m, th, tw) or NULL */);
+MSIREN_API int msiren_align_stack_r_dev(msiren_handle h, const float* stack_dev, int64_t n_slices, int32_t height, int32_t width,
+                                        const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw, const float* maps_dev /* (m, 9) */,
+                                        const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */,
+                                        const double* scale_dev /* (m) */, double* sums_dev /* (m, 80) */, float* warped_dev /* or NULL */,
+                                        float* wgrad_dev /* or NULL */, float* rweight_dev /* or NULL */);
+MSIREN_API int msiren_align_stack_solve_group_r(msiren_handle h, const float* stack_host, int64_t n_slices, int32_t height, int32_t width,
+                                                const float* targets_host, int64_t m_targets, int32_t th, int32_t tw,
+                                                const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start /* host, (G + 1) */,
+                                                int64_t n_groups, const double* planes /* (m, 12) */, const double* rigid_in /* (G, 12) */,
+                                                const float* weights /* (m, th, tw) or NULL */, const float* intensity_in /* (m, 2) or NULL */,
+                                                const double* scale /* (m) */, float* maps_out /* (m, 9) */, float* intensity_out /* (m, 2) */,
+                                                double* rigid_out /* (G, 12) or NULL */, double* report /* (G, 7) */,
+                                                double* target_report /* (m, 3) or NULL */, double* trace /* (iterations, G, 15) or NULL */);
+MSIREN_API int msiren_align_stack_solve_group_r_dev(msiren_handle h, const float* stack_dev, int64_t n_slices, int32_t height, int32_t width,
+                                                    const float* targets_dev, int64_t m_targets, int32_t th, int32_t tw,
+                                                    const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start /* host, (G + 1) */,
+                                                    int64_t n_groups, const double* planes_dev /* (m, 12) */, const double* rigid_in_dev /* (G, 12) */,
+                                                    const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_in_dev /* (m, 2) or NULL */,
+                                                    const double* scale_dev /* (m) */, float* maps_out_dev /* (m, 9) */,
+                                                    float* intensity_out_dev /* (m, 2) */, double* rigid_out_dev /* (G, 12) or NULL */,
+                                                    double* report_dev /* (G, 7) */, double* target_report_dev /* (m, 3) or NULL */,
+                                                    double* trace_dev /* (iterations, G, 15) or NULL */);
 
 /* Build-defined: the aligned targets put back onto the stack's voxel grid -- a motion-corrected (n, H, W) stack from what the
  * volume alignment calls return.  No images, no trunk, no committed weights: a gather over the targets per output voxel.

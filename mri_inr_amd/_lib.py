@@ -258,6 +258,12 @@ PROTOTYPES = {
                                                     _vp, _vp, _vp, _vp, _vp]),
     "msiren_align_volume_solve_group_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
                                                         _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_stack_r": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_stack_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_stack_solve_group_r": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp]),
+    "msiren_align_stack_solve_group_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _i32, _i32, C.POINTER(AlignVolumeSolveGroupOpts), _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_fuse_targets": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp]),
     "msiren_fuse_targets_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp]),
     "msiren_project_volume": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, C.POINTER(FuseOpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

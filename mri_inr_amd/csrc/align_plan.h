@@ -11,6 +11,7 @@
 //     align, align-w    B = n nV nH    E = S = n th tw K       P = 0          R = n chunks, chunks = ceil(th tw / 1024), 29 / 47 sums
 //     align-volume      B = n nV nH    E = 2 M K, S = M K      P = M = m th tw, R = m chunks, 56 sums
 //     align-volume-w    align-volume's, with 80 sums (640 bytes per partial record)
+//     align-stack       no bins, entries, slots or points: the block starts with the partials, R = m chunks, 80 sums (stack_layout)
 // The memset in front of the count kernel covers counts and cursors: zero_bytes.  The limits keep every buffer of a call below 2^31 bytes and
 // every index in 32 bits; the bin scratch over the points and over the bins stays below 2^30 each.
 #pragma once
@@ -47,6 +48,14 @@ inline GeomLayout align_layout(int64_t NP, int64_t n, int64_t Mt, int K, int nsu
 }
 inline GeomLayout align_volume_layout(int64_t NP, int64_t m, int64_t Mt, int K, int nsums) {
     return geom_layout(NP, 2 * m * Mt * K, m * Mt * K, m * Mt, m * align_chunks(Mt), nsums);
+}
+
+// align-stack: a plain voxel stack is read, so there are no bins, entries, slots or points -- the block is the partial
+// records of `nsums` doubles at offset 0, and what follows them is the solve's (group_solve_layout).  Every other offset of the layout is 0 and unused.
+inline GeomLayout stack_layout(int64_t m, int64_t Mt, int nsums) {
+    GeomLayout l{};
+    l.total = (size_t)m * (size_t)align_chunks(Mt) * nsums * sizeof(double);
+    return l;
 }
 
 // A solve's state per unit (slice or target) behind `base` = GeomLayout::total, a multiple of 8: the doubles, then the 4-byte words.
@@ -116,6 +125,14 @@ inline bool align_pixels_fit(int64_t n, int64_t Mt, int K, int nsums) {
 // resample-volume's bytes over M = m th tw pixels and one record per chunk; the trunk's three planes are 24 M K bytes
 inline bool align_volume_pixels_fit(int64_t m, int64_t Mt, int K, int nsums) {
     return !(Mt > 0x0fffffffLL || m > 0x0fffffffLL || m * Mt > 0x0fffffffLL || 32 * m * Mt * K + 8 * m * Mt + 8 * nsums * m * align_chunks(Mt) > 0x3fffffffLL);
+}
+// align-stack: every extent is compared as an fp32 integer (below 2^24), a voxel's index stays below 2^30 and a pixel's below 2^28.  The arguments
+// are not negative.
+inline bool stack_voxels_fit(int64_t n, int64_t H, int64_t W) {
+    return !(n > 0x00ffffffLL || H > 0x00ffffffLL || W > 0x00ffffffLL || n * H > 0x3fffffffLL || n * H * W > 0x3fffffffLL);
+}
+inline bool stack_pixels_fit(int64_t m, int64_t th, int64_t tw) {
+    return !(m > 0x0fffffffLL || th * tw > 0x0fffffffLL || m * (th * tw) > 0x0fffffffLL);
 }
 
 }  // namespace msiren

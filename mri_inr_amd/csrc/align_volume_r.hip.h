@@ -13,8 +13,8 @@
 // cost is the weighted loss, dcost its exact gradient, jtj the majoriser's (IRLS) Gauss-Newton matrix, wsum the plain sum of the weights.  With
 // s = +inf: u = 0, v = om = 1, wl = wq = wd, and every term is align_volume_partial_w_kernel's term -- the same bits.
 // rweight (m, Mt) float32, optional: (float)(om om) at a valid pixel, NaN elsewhere (the outlier map).
-// The kernel's body is align_volume_partial_w_body<true> (align_volume_w.hip.h), shared with the weighted reduce; here are the robust factors it
-// calls and the kernel as a wrapper.
+// The kernel's body is align_volume_partial_w_body<true> (align_volume_w.hip.h), shared with the weighted reduce and, with another pixel source, with
+// align_stack_partial_r_kernel (align_stack.hip.h); here are the robust factors it calls and the kernel as a wrapper.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,8 +38,10 @@ __global__ __launch_bounds__(256) void align_volume_partial_r_kernel(const float
                                                                      const double* __restrict__ scale, float* __restrict__ warped, float* __restrict__ wgrad,
                                                                      float* __restrict__ rweight, double* __restrict__ partials, int m, int Mt, int tw, int K, int NPt,
                                                                      int T, int chunks) {
-    align_volume_partial_w_body<true>(vals, ent, tile, w, black, pair, fz, targets, weights, intensity, scale, warped, wgrad, rweight, partials, m, Mt, tw, K, NPt, T,
-                                      chunks);
+    const size_t M = (size_t)m * Mt;
+    align_volume_partial_w_body<true>(
+        [&](size_t gp, int, float* R, float* gZ, float* gY, float* gX) { align_volume_pixel(vals, ent, tile, w, black, pair, fz, warped, wgrad, gp, M, K, NPt, T, R, gZ, gY, gX); },
+        targets, weights, intensity, scale, rweight, partials, Mt, tw, chunks);
 }
 
 }  // namespace msiren

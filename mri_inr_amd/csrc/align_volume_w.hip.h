@@ -34,18 +34,17 @@ __device__ __forceinline__ void align_robust_factors(double wd, double r, double
 // The reduce of the 80 sums under the square loss (ROBUST = false: align_volume_partial_w_kernel, wl = wq = w, neither scale nor rweight is touched)
 // or the Geman-McClure loss (ROBUST = true: align_volume_partial_r_kernel, scale (m) doubles, rweight (m, Mt) or null).  Per valid pixel
 //     count += 1, wsum += w, cost += (wl r) r, dcost[a] += (2 (wq r)) J[a], jtj[a, b] += (wq J[a]) J[b] (a <= b)
-template <bool ROBUST>
-__device__ __forceinline__ void align_volume_partial_w_body(const float* __restrict__ vals, const int* __restrict__ ent, const int* __restrict__ tile,
-                                                            const float* __restrict__ w, const int* __restrict__ black, const int* __restrict__ pair,
-                                                            const float* __restrict__ fz, const float* __restrict__ targets, const float* __restrict__ weights,
-                                                            const float* __restrict__ intensity, const double* __restrict__ scale, float* __restrict__ warped,
-                                                            float* __restrict__ wgrad, float* __restrict__ rweight, double* __restrict__ partials, int m, int Mt,
-                                                            int tw, int K, int NPt, int T, int chunks) {
+// Where the pixel comes from is the caller's: pixel(gp, px, &R, &gZ, &gY, &gX) gives pixel px of the workgroup's target (gp = q Mt + px) and does the
+// optional warped / wgrad stores.  The two kernels of the volume families pass align_volume_pixel; align_stack_partial_r_kernel (align_stack.hip.h)
+// passes the point and a trilinear read of a voxel stack.  Inlined, the callable costs the older kernels no register (LAB_NOTES.md section 37).
+template <bool ROBUST, typename Pixel>
+__device__ __forceinline__ void align_volume_partial_w_body(Pixel pixel, const float* __restrict__ targets, const float* __restrict__ weights,
+                                                            const float* __restrict__ intensity, const double* __restrict__ scale,
+                                                            float* __restrict__ rweight, double* __restrict__ partials, int Mt, int tw, int chunks) {
 #pragma clang fp contract(off)
     __shared__ double red[ALIGN_VOLUME_SUMS_W][4];
     const int q = blockIdx.x / chunks, chunk = blockIdx.x - q * chunks;
     const int lo = chunk * ALIGN_CHUNK, hi = lo + ALIGN_CHUNK < Mt ? lo + ALIGN_CHUNK : Mt;
-    const size_t M = (size_t)m * Mt;
     const double g = intensity ? (double)intensity[(size_t)q * 2] : 1.0, b = intensity ? (double)intensity[(size_t)q * 2 + 1] : 0.0;
     double s = 0.0;
     if constexpr (ROBUST) s = scale[q];
@@ -56,7 +55,7 @@ __device__ __forceinline__ void align_volume_partial_w_body(const float* __restr
     for (int px = lo + threadIdx.x; px < hi; px += 256) {
         const size_t gp = (size_t)q * Mt + px;
         float R, gZ, gY, gX;
-        align_volume_pixel(vals, ent, tile, w, black, pair, fz, warped, wgrad, gp, M, K, NPt, T, &R, &gZ, &gY, &gX);
+        pixel(gp, px, &R, &gZ, &gY, &gX);
         const float tv = targets[gp], wv = weights ? weights[gp] : 1.f;
         float rw = __builtin_nanf("");
         if (scored && align_finite(tv) && align_finite(R) && align_finite(gZ) && align_finite(gY) && align_finite(gX) && align_finite(wv) && wv > 0.f) {
@@ -98,8 +97,10 @@ __global__ __launch_bounds__(256) void align_volume_partial_w_kernel(const float
                                                                      const float* __restrict__ weights, const float* __restrict__ intensity,
                                                                      float* __restrict__ warped, float* __restrict__ wgrad, double* __restrict__ partials, int m,
                                                                      int Mt, int tw, int K, int NPt, int T, int chunks) {
-    align_volume_partial_w_body<false>(vals, ent, tile, w, black, pair, fz, targets, weights, intensity, nullptr, warped, wgrad, nullptr, partials, m, Mt, tw, K, NPt, T,
-                                       chunks);
+    const size_t M = (size_t)m * Mt;
+    align_volume_partial_w_body<false>(
+        [&](size_t gp, int, float* R, float* gZ, float* gY, float* gX) { align_volume_pixel(vals, ent, tile, w, black, pair, fz, warped, wgrad, gp, M, K, NPt, T, R, gZ, gY, gX); },
+        targets, weights, intensity, nullptr, nullptr, partials, Mt, tw, chunks);
 }
 
 // sums[q, a] = the target's partial records added in index order

@@ -8,6 +8,8 @@
 // 5.8 - 5.16) are built on these trunks: the five
 // geometry pipelines below (namespace mh), each behind launch_dispatch.hip's slice_prologue on the call's stream, then their host-pointer forms
 // and the entry points.  Where each call's scratch sections lie and what it refuses as too large: align_plan.h.
+// msiren_align_stack_r* and msiren_align_stack_solve_group_r* (align_stack.hip.h) stand beside them on none of the trunks: the
+// robust volume family's reduce and grouped solve with the pixel read trilinearly from a plain voxel stack, on a handle that needs no weights.
 #include "host_buffers.h"
 #include "host_ctx.h"
 #include "align_plan.h"
@@ -19,6 +21,7 @@
 #include "align_volume_w.hip.h"
 #include "align_volume_r.hip.h"
 #include "align_group.hip.h"
+#include "align_stack.hip.h"
 
 namespace mh {
 
@@ -201,7 +204,9 @@ int resample_volume(msiren_handle h, const Call& c, const float* images_dev, int
 // these four is untouched by the fifth:
 // ALIGN_VOLUME_ROBUST (align_volume_r.hip.h): the weighted volume family's layout, bins and limits, its 80 sums formed under
 // a Geman-McClure loss with one scale per target.
-enum AlignFamily { ALIGN_PLAIN, ALIGN_WEIGHTED, ALIGN_VOLUME, ALIGN_VOLUME_WEIGHTED, ALIGN_VOLUME_ROBUST };
+// ALIGN_STACK (align_stack.hip.h): the robust 80 sums with the pixel read trilinearly from a plain voxel stack.  Its own check
+// (align_stack_check) and prepare (align_stack_prepare): no model, no prologue, no bins, no trunk; its scratch is the partials.
+enum AlignFamily { ALIGN_PLAIN, ALIGN_WEIGHTED, ALIGN_VOLUME, ALIGN_VOLUME_WEIGHTED, ALIGN_VOLUME_ROBUST, ALIGN_STACK };
 static int align_nsums(AlignFamily f) {
     return f == ALIGN_PLAIN ? msiren::ALIGN_SUMS : f == ALIGN_WEIGHTED ? msiren::ALIGN_SUMS_W : f == ALIGN_VOLUME ? msiren::ALIGN_VOLUME_SUMS : msiren::ALIGN_VOLUME_SUMS_W;
 }
@@ -270,6 +275,8 @@ struct AlignPlan {
     Call pc;
     const double* scale = nullptr;  // robust: (units) doubles
     float* rweight = nullptr;       // robust: (units, th, tw) or null
+    const float* stack = nullptr;   // stack family: the voxels (n, height, width); n above
+    int32_t height = 0, width = 0;
 };
 
 // the family's check, every workspace of the call (`extra` bytes more behind the partials: a solve's state) and the slice prologue.
@@ -308,6 +315,17 @@ static int align_evaluate(msiren_handle h, const Call& c, const AlignPlan& a, co
     const int64_t NP = a.n * g.NPt, T = a.T;
     hipStream_t st = sc.s;
     char* const base = (char*)sc.ragged.p;
+    if (a.fam == ALIGN_STACK) {  // no bins and no trunk: the partial reads the stack itself.  sums_dev (m, 80)
+        double* const partials = (double*)(base + a.lay.partials);
+        hipEvent_t e1 = nullptr;
+        if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+        hipLaunchKernelGGL(msiren::align_stack_partial_r_kernel, dim3((unsigned)(a.units * a.chunks)), dim3(256), 0, st, a.stack, maps_dev, a.targets, a.weights, a.intensity,
+                           a.scale, warped_dev, wgrad_dev, a.rweight, partials, (int)a.n, a.height, a.width, (int)a.units, (int)a.Mt, a.tw, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(msiren::align_volume_combine_w_kernel, dim3((unsigned)a.units), dim3(256), 0, st, partials, sums_dev, (int)a.chunks);
+        HIPCHK(hipGetLastError());
+        return profile_end(h, c.stream, e1, a.M, "align_stack_reduce_kernels");
+    }
     msiren::AlignVolumeParams avp{};
     msiren::ResampleVolumeParams& vp = avp.v;
     msiren::AlignParams ap{maps_dev, (int)a.n, a.th, a.tw, (int)a.Mt, g.nV, g.nH, h->S, h->I, (h->S - h->I) / 2, g.KA};
@@ -429,6 +447,64 @@ int align_volume_r(msiren_handle h, const Call& c, const float* images_dev, int6
     rc = align_prepare(h, c, ALIGN_VOLUME_ROBUST, images_dev, n, height, width, targets_dev, m, th, tw, maps_dev, sums_dev, 0, &a, &todo);
     if (rc || !todo) return rc;
     a.weights = weights_dev, a.intensity = intensity_dev, a.scale = scale_dev, a.rweight = rweight_dev;
+    return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
+}
+
+// ---- targets against a plain voxel stack (kernel: align_stack.hip.h) -------------------------------------------------------
+// Nothing of the model is asked: no jet_supported, no geom_check, no reflect padding.  Every refusal that needs no pointer, naming its argument.
+int align_stack_check(msiren_ctx*, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw) {
+    if (n < 0 || height < 0 || width < 0 || m < 0 || th < 0 || tw < 0)
+        return fail(MSIREN_E_INVALID, "bad arguments (n=%lld, height=%d, width=%d, m=%lld, th=%d, tw=%d)", (long long)n, height, width, (long long)m, th, tw);
+    if (!msiren::stack_pixels_fit(m, th, tw))
+        return fail(MSIREN_E_INVALID, "too many pixels for one call: m th tw = %lld targets x %d x %d must stay below 2^28", (long long)m, th, tw);
+    if (m == 0 || (int64_t)th * tw == 0) return 0;  // nothing to do: the stack is not looked at
+    if (n < 2) return fail(MSIREN_E_INVALID, "n = %lld: a stack needs two slices at least", (long long)n);
+    if (height < 2) return fail(MSIREN_E_INVALID, "height = %d: a stack needs two rows at least", height);
+    if (width < 2) return fail(MSIREN_E_INVALID, "width = %d: a stack needs two columns at least", width);
+    if (!msiren::stack_voxels_fit(n, height, width))
+        return fail(MSIREN_E_INVALID, "stack too large for one call: n height width = %lld x %d x %d must stay below 2^30, each extent below 2^24", (long long)n, height, width);
+    return 0;
+}
+
+// the stack family's prepare: its check, the null and alignment refusals of what every stack call takes, and the scratch -- the partials and `extra`
+// bytes behind them (a solve's state).  No prologue, no patches, no rec.  *todo = false: nothing to do (m = 0 or th tw = 0).
+static int align_stack_prepare(msiren_handle h, const Call& c, const float* stack_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m,
+                               int32_t th, int32_t tw, const float* weights_dev, const double* scale_dev, size_t extra, AlignPlan* a, bool* todo) {
+    *todo = false;
+    int rc = align_stack_check(h, n, height, width, m, th, tw);
+    if (rc) return rc;
+    const int64_t Mt = (int64_t)th * tw, M = m * Mt;
+    if (M == 0) return 0;
+    if (!stack_dev) return fail(MSIREN_E_INVALID, "null argument (stack)");
+    if (!targets_dev) return fail(MSIREN_E_INVALID, "null argument (targets)");
+    if (!scale_dev) return fail(MSIREN_E_INVALID, "null argument (scale)");
+    if ((uintptr_t)stack_dev % 4 || (uintptr_t)targets_dev % 4 || (uintptr_t)weights_dev % 4)
+        return fail(MSIREN_E_INVALID, "device stack, targets and weights must be 4-byte aligned");
+    if ((uintptr_t)scale_dev % 8) return fail(MSIREN_E_INVALID, "device scale must be 8-byte aligned");
+    const msiren::GeomLayout lay = msiren::stack_layout(m, Mt, msiren::ALIGN_VOLUME_SUMS_W);
+    if ((rc = ensure(h, h->sc[c.stream].ragged, lay.total + extra))) return rc;
+    *a = AlignPlan{};
+    a->fam = ALIGN_STACK, a->n = n, a->units = m, a->Mt = Mt, a->M = M, a->chunks = msiren::align_chunks(Mt), a->th = th, a->tw = tw, a->lay = lay;
+    a->targets = targets_dev, a->weights = weights_dev, a->scale = scale_dev, a->stack = stack_dev, a->height = height, a->width = width;
+    *todo = true;
+    return 0;
+}
+
+// sums_dev (m, 80) under the robust loss; every optional array may be null
+int align_stack_r(msiren_handle h, const Call& c, const float* stack_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                  const float* maps_dev, const float* weights_dev, const float* intensity_dev, const double* scale_dev, double* sums_dev, float* warped_dev, float* wgrad_dev,
+                  float* rweight_dev) {
+    int rc = align_stack_check(h, n, height, width, m, th, tw);
+    if (rc || m == 0 || (int64_t)th * tw == 0) return rc;
+    if (!maps_dev || !sums_dev) return fail(MSIREN_E_INVALID, "null argument (%s)", !maps_dev ? "maps" : "sums");
+    if ((uintptr_t)maps_dev % 4 || (uintptr_t)intensity_dev % 4 || (uintptr_t)warped_dev % 4 || (uintptr_t)wgrad_dev % 4 || (uintptr_t)rweight_dev % 4)
+        return fail(MSIREN_E_INVALID, "device maps, intensity, warped, wgrad and rweight must be 4-byte aligned");
+    if ((uintptr_t)sums_dev % 8) return fail(MSIREN_E_INVALID, "device sums must be 8-byte aligned");
+    AlignPlan a;
+    bool todo;
+    rc = align_stack_prepare(h, c, stack_dev, n, height, width, targets_dev, m, th, tw, weights_dev, scale_dev, 0, &a, &todo);
+    if (rc || !todo) return rc;
+    a.intensity = intensity_dev, a.rweight = rweight_dev;
     return align_evaluate(h, c, a, maps_dev, sums_dev, warped_dev, wgrad_dev);
 }
 
@@ -650,6 +726,8 @@ int align_volume_solve_w(msiren_handle h, const Call& c, const float* images_dev
 // ---- the grouped rigid solve (kernels: align_group.hip.h): align_volume_solve_w's loop with the step stage for groups of
 // consecutive targets under one rigid state per group.  Prologue, bins, trunk and the 80-sum reduce are the weighted volume family's; the loop is
 // solve_loop_staged with the four step kernels as its stage.
+static int groups_check(const int32_t* group_start, int64_t G, int64_t m);  // what is wrong with group_start, by name and index (below)
+
 // every refusal that needs no device pointer: what align_volume_solve_w_check refuses in rigid mode, then the groups (group_start is a host array)
 int align_volume_solve_group_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_group_opts* o,
                                    const int32_t* group_start, int64_t G, const void* planes, const void* rigid_in, const void* maps_out, const void* intensity_out,
@@ -662,6 +740,28 @@ int align_volume_solve_group_check(msiren_ctx* h, int64_t n, int32_t height, int
                                              o->lam_max, o->spacing};
     int rc = align_volume_solve_w_check(h, n, height, width, m, th, tw, &w, nullptr, planes, rigid_in, maps_out, intensity_out, report);
     if (rc || m == 0) return rc;
+    return groups_check(group_start, G, m);
+}
+
+// the stack family's: the same refusals in the same order with align_stack_check in the model's place
+int align_stack_solve_group_check(msiren_ctx* h, int64_t n, int32_t height, int32_t width, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_group_opts* o,
+                                  const int32_t* group_start, int64_t G, const void* planes, const void* rigid_in, const void* maps_out, const void* intensity_out,
+                                  const void* report) {
+    if (!o) return fail(MSIREN_E_INVALID, "null options");
+    if (o->struct_size != sizeof(msiren_align_volume_solve_group_opts))
+        return fail(MSIREN_E_INVALID, "msiren_align_volume_solve_group_opts.struct_size = %u, this library's is %u", o->struct_size,
+                    (unsigned)sizeof(msiren_align_volume_solve_group_opts));
+    if (o->intensity_mode != 0 && o->intensity_mode != 1) return fail(MSIREN_E_INVALID, "intensity_mode = %d (0: fixed, 1: estimate)", o->intensity_mode);
+    int rc = align_stack_check(h, n, height, width, m, th, tw);
+    if (rc || (rc = lm_opts_check(1, o->iterations, o->damping, o->down, o->up, o->lam_min, o->lam_max))) return rc;
+    if (!(o->spacing > 0.0 && o->spacing < __builtin_inf())) return fail(MSIREN_E_INVALID, "spacing = %g must be finite and > 0", o->spacing);
+    if (m > 0 && (int64_t)th * tw > 0 && (!rigid_in || !planes || !maps_out || !intensity_out || !report))
+        return fail(MSIREN_E_INVALID, "null argument (%s)", !maps_out ? "maps_out" : !intensity_out ? "intensity_out" : !report ? "report" : !planes ? "planes" : "rigid_in");
+    if (m == 0) return 0;
+    return groups_check(group_start, G, m);
+}
+
+static int groups_check(const int32_t* group_start, int64_t G, int64_t m) {
     int64_t at = 0;
     switch (msiren::group_start_check(group_start, G, m, &at)) {
         case msiren::GROUPS_OK: return 0;
@@ -676,15 +776,18 @@ int align_volume_solve_group_check(msiren_ctx* h, int64_t n, int32_t height, int
 }
 
 // the grouped solve on the sums of `fam`: ALIGN_VOLUME_WEIGHTED (scale_dev unused) or ALIGN_VOLUME_ROBUST (scale_dev (m) doubles,
-// fixed for the call, so every evaluation scores one objective).  The step stage reads the 80 sums whatever loss formed them.
+// fixed for the call, so every evaluation scores one objective).  The step stage reads the 80 sums whatever loss formed them.  ALIGN_STACK (section
+// 5.22): images_dev is the voxel stack, the check and the prepare are the stack family's, the rest is the same.
 static int group_solve(msiren_handle h, const Call& c, AlignFamily fam, const double* scale_dev, const float* images_dev, int64_t n, int32_t height, int32_t width,
                        const float* targets_dev, int64_t m, int32_t th, int32_t tw, const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G,
                        const double* planes, const double* rigid_in, const float* weights_dev, const float* intensity_in, float* maps_out, float* intensity_out,
                        double* rigid_out, double* report, double* target_report, double* trace) {
-    int rc = align_volume_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report);
+    const bool stack = fam == ALIGN_STACK;  // images_dev: the voxels
+    int rc = stack ? align_stack_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report)
+                   : align_volume_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report);
     if (rc || m == 0 || (int64_t)th * tw == 0) return rc;
-    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, "null argument");
-    if (fam == ALIGN_VOLUME_ROBUST && !scale_dev) return fail(MSIREN_E_INVALID, "null argument (scale)");
+    if (!images_dev || !targets_dev) return fail(MSIREN_E_INVALID, stack ? (!images_dev ? "null argument (stack)" : "null argument (targets)") : "null argument");
+    if ((fam == ALIGN_VOLUME_ROBUST || stack) && !scale_dev) return fail(MSIREN_E_INVALID, "null argument (scale)");
     if (fam == ALIGN_VOLUME_ROBUST && (uintptr_t)scale_dev % 8) return fail(MSIREN_E_INVALID, "device scale must be 8-byte aligned");
     if ((uintptr_t)targets_dev % 4 || (uintptr_t)maps_out % 4 || (uintptr_t)weights_dev % 4 || (uintptr_t)intensity_in % 4 || (uintptr_t)intensity_out % 4 ||
         (uintptr_t)planes % 8 || (uintptr_t)rigid_in % 8 || (uintptr_t)rigid_out % 8 || (uintptr_t)report % 8 || (uintptr_t)target_report % 8 || (uintptr_t)trace % 8)
@@ -692,8 +795,10 @@ static int group_solve(msiren_handle h, const Call& c, AlignFamily fam, const do
     constexpr int S = msiren::ALIGN_VOLUME_SUMS_W, R = msiren::ALIGN_GROUP_REC, NS = msiren::ALIGN_GROUP_SCAL, NC = msiren::ALIGN_GROUP_CNT;
     AlignPlan a;
     bool todo;
-    if ((rc = align_prepare(h, c, fam, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report,
-                            msiren::group_solve_layout(0, m, G, S, R, NS, NC).total, &a, &todo)) || !todo)
+    const size_t extra = msiren::group_solve_layout(0, m, G, S, R, NS, NC).total;
+    if ((rc = stack ? align_stack_prepare(h, c, images_dev, n, height, width, targets_dev, m, th, tw, weights_dev, scale_dev, extra, &a, &todo)
+                    : align_prepare(h, c, fam, images_dev, n, height, width, targets_dev, m, th, tw, maps_out, report, extra, &a, &todo)) ||
+        !todo)
         return rc;
     auto& sc = h->sc[c.stream];
     hipStream_t st = sc.s;
@@ -753,6 +858,15 @@ int align_volume_solve_group_r(msiren_handle h, const Call& c, const float* imag
                                double* report, double* target_report, double* trace) {
     return group_solve(h, c, ALIGN_VOLUME_ROBUST, scale_dev, images_dev, n, height, width, targets_dev, m, th, tw, o, group_start, G, planes, rigid_in, weights_dev,
                        intensity_in, maps_out, intensity_out, rigid_out, report, target_report, trace);
+}
+
+// the same loop on the sums of a plain voxel stack: no prologue, no trunk, no weights of the model
+int align_stack_solve_group_r(msiren_handle h, const Call& c, const float* stack_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                              int32_t tw, const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
+                              const float* weights_dev, const float* intensity_in, const double* scale_dev, float* maps_out, float* intensity_out, double* rigid_out,
+                              double* report, double* target_report, double* trace) {
+    return group_solve(h, c, ALIGN_STACK, scale_dev, stack_dev, n, height, width, targets_dev, m, th, tw, o, group_start, G, planes, rigid_in, weights_dev, intensity_in,
+                       maps_out, intensity_out, rigid_out, report, target_report, trace);
 }
 
 }  // namespace mh
@@ -1137,9 +1251,96 @@ int align_volume_solve_group_r_host(msiren_ctx* h, const float* images_host, int
     return io.finish();
 }
 
+// the stack forms: as the two above with the stack in the place of the images, on a handle that needs no weights
+int align_stack_r_host(msiren_ctx* h, const float* stack_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                       const float* maps_host, const float* weights_host, const float* intensity_host, const double* scale_host, double* sums_host, float* warped_host,
+                       float* wgrad_host, float* rweight_host) {
+    const int64_t M = m * (int64_t)th * tw;
+    int rc = check(h, false);
+    if (rc || (rc = align_stack_check(h, n, height, width, m, th, tw)) || M == 0) return rc;
+    const char* const missing = !stack_host ? "stack" : !targets_host ? "targets" : !maps_host ? "maps" : !scale_host ? "scale" : !sums_host ? "sums" : nullptr;
+    if (missing) return fail(MSIREN_E_INVALID, "null argument (%s)", missing);
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(stack_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)m * 9 * sizeof(float), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_host, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int i_s = io.in(scale_host, (size_t)m * sizeof(double), HOST_COPY);
+    const int o_s = io.out(sums_host, (size_t)m * kAlignVolumeSumsW * sizeof(double), HOST_IN_PLACE);
+    const int o_w = io.out(warped_host, nt, HOST_IN_PLACE), o_g = io.out(wgrad_host, 3 * nt, HOST_IN_PLACE), o_rw = io.out(rweight_host, nt, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_stack_r(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, io.src<float>(i_m), io.src<float>(i_w), io.src<float>(i_gb),
+                            io.src<double>(i_s), io.dst<double>(o_s), io.dst<float>(o_w), io.dst<float>(o_g), io.dst<float>(o_rw))))
+        return rc;
+    return io.finish();
+}
+
+int align_stack_solve_group_r_host(msiren_ctx* h, const float* stack_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                                   const msiren_align_volume_solve_group_opts* o, const int32_t* group_start, int64_t G, const double* planes, const double* rigid_in,
+                                   const float* weights_host, const float* intensity_in, const double* scale_host, float* maps_out, float* intensity_out, double* rigid_out,
+                                   double* report, double* target_report, double* trace) {
+    const int64_t M = m * (int64_t)th * tw;
+    int rc = check(h, false);
+    if (rc || (rc = align_stack_solve_group_check(h, n, height, width, m, th, tw, o, group_start, G, planes, rigid_in, maps_out, intensity_out, report)) || M == 0) return rc;
+    const char* const missing = !stack_host ? "stack" : !targets_host ? "targets" : !scale_host ? "scale" : nullptr;
+    if (missing) return fail(MSIREN_E_INVALID, "null argument (%s)", missing);
+    Call c = make_call(h, true);
+    const size_t ni = (size_t)n * height * width * sizeof(float), nt = (size_t)M * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_img = io.in(stack_host, ni, HOST_COPY), i_t = io.in(targets_host, nt, HOST_COPY);
+    const int i_p = io.in(planes, (size_t)m * 12 * sizeof(double), HOST_COPY), i_r = io.in(rigid_in, (size_t)G * 12 * sizeof(double), HOST_COPY);
+    const int i_w = io.in(weights_host, nt, HOST_COPY), i_gb = io.in(intensity_in, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int i_s = io.in(scale_host, (size_t)m * sizeof(double), HOST_COPY);
+    const int o_m = io.out(maps_out, (size_t)m * 9 * sizeof(float), HOST_COPY), o_gb = io.out(intensity_out, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    const int o_r = io.out(rigid_out, (size_t)G * 12 * sizeof(double), HOST_COPY), o_rep = io.out(report, (size_t)G * 7 * sizeof(double), HOST_COPY);
+    const int o_tr = io.out(target_report, (size_t)m * 3 * sizeof(double), HOST_COPY), o_trace = io.out(trace, (size_t)o->iterations * G * 15 * sizeof(double), HOST_COPY);
+    if ((rc = io.begin())) return rc;
+    if ((rc = align_stack_solve_group_r(h, c, io.src<float>(i_img), n, height, width, io.src<float>(i_t), m, th, tw, o, group_start, G, io.src<double>(i_p), io.src<double>(i_r),
+                                        io.src<float>(i_w), io.src<float>(i_gb), io.src<double>(i_s), io.dst<float>(o_m), io.dst<float>(o_gb), io.dst<double>(o_r),
+                                        io.dst<double>(o_rep), io.dst<double>(o_tr), io.dst<double>(o_trace))))
+        return rc;
+    return io.finish();
+}
+
 }  // namespace
 
 extern "C" {
+
+int msiren_align_stack_r(msiren_handle h, const float* stack_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
+                         const float* maps_host, const float* weights_host, const float* intensity_host, const double* scale_host, double* sums_host, float* warped_host,
+                         float* wgrad_host, float* rweight_host) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_stack_r_host(h, stack_host, n, height, width, targets_host, m, th, tw, maps_host, weights_host, intensity_host, scale_host, sums_host, warped_host, wgrad_host,
+                              rweight_host);
+}
+int msiren_align_stack_r_dev(msiren_handle h, const float* stack_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th, int32_t tw,
+                             const float* maps_dev, const float* weights_dev, const float* intensity_dev, const double* scale_dev, double* sums_dev, float* warped_dev,
+                             float* wgrad_dev, float* rweight_dev) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    if ((rc = align_stack_check(h, n, height, width, m, th, tw))) return rc;  // (before the stream rotates)
+    return align_stack_r(h, dev_call(h), stack_dev, n, height, width, targets_dev, m, th, tw, maps_dev, weights_dev, intensity_dev, scale_dev, sums_dev, warped_dev, wgrad_dev,
+                         rweight_dev);
+}
+int msiren_align_stack_solve_group_r(msiren_handle h, const float* stack_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th,
+                                     int32_t tw, const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start, int64_t n_groups, const double* planes,
+                                     const double* rigid_in, const float* weights_host, const float* intensity_in, const double* scale, float* maps_out, float* intensity_out,
+                                     double* rigid_out, double* report, double* target_report, double* trace) {
+    if (!h) return fail(MSIREN_E_INVALID, "null handle");
+    return align_stack_solve_group_r_host(h, stack_host, n, height, width, targets_host, m, th, tw, opts, group_start, n_groups, planes, rigid_in, weights_host, intensity_in,
+                                          scale, maps_out, intensity_out, rigid_out, report, target_report, trace);
+}
+int msiren_align_stack_solve_group_r_dev(msiren_handle h, const float* stack_dev, int64_t n, int32_t height, int32_t width, const float* targets_dev, int64_t m, int32_t th,
+                                         int32_t tw, const msiren_align_volume_solve_group_opts* opts, const int32_t* group_start, int64_t n_groups, const double* planes_dev,
+                                         const double* rigid_in_dev, const float* weights_dev, const float* intensity_in_dev, const double* scale_dev, float* maps_out_dev,
+                                         float* intensity_out_dev, double* rigid_out_dev, double* report_dev, double* target_report_dev, double* trace_dev) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    if ((rc = align_stack_solve_group_check(h, n, height, width, m, th, tw, opts, group_start, n_groups, planes_dev, rigid_in_dev, maps_out_dev, intensity_out_dev, report_dev)))
+        return rc;  // (before the stream rotates)
+    return align_stack_solve_group_r(h, dev_call(h), stack_dev, n, height, width, targets_dev, m, th, tw, opts, group_start, n_groups, planes_dev, rigid_in_dev, weights_dev,
+                                     intensity_in_dev, scale_dev, maps_out_dev, intensity_out_dev, rigid_out_dev, report_dev, target_report_dev, trace_dev);
+}
 
 int msiren_align_volume_r(msiren_handle h, const float* images_host, int64_t n, int32_t height, int32_t width, const float* targets_host, int64_t m, int32_t th, int32_t tw,
                           const float* maps_host, const float* weights_host, const float* intensity_host, const double* scale_host, double* sums_host, float* warped_host,

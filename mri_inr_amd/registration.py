@@ -1,12 +1,12 @@
-"""The slice-to-volume registration calls of ``ModulatedSiren``, from ``resample`` to ``solve_volume_robust``: the ctypes binding of the
-``msiren_resample_*``, ``msiren_align_*``, ``msiren_fuse_targets``, ``msiren_project_volume`` and ``msiren_solve_volume*`` entry points
-(DESIGN.md sections 5.8 to 5.20), as the mixin ``_Registration`` the model inherits.
+"""The slice-to-volume registration calls of ``ModulatedSiren``, from ``resample`` to ``solve_volume_robust`` and ``align_stack_solve``: the ctypes
+binding of the ``msiren_resample_*``, ``msiren_align_*``, ``msiren_fuse_targets``, ``msiren_project_volume`` and ``msiren_solve_volume*`` entry
+points (DESIGN.md sections 5.8 to 5.20 and 5.22), as the mixin ``_Registration`` the model inherits.
 
 Every public method reads the same way: check the inputs, build the options, allocate the outputs, one call into the library, wrap the
 result.  The rules all of them keep:
 
-* ``_ensure_committed()`` in front of everything that evaluates the model; ``fuse_targets``, ``project_volume`` and the two volume solves
-  involve no weights of the model and only need the handle (``_ensure_handle()``).
+* ``_ensure_committed()`` in front of everything that evaluates the model; ``fuse_targets``, ``project_volume``, the two volume solves and the
+  two ``align_stack_*`` methods involve no weights of the model and only need the handle (``_ensure_handle()``).
 * Outputs are filled before the call -- NaN for sampled images and volumes, 0 for sums, reports and coverage, -1 for ``stopped_at``, (1, 0)
   rows for an absent intensity -- because the library may return without writing them (no targets, an empty grid, no rounds).
 * An absent optional array is a null pointer (``_addr``).  For m = 0 targets the fuse, project and solve-volume calls take null for every
@@ -509,6 +509,63 @@ class _Registration:
         steps = _steps(iterations, damping, down, up, lam_min, lam_max)
         return self._align_volume_solve_group(images, targets, planes, spacing, groups, rotation, shift, weights, intensity, estimate_intensity, steps, trace,
                                               True, scale)
+
+    # ---- targets against a stack that is just voxels ----
+    def align_stack_cost(self, stack, targets, maps, *, scale=float("inf"), weights=None, intensity=None, warped=False, gradient=False, rweight=False):
+        """``align_volume_cost_r`` against a plain voxel ``stack`` (n, H, W), n, H, W >= 2 -- what ``fuse_targets`` and the volume solves return, NaN
+        holes included -- instead of the stack the network reconstructs -> ``align_robust.AlignResultR``.  targets (m, th, tw), maps (m, 9) in the same
+        convention; the pixel is a trilinear read of the stack with its analytic gradient (``align_stack.read_stack``), NaN outside the stack and
+        wherever one of its eight corners is not finite; everything behind the pixel is ``align_volume_cost_r``'s.  ``scale`` +inf (the default): the
+        weighted square loss.  Build-defined (msiren_align_stack_r); bit for bit what ``align_stack.cost_on_host`` gives.  No
+        images and no weights of the model are involved."""
+        from . import align_robust as ar, align_volume as av
+
+        self._ensure_handle()
+        a = _stack(stack)
+        t = _targets(targets)
+        w, gb = _weights_intensity(weights, intensity, t.shape)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        mp = _maps(maps, m, 9)
+        s = ar.scales(scale, m)
+        sums = np.zeros((m, av.SUMS_VW), np.float64)
+        wp = _optional(warped, (m, th, tw), np.nan)
+        g = _optional(gradient, (3, m, th, tw), np.nan)
+        rw = _optional(rweight, (m, th, tw), np.nan)
+        _lib.check(self._lib.msiren_align_stack_r(self._h, _addr(a), n, Hh, Ww, _addr(t), m, th, tw, _addr(mp), _addr(w), _addr(gb), _addr(s), _addr(sums), _addr(wp),
+                                                  _addr(g), _addr(rw)))
+        return ar.unpack_r(sums, wp, g, rw)
+
+    def align_stack_solve(self, stack, targets, planes, spacing, *, groups=None, scale=float("inf"), rotation=None, shift=None, weights=None, intensity=None,
+                          estimate_intensity=True, iterations=12, damping=1e-3, down=0.1, up=10.0, lam_min=1e-9, lam_max=1e9, trace=False):
+        """``align_volume_solve_group_robust`` on ``align_stack_cost``: the targets registered to a plain voxel ``stack`` under one rigid motion per
+        group -> ``align_group.SolveResultG``.  ``groups`` None: every target on its own.  Every other argument, the step rule and the result are
+        ``align_volume_solve_group_robust``'s (build-defined; msiren_align_stack_solve_group_r); bit for bit what
+        ``align_stack.solve_on_host_s`` gives.  With ``solve_volume_robust`` on either side it is the registration step of the outer loop
+        reconstruct -> register -> reconstruct, with no images and no weights of the model."""
+        from . import align_group as ag, align_robust as ar, align_volume as av
+
+        self._ensure_handle()
+        a = _stack(stack)
+        t = _targets(targets)
+        w, gb = _weights_intensity(weights, intensity, t.shape)
+        n, Hh, Ww = a.shape
+        m, th, tw = t.shape
+        pl = _planes(planes, m)
+        s = ar.scales(scale, m)
+        gs = np.ascontiguousarray(list(range(m + 1)) if groups is None else ag.group_offsets(groups, m), dtype=np.int32)  # (None: singletons)
+        G = len(gs) - 1
+        state = _rigid3(rotation, shift, G)
+        iterations, lm = _steps(iterations, damping, down, up, lam_min, lam_max)
+        opts = _lib.AlignVolumeSolveGroupOpts
+        o = opts(C.sizeof(opts), iterations, av.ESTIMATE if estimate_intensity else av.FIXED, 0, *lm, float(spacing))
+        out = np.zeros((m, 9), np.float32)
+        gout = _intensity_out(gb, m)
+        rout, report, trep = state.copy(), np.zeros((G, 7), np.float64), np.zeros((m, 3), np.float64)
+        tr = _optional(trace, (max(iterations, 0), G, 15), 0, np.float64)
+        _lib.check(self._lib.msiren_align_stack_solve_group_r(self._h, _addr(a), n, Hh, Ww, _addr(t), m, th, tw, C.byref(o), _addr(gs), G, _addr(pl), _addr(state), _addr(w),
+                                                              _addr(gb), _addr(s), _addr(out), _addr(gout), _addr(rout), _addr(report), _addr(trep), _addr(tr)))
+        return ag.solve_result_g(out, gout, rout, report, trep, tr)
 
     # ---- the aligned targets back on the stack's grid, and the stack back on the targets (DESIGN.md sections 5.17 to 5.20) ----
     def fuse_targets(self, targets, maps, shape, spacing, *, thickness=None, weights=None, intensity=None, min_coverage=0.0, coverage=False):
