@@ -47,7 +47,8 @@ extern "C" {
  * msiren_solve_volume(_dev) and msiren_solve_opts (the stack that best explains all targets: regularised conjugate gradients on those two operators);
  * msiren_solve_volume_r(_dev) and msiren_solve_r_opts (rounds of that solve, reweighted by a Geman-McClure loss with one annealed scale per target);
  * msiren_align_stack_r(_dev) and msiren_align_stack_solve_group_r(_dev) (the robust volume cost and the grouped solve against a plain voxel stack read
- * trilinearly: no images, no trunk, no weights).
+ * trilinearly: no images, no trunk, no weights); msiren_residual_scale(_dev) and msiren_scale_opts (a robust scale per target or per group of targets
+ * from an exact order statistic of the residuals, on the device: what every robust call takes as `scale`, without a host read).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -1067,6 +1068,55 @@ MSIREN_API int msiren_solve_volume_r_dev(msiren_handle h, const float* targets_d
                                          int32_t* flags_dev /* (m) or NULL */, int32_t* stopped_at_dev /* (rounds) or NULL */,
                                          float* rweight_dev /* (m, th, tw) or NULL */, float* residual_dev /* (m, th, tw) or NULL */,
                                          double* stats_dev /* (m, 4) or NULL */);
+
+/* Build-defined: the `scale` of the robust calls (msiren_align_volume_r, msiren_align_stack_r, the grouped solves,
+ * msiren_solve_volume_r) estimated on the device from an exact order statistic of the residuals -- per target, or pooled over groups of consecutive
+ * targets -- so that it never has to leave the device.  No images, no trunk: the handle need not hold committed weights.
+ *     targets (m, th, tw) float32;  simulated (m, th, tw) float32 or NULL;  weights (m, th, tw) float32 or NULL (all 1);  intensity (m, 2) float32 =
+ *     (g, b) per target or NULL;  opts (HOST memory in both forms);  group_start (n_groups + 1) int32, HOST memory in both forms, or NULL with n_groups
+ *     = 0;  scale (m) float64 out;  stats (S, 4) float64 out or NULL, S = n_groups, or m without groups
+ *   RESIDUAL per pixel, fp64 + - *, one rounding per operation, no fused multiply-add:
+ *     simulated and intensity given:   e = (float)((double)T - ((g (double)S) + b))        (pass `warped` of the align calls with their intensity)
+ *     simulated alone:                 e = (float)((double)T - (double)S)                  ((g, b) = (1, 0), which are not multiplied in: the product and
+ *                                      the sum would turn S = -0.0 into +0.0.  msiren_project_volume's residual bit for bit wherever that one is finite)
+ *     simulated NULL:                  e = T                                               (the array already is a residual; intensity must be NULL)
+ *   A pixel COUNTS iff e is finite and its weight is finite and > 0 (msiren_project_volume's rule).
+ *   SEGMENTS: without group_start one per target.  With it: n_groups >= 1 groups of consecutive targets, group g = targets group_start[g] ..
+ *   group_start[g + 1] - 1 (first offset 0, last m, strictly ascending), and one segment covers all pixels of a group.  One group pools everything.
+ *   PER SEGMENT with count pixels that count:
+ *     k = (int64)floor(quantile (double)(count - 1))                                       (one fp64 multiply; no interpolation between ranks)
+ *     centre = 0:  c = +0.0f, d_i = |e_i|
+ *     centre = 1:  c = the element of rank k (0-based, ascending) of the e_i in the total order of their bit patterns -- key = bits ^ 0x80000000 where
+ *                  the sign bit is clear, ~bits where it is set, compared as uint32: -0 sorts before +0 -- and d_i = fabsf(e_i - c), one fp32 subtraction
+ *     d = the element of rank k of the d_i, ordered as their uint32 bits (they are not negative; +inf, from an overflowing subtraction, sorts last)
+ *     t = tune (double)d,  s = t t,  scale = s if s > floor, else floor -- written to scale[q] of every target q of the segment
+ *     stats[segment] = (count, k, (double)c, (double)d)
+ *     count = 0:  scale = +inf (the quadratic loss) and stats = (0, 0, 0, 0)
+ *   numpy's quantile(., method="lower") on the same float32 values is the same statistic.  quantile = 0.5, centre = 1, tune = 1.4826 c: (c sigma)^2 from
+ *   the median absolute deviation.  mri_inr_amd/residual_scale.py: residual_scale_on_host (numpy) gives the same bits.
+ * The _dev form enqueues on the handle's stream rotation without a host synchronisation and reads nothing back: the sequence of launches depends on
+ * centre and n_groups alone.  group_start is carried to the device in kernel arguments: the caller may reuse the array as soon as the call returns.
+ * m_targets = 0 or th tw = 0 does nothing.  MSIREN_E_INVALID before any launch, naming the argument: opts->struct_size; centre not 0 or 1; quantile
+ * outside [0, 1] or NaN; tune not finite or not > 0; floor NaN, negative or infinite; a negative extent; m th tw >= 2^28; with m > 0 a null targets,
+ * opts or scale; intensity without simulated; group_start and n_groups not both given or both absent, and a group_start that is not as above; a device
+ * targets, simulated, weights or intensity that is not 4-byte aligned, a device scale or stats that is not 8-byte aligned.  Under
+ * msiren_profile_enable: one entry per call, "residual_scale_kernels". */
+typedef struct {
+    int32_t struct_size;      /* sizeof(msiren_scale_opts) */
+    int32_t centre;           /* 0: d = |e|;  1: d = |e - c|, c the same order statistic of the e themselves */
+    double quantile;          /* 0 .. 1 */
+    double tune;              /* finite, > 0 */
+    double floor;             /* finite, >= 0: the least scale returned for a segment that has pixels */
+} msiren_scale_opts;
+MSIREN_API int msiren_residual_scale(msiren_handle h, const float* targets_host /* (m, th, tw) */, const float* simulated_host /* (m, th, tw) or NULL */,
+                                     const float* weights_host /* (m, th, tw) or NULL */, const float* intensity_host /* (m, 2) or NULL */, int64_t m_targets,
+                                     int32_t th, int32_t tw, const msiren_scale_opts* opts, const int32_t* group_start /* (n_groups + 1), host, or NULL */,
+                                     int64_t n_groups, double* scale_host /* (m) */, double* stats_host /* (S, 4) or NULL */);
+MSIREN_API int msiren_residual_scale_dev(msiren_handle h, const float* targets_dev /* (m, th, tw) */, const float* simulated_dev /* (m, th, tw) or NULL */,
+                                         const float* weights_dev /* (m, th, tw) or NULL */, const float* intensity_dev /* (m, 2) or NULL */, int64_t m_targets,
+                                         int32_t th, int32_t tw, const msiren_scale_opts* opts /* host */,
+                                         const int32_t* group_start /* (n_groups + 1), host, or NULL */, int64_t n_groups, double* scale_dev /* (m) */,
+                                         double* stats_dev /* (S, 4) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

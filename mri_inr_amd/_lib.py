@@ -166,6 +166,17 @@ class SolveROpts(C.Structure):
     ]
 
 
+class ScaleOpts(C.Structure):
+    """msiren_scale_opts"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("centre", C.c_int32),
+        ("quantile", C.c_double),
+        ("tune", C.c_double),
+        ("floor", C.c_double),
+    ]
+
+
 _fp = C.POINTER(C.c_float)
 _vp = C.c_void_p
 _i64 = C.c_int64
@@ -273,6 +284,8 @@ PROTOTYPES = {
     "msiren_solve_volume_r": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(SolveROpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "msiren_solve_volume_r_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(SolveROpts), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp]),
+    "msiren_residual_scale": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(ScaleOpts), _vp, _i64, _vp, _vp]),
+    "msiren_residual_scale_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(ScaleOpts), _vp, _i64, _vp, _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

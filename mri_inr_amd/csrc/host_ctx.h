@@ -33,6 +33,10 @@
 //                          refusals, scratch and the launch plan: solve_volume_plan.h, tests/test_solve_volume_reference.py)
 //                          and msiren_solve_volume_r*: that solve in rounds reweighted by a Geman-McClure loss (kernels: solve_volume_r.hip.h;
 //                          refusals, scratch, the schedule and the launch plan: solve_volume_r_plan.h, tests/test_solve_volume_robust_reference.py)
+//     residual_scale.hip   msiren_residual_scale*: the scale of the robust calls from an exact order statistic of the residuals, on the device
+//                          (kernels: residual_scale.hip.h, an MSD radix select per segment of targets; refusals, chunking, launch count and
+//                          scratch: residual_scale_plan.h, tests/test_residual_scale_plan.py).  A unit of its own: it includes none of the other
+//                          families' kernel headers
 // Everything in namespace mh is internal (the library is built with -fvisibility=hidden; only include/msiren.h is exported).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,15 +1,16 @@
-"""The slice-to-volume registration calls of ``ModulatedSiren``, from ``resample`` to ``solve_volume_robust`` and ``align_stack_solve``: the ctypes
-binding of the ``msiren_resample_*``, ``msiren_align_*``, ``msiren_fuse_targets``, ``msiren_project_volume`` and ``msiren_solve_volume*`` entry
-points (DESIGN.md sections 5.8 to 5.20 and 5.22), as the mixin ``_Registration`` the model inherits.
+"""The slice-to-volume registration calls of ``ModulatedSiren``, from ``resample`` to ``solve_volume_robust``, ``align_stack_solve`` and
+``residual_scale``: the ctypes binding of the ``msiren_resample_*``, ``msiren_align_*``, ``msiren_fuse_targets``, ``msiren_project_volume``,
+``msiren_solve_volume*`` and ``msiren_residual_scale`` entry points (DESIGN.md sections 5.8 to 5.20, 5.22 and 5.23), as the mixin ``_Registration`` the
+model inherits.
 
 Every public method reads the same way: check the inputs, build the options, allocate the outputs, one call into the library, wrap the
 result.  The rules all of them keep:
 
 * ``_ensure_committed()`` in front of everything that evaluates the model; ``fuse_targets``, ``project_volume``, the two volume solves and the
-  two ``align_stack_*`` methods involve no weights of the model and only need the handle (``_ensure_handle()``).
+  two ``align_stack_*`` methods and ``residual_scale`` involve no weights of the model and only need the handle (``_ensure_handle()``).
 * Outputs are filled before the call -- NaN for sampled images and volumes, 0 for sums, reports and coverage, -1 for ``stopped_at``, (1, 0)
-  rows for an absent intensity -- because the library may return without writing them (no targets, an empty grid, no rounds).
-* An absent optional array is a null pointer (``_addr``).  For m = 0 targets the fuse, project and solve-volume calls take null for every
+  rows for an absent intensity, +inf for an estimated scale -- because the library may return without writing them (no targets, an empty grid, no rounds).
+* An absent optional array is a null pointer (``_addr``).  For m = 0 targets the fuse, project, solve-volume and residual-scale calls take null for every
   per-target pointer (``_ptr``); the alignment calls take the address of the empty array.  The library answers the two differently.
 * numpy or torch in, numpy out; a tensor in gives tensors out for the resample methods only."""
 
@@ -678,3 +679,33 @@ class _Registration:
                                                    _ptr(st, vol.size), _addr(vol), _addr(cov), _ptr(hist, nr), _ptr(flags, m), _ptr(stopped, nr), _ptr(rw, m),
                                                    _ptr(sts, m)))
         return svr.SolveVolumeRobustResult(vol, cov, hist, flags, stopped, rw, sts)
+
+    # ---- the scale of the robust calls from the residuals themselves ----
+    def residual_scale(self, targets, simulated=None, *, tune, weights=None, intensity=None, groups=None, quantile=0.5, centre=False, floor=0.0, stats=False):
+        """The ``scale`` every robust call takes, estimated on the device from an exact order statistic of the residuals ->
+        ``residual_scale.ResidualScaleResult``.  targets (m, th, tw); ``simulated`` (m, th, tw): the residual is targets - (g simulated + b) with
+        ``intensity`` (m, 2) or None ((1, 0)) -- ``warped`` of the align calls with their intensity, ``simulated`` of ``project_volume`` without -- or
+        None: the targets already are residuals.  A pixel counts where the residual is finite and its ``weights`` entry (None: 1) is finite and > 0.
+        ``groups``: offsets or sizes of groups of consecutive targets as in ``align_stack_solve`` (None: every target on its own; ``[m]`` pools all):
+        one statistic per group.  Per group the element of rank floor(quantile (count - 1)) of |e|, or with ``centre`` of |e - c| with c that element
+        of the e themselves -- no interpolation -- as d; scale = max((tune d)^2, floor) for every target of the group, +inf where no pixel counts.
+        ``tune`` = c ``residual_scale.MAD_TO_SIGMA`` gives (c sigma)^2.  ``stats``: (count, k, c, d) per group too.  Build-defined (DESIGN.md section
+        5.23; msiren_residual_scale); bit for bit what ``residual_scale.residual_scale_on_host`` gives.  No images and no weights of the model are
+        involved."""
+        from . import align_group as ag, residual_scale as rs
+
+        self._ensure_handle()
+        t = _targets(targets)
+        m, th, tw = t.shape
+        sim = None if simulated is None else _exactly(simulated, t.shape, "simulated")
+        w, gb = _weights_intensity(weights, intensity, t.shape)
+        if gb is not None and sim is None:
+            raise ValueError("intensity needs simulated")
+        gs = None if groups is None else np.ascontiguousarray(ag.group_offsets(groups, m), dtype=np.int32)
+        G = 0 if gs is None else len(gs) - 1
+        o = _lib.ScaleOpts(C.sizeof(_lib.ScaleOpts), int(bool(centre)), float(quantile), float(tune), float(floor))
+        scale = np.full(m, np.inf, np.float64)
+        st = _optional(stats, (G if gs is not None else m, 4), 0, np.float64)
+        _lib.check(self._lib.msiren_residual_scale(self._h, _ptr(t, m), _ptr(sim, m), _ptr(w, m), _ptr(gb, m), m, th, tw, C.byref(o), _addr(gs), G, _ptr(scale, m),
+                                                   _ptr(st, m)))
+        return rs.ResidualScaleResult(scale, st)
