@@ -114,7 +114,9 @@ typedef struct msiren_config {
     int32_t dim_hidden;       /* H                                                              */
     int32_t dim_out;          /* must be 1 (squeeze(2)+rearrange at :451-455)                   */
     int32_t num_layers;       /* L: number of modulated sine layers before last_layer           */
-    int32_t latent_dim;       /* Z                                                              */
+    int32_t latent_dim;       /* Z; where dim_hidden or latent_dim is not a multiple of 16:
+                                 (num_layers > 1 ? dim_hidden : 0) + latent_dim <= 1792 (the
+                                 Modulator's input rows fit 64 KB of LDS), else MSIREN_E_INVALID */
     float w0;                 /* frequency of layers 1..L-1 and of last_layer (:196, :211-213)  */
     float w0_initial;         /* frequency of layer 0                                           */
     int32_t use_bias;

@@ -183,6 +183,24 @@ inline bool linear_tiled(int64_t B, int H, int Z, int Kh) {
     return B >= tile_min && (uint64_t)B * (uint64_t)widest < (1ULL << 32);
 }
 
+// The exact-fp32 per-layer launches (handles without the split-fp16 prologue: every fp32 handle, and 16-bit handles off the packed
+// (H, Z) pairs).  The MFMA Linear kernels read 16-k blocks of whole 16-feature tiles: H and Z multiples of 16.  Other shapes run the
+// VALU kernels: modulator_layer_kernel per Modulator layer; for the encoder the one fused per-tile encoder_kernel where Linear(64, Z)
+// does not fit (Z % 16; conv3 == Linear(2048, 64) always fits), otherwise encoder_conv_kernel + two MFMA GEMMs.
+inline bool modulator_mfma(int H, int Z) { return H % 16 == 0 && Z % 16 == 0; }
+inline bool encoder_fused_valu(int Z) { return Z % 16 != 0; }
+
+// LDS of one modulator_layer_kernel workgroup at its widest layer: the static partial sums (4 k-slices x MOD_ROWS x 64 features) plus
+// the dynamic input rows (MOD_ROWS x K floats, K = H + Z behind layer 0, Z for a one-layer Modulator).  The launch is a plain one:
+// at most 64 KB, which msiren_create checks (K <= 1792).
+constexpr int kModRows = 8;  // encoder_modulator.hip.h: MOD_ROWS
+constexpr int64_t kPlainLaunchLdsMax = 64 * 1024;
+inline int64_t modulator_valu_lds_bytes(int H, int Z, int L) {
+    const int64_t K = (int64_t)(L > 1 ? H : 0) + Z;
+    return 4 * kModRows * 64 * 4 + kModRows * K * 4;
+}
+inline bool modulator_valu_fits(int H, int Z, int L) { return modulator_mfma(H, Z) || modulator_valu_lds_bytes(H, Z, L) <= kPlainLaunchLdsMax; }
+
 // ---- call level --------------------------------------------------------------------------------------------------------------
 // msiren_forward_tiles cuts itself into chunks over two streams (host_plan.h) from host_pipe_min tiles up
 inline bool host_call_pipelines(const DispatchHandle& d, int64_t B) {

@@ -637,7 +637,8 @@ int launch_modulator(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B
     if (h->em_mod) return launch_prologue_f16x3(h, c, nullptr, z_dev, B, nullptr, mods_dev);
     h->last_prologue = "";  // (the per-layer exact-fp32 launches)
     size_t off = 0;
-    const bool mfma_ok = (h->H % 16 == 0) && (h->Z % 16 == 0);
+    static_assert(msiren::kModRows == msiren::MOD_ROWS, "dispatch.h sizes the VALU Modulator's LDS from the kernel's rows per workgroup");
+    const bool mfma_ok = msiren::modulator_mfma(h->H, h->Z);
     for (int l = 0; l < h->L && mfma_ok; ++l) {
         const int Kh = (l == 0 ? 0 : h->H);
         msiren::ModulatorMfmaParams mp{};
@@ -657,7 +658,7 @@ int launch_modulator(msiren_ctx* h, const Call& c, const float* z_dev, int64_t B
         off += (size_t)(Kh + h->Z) * h->H;
     }
     if (mfma_ok) return 0;
-    off = 0;
+    off = 0;  // (plain launches: at most 64 KB of LDS, static + dynamic -- msiren_create refuses the shapes past it, dispatch.h)
     for (int l = 0; l < h->L; ++l) {
         const int Kh = (l == 0 ? 0 : h->H);
         msiren::ModulatorLayerParams mp{};
@@ -691,7 +692,7 @@ int launch_encoder(msiren_ctx* h, const Call& c, const float* tiles_dev, int64_t
     // Shapes the MFMA Linear kernels do not take (latent_dim not a multiple of 16): one fused per-tile kernel.  (Until round 6 batches
     // below 48 tiles took it as well, for two launches less -- but its VALU sums run in another order than the MFMA kernels', so an
     // fp32 handle's latent depended in the last bits on the size of the batch a tile came in; the split-fp16 prologue never had that seam.)
-    if (h->Z % 16 != 0) {
+    if (msiren::encoder_fused_valu(h->Z)) {
         hipLaunchKernelGGL(msiren::encoder_kernel, dim3((unsigned)B), dim3(256), 0, sc.s, enc, tiles_dev, z_dev);
         HIPCHK(hipGetLastError());
         return 0;

@@ -160,6 +160,10 @@ int msiren_create(const msiren_config* cfg, msiren_handle* out) {
     if (cfg->dim_hidden < 1 || cfg->dim_hidden > 512) return fail(MSIREN_E_INVALID, "dim_hidden must be in [1,512], got %d", cfg->dim_hidden);
     if (cfg->num_layers < 1 || cfg->num_layers > 64) return fail(MSIREN_E_INVALID, "num_layers must be in [1,64], got %d", cfg->num_layers);
     if (cfg->latent_dim < 1) return fail(MSIREN_E_INVALID, "latent_dim must be positive, got %d", cfg->latent_dim);
+    // (shapes off the MFMA Linear kernels run the VALU Modulator, whose input rows live in the LDS of a plain launch: dispatch.h)
+    if (!msiren::modulator_valu_fits(cfg->dim_hidden, cfg->latent_dim, cfg->num_layers))
+        return fail(MSIREN_E_INVALID, "latent_dim too large for dim_hidden %% 16 != 0 or latent_dim %% 16 != 0: need %s + latent_dim <= 1792, got %d + %d",
+                    cfg->num_layers > 1 ? "dim_hidden" : "0", cfg->num_layers > 1 ? cfg->dim_hidden : 0, cfg->latent_dim);
     if (cfg->siren_patch_size < 2) return fail(MSIREN_E_INVALID, "siren_patch_size must be >= 2, got %d", cfg->siren_patch_size);
     if (cfg->inner_patch_size < 1 || cfg->outer_patch_size < cfg->inner_patch_size)
         return fail(MSIREN_E_INVALID, "need outer_patch_size >= inner_patch_size >= 1");

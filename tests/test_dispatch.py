@@ -254,6 +254,26 @@ PROG = textwrap.dedent(r"""
         assert(!linear_tiled(255, 512, 128, 512) && linear_tiled(256, 512, 128, 512));
         assert(!linear_tiled((1LL << 32) / 2048, 64, 2048, 0) && linear_tiled((1LL << 32) / 2048 - 1, 64, 2048, 0));
 
+        // (the shapes tests/fp32_prologue_cases.py relies on: H < 512 from 1024 rows, 512-wide layers from 256 -- by the layer's own
+        //  H, so conv3 (64 outputs) of a 512-latent encoder stays on 16 x 16 tiles at 273 rows while its Linear(64, 512) is tiled)
+        assert(!linear_tiled(1023, 48, 48, 48) && linear_tiled(1024, 48, 48, 0) && linear_tiled(1041, 256, 128, 256));
+        assert(!linear_tiled(273, 64, 2048, 0) && linear_tiled(273, 512, 64, 0) && linear_tiled(273, 512, 512, 512) && !linear_tiled(255, 512, 512, 512));
+
+        // exact-fp32 per-layer launches: the MFMA Linear kernels take H and Z that are multiples of 16, the VALU Modulator everything
+        // else; the fused per-tile encoder kernel where Linear(64, Z) does not fit them (Z alone decides)
+        assert(modulator_mfma(256, 128) && modulator_mfma(48, 48) && modulator_mfma(64, 16) && modulator_mfma(512, 512) && modulator_mfma(256, 320));
+        assert(!modulator_mfma(100, 24) && !modulator_mfma(250, 256) && !modulator_mfma(256, 24) && !modulator_mfma(20, 3) && !modulator_mfma(8, 16));
+        assert(encoder_fused_valu(24) && encoder_fused_valu(3) && encoder_fused_valu(1300));
+        assert(!encoder_fused_valu(16) && !encoder_fused_valu(256) && !encoder_fused_valu(128));
+        assert(!modulator_mfma(250, 256) && !encoder_fused_valu(256));  // the MFMA encoder in front of the VALU Modulator
+        // the VALU Modulator's LDS: 8 192 static + MOD_ROWS K 4 of input rows, K = (L > 1 ? H : 0) + Z; a plain launch carries 64 KB
+        assert(modulator_valu_lds_bytes(100, 24, 3) == 8192 + 8 * 124 * 4 && modulator_valu_lds_bytes(100, 24, 1) == 8192 + 8 * 24 * 4);
+        assert(modulator_valu_lds_bytes(500, 1292, 2) == 65536 && modulator_valu_fits(500, 1292, 2));
+        assert(modulator_valu_lds_bytes(500, 1300, 2) == 65792 && !modulator_valu_fits(500, 1300, 2));
+        assert(modulator_valu_fits(500, 1300, 1) && modulator_valu_fits(500, 1792, 1) && !modulator_valu_fits(500, 1793, 1));
+        assert(modulator_valu_fits(512, 2048, 10) && modulator_valu_fits(496, 1312, 2));  // (the MFMA kernels keep nothing in LDS but partial sums)
+        assert(!modulator_valu_fits(500, 0x7fffffff, 2));                                  // (no overflow at the largest latent_dim)
+
         // ---- call level ----
         {   // a host call pipelines itself from host_pipe_min tiles up: split-fp16 trunk, L = 5, both prologue halves, weight-stationary
             const DispatchHandle d = f16x3(5);
