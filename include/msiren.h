@@ -48,7 +48,8 @@ extern "C" {
  * msiren_solve_volume_r(_dev) and msiren_solve_r_opts (rounds of that solve, reweighted by a Geman-McClure loss with one annealed scale per target);
  * msiren_align_stack_r(_dev) and msiren_align_stack_solve_group_r(_dev) (the robust volume cost and the grouped solve against a plain voxel stack read
  * trilinearly: no images, no trunk, no weights); msiren_residual_scale(_dev) and msiren_scale_opts (a robust scale per target or per group of targets
- * from an exact order statistic of the residuals, on the device: what every robust call takes as `scale`, without a host read).
+ * from an exact order statistic of the residuals, on the device: what every robust call takes as `scale`, without a host read);
+ * msiren_leave_out_targets(_dev) (every target predicted from the fusion of the targets outside its own group: the left-out residual, in one call).
  * 8: msiren_sample_ragged_mods_native(_dev) and msiren_resample_slices_native(_dev) (per-patch coordinate sets and the reconstruction at
  * points in the handle's own trunk arithmetic) added.
  * 7: msiren_sample_ragged_* (one coordinate set per patch on the exact-fp32 trunks) and msiren_resample_slices* (the reconstruction at
@@ -1119,6 +1120,57 @@ MSIREN_API int msiren_residual_scale_dev(msiren_handle h, const float* targets_d
                                          int32_t th, int32_t tw, const msiren_scale_opts* opts /* host */,
                                          const int32_t* group_start /* (n_groups + 1), host, or NULL */, int64_t n_groups, double* scale_dev /* (m) */,
                                          double* stats_dev /* (S, 4) or NULL */);
+
+/* Build-defined: every target PREDICTED FROM THE OTHERS -- the stack that msiren_fuse_targets builds from all targets outside
+ * the target's own group of consecutive targets, read back onto the target's lattice as msiren_project_volume reads a stack -- in one call at about the
+ * cost of two projections, instead of one fusion and one projection per group.  The residual against such a prediction is not biased towards zero as
+ * the residual against a stack the target helped to build is: the input for msiren_residual_scale, and the score by which thickness and min_coverage
+ * can be chosen.  No images, no trunk: the handle need not hold committed weights.
+ *     targets (m, th, tw) float32;  maps (m, 9) float32;  weights (m, th, tw) float32 or NULL (all 1);  intensity (m, 2) float32 or NULL ((1, 0));
+ *     opts (HOST memory in both forms): msiren_fuse_targets' options;  group_start (n_groups + 1) int32, HOST memory in both forms, or NULL with
+ *     n_groups = 0: every target is its own group.  With it: msiren_residual_scale's conventions, group y = targets group_start[y] .. group_start[y + 1] - 1
+ *     (first offset 0, last m, strictly ascending);  simulated (m, th, tw) float32 out;  coverage, residual (m, th, tw) float32 out or NULL;  stats (m, 4)
+ *     float64 out or NULL;  flags (m) int32 out or NULL;  volume, volume_coverage (n, H, W) float32 out or NULL
+ *   fp64 + - * /, one rounding per operation, no fused multiply-add.  The records and flags, p, pa, pb, cp, i, j, k, the contribution test, i0, j0, fi,
+ *   fj, the four beta, the validity of a tap and the per-target terms k sn, k sd are msiren_fuse_targets' expressions, character for character.
+ *   PASS 1, per voxel v:  num_v, den_v = msiren_fuse_targets' two sums over all targets, q ascending.
+ *   PASS 2, per unflagged target q of the group [lo, hi), per target pixel (pi, pj):  N = D = 0.0;  the voxels in ascending flat index;  each voxel v that
+ *   contributes to q under msiren_fuse_targets' test and has (pi, pj) among its four taps, with bilinear weight beta_tap:
+ *     own_n = own_d = 0.0;  for q' = lo .. hi - 1 ascending, unflagged and contributing at v:  own_n += (k sn)_q',  own_d += (k sd)_q'
+ *     numL = num_v - own_n,  denL = den_v - own_d
+ *     v takes part iff  denL > min_coverage  and  denL > den_v MSIREN_LEAVE_OUT_FLOOR       (a power of two: the product is exact)
+ *     U = numL / denL  (fp64, never rounded to float32),  kb = k_q beta_tap,  N += kb U,  D += kb
+ *   coverage = (float)D;  simulated = (float)((g (N / D)) + b) if D > min_coverage, else NaN.  A flagged target: NaN, coverage 0.
+ *   residual and stats (m, 4) = (count, sum w, sum w r, sum (w r) r): msiren_project_volume's, from targets, weights and simulated.
+ *   volume, volume_coverage: the plain fusion of ALL targets, msiren_fuse_targets' bits ((float)(num_v / den_v) where den_v > min_coverage, else NaN;
+ *   (float)den_v).
+ *   THE FLOOR: den_v carries up to m roundings; where the group holds all but a sliver of a voxel's weight, denL is rounding noise.  Above
+ *   2^-20 den_v its relative error is at most m 2^-33.  Where the group is the voxel's only contributor, num_v and den_v are own_n and own_d exactly (the
+ *   same terms in the same order from 0.0), denL = 0 and the voxel is excluded exactly.
+ *   mri_inr_amd/leave_out.py: leave_out_on_host (numpy) gives the same bits.
+ * The _dev form enqueues on the handle's stream rotation without a host synchronisation and reads nothing back: the sequence of launches depends on
+ * m > 0, n_groups and which of residual / stats / volume / volume_coverage are given alone.  group_start is carried to the device in kernel arguments:
+ * the caller may reuse the array as soon as the call returns.  m_targets = 0 is valid: nothing that reads a target is launched; volume is NaN and
+ * volume_coverage 0 where given.  MSIREN_E_INVALID before any launch, naming the argument: everything msiren_fuse_targets refuses of opts, sizes and
+ * limits; with m > 0 a null targets, maps, opts or simulated; group_start and n_groups not both given or both absent, and a group_start that is not as
+ * above; a device pointer that is not 4-byte aligned (stats: 8).  Under msiren_profile_enable: one entry per call, "leave_out_kernels". */
+#define MSIREN_LEAVE_OUT_FLOOR (1.0 / 1048576.0) /* 2^-20 */
+MSIREN_API int msiren_leave_out_targets(msiren_handle h, const float* targets_host /* (m, th, tw) */, int64_t m_targets, int32_t th, int32_t tw,
+                                        const float* maps_host /* (m, 9) */, const float* weights_host /* (m, th, tw) or NULL */,
+                                        const float* intensity_host /* (m, 2) or NULL */, const msiren_fuse_opts* opts,
+                                        const int32_t* group_start /* (n_groups + 1), host, or NULL */, int64_t n_groups, int64_t n_slices, int32_t height,
+                                        int32_t width, float* simulated_host /* (m, th, tw) */, float* coverage_host /* (m, th, tw) or NULL */,
+                                        float* residual_host /* (m, th, tw) or NULL */, double* stats_host /* (m, 4) or NULL */,
+                                        int32_t* flags_host /* (m) or NULL */, float* volume_host /* (n, H, W) or NULL */,
+                                        float* volume_coverage_host /* (n, H, W) or NULL */);
+MSIREN_API int msiren_leave_out_targets_dev(msiren_handle h, const float* targets_dev /* (m, th, tw) */, int64_t m_targets, int32_t th, int32_t tw,
+                                            const float* maps_dev /* (m, 9) */, const float* weights_dev /* (m, th, tw) or NULL */,
+                                            const float* intensity_dev /* (m, 2) or NULL */, const msiren_fuse_opts* opts /* host */,
+                                            const int32_t* group_start /* (n_groups + 1), host, or NULL */, int64_t n_groups, int64_t n_slices, int32_t height,
+                                            int32_t width, float* simulated_dev /* (m, th, tw) */, float* coverage_dev /* (m, th, tw) or NULL */,
+                                            float* residual_dev /* (m, th, tw) or NULL */, double* stats_dev /* (m, 4) or NULL */,
+                                            int32_t* flags_dev /* (m) or NULL */, float* volume_dev /* (n, H, W) or NULL */,
+                                            float* volume_coverage_dev /* (n, H, W) or NULL */);
 
 /* Image-quality scores of the evaluation harness (src/util/error.py:23-84 as mri_inr_amd/metrics.py restates them):
  * n pairs of (H, W) float32 images -> scores (n, 3) float64 = PSNR [dB], SSIM, NRMSE per pair, original first.

@@ -286,6 +286,9 @@ PROTOTYPES = {
                                             _vp]),
     "msiren_residual_scale": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(ScaleOpts), _vp, _i64, _vp, _vp]),
     "msiren_residual_scale_dev": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, C.POINTER(ScaleOpts), _vp, _i64, _vp, _vp]),
+    "msiren_leave_out_targets": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(FuseOpts), _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "msiren_leave_out_targets_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, C.POINTER(FuseOpts), _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
+                                               _vp]),
     "msiren_reconstruct_slices_grad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_reconstruct_slices_grad_dev": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp]),
     "msiren_upsampled_geometry": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32), C.POINTER(_i32)]),

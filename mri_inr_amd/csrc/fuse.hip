@@ -8,9 +8,12 @@
 // msiren_solve_volume_r(_dev): rounds of that solve, each reweighted by the Geman-McClure weight of the pixels' residuals
 // against the current iterate.  Kernels: solve_volume_r.hip.h and, launched as they are, solve_volume.hip.h's; refusals, scratch, the schedule and
 // the launch plan: solve_volume_r_plan.h.
+// msiren_leave_out_targets(_dev): every target predicted from the fusion of the targets outside its own group.  Kernels:
+// leave_out.hip.h and, launched as they are, fuse_setup_kernel and project_stats_kernel; refusals, scratch and the launch count: leave_out_plan.h.
 // The calls share the record of fuse_setup_kernel, the tiling and the two loops (fuse_visit_targets, project_visit_voxels), and on this side
 // the refusal, the checked launch and the launches of the set-up and of the fusion below.
 #include "solve_volume_r.hip.h"  // (and through it solve_volume.hip.h, project.hip.h, fuse.hip.h and the four plans)
+#include "leave_out.hip.h"
 #include "host_buffers.h"
 #include "host_ctx.h"
 
@@ -21,6 +24,7 @@ static_assert(msiren::kProjectSums == 4, "project_stats_kernel parks four sums p
 static_assert(sizeof(msiren_solve_opts) == 40, "msiren_solve_opts is 40 bytes");
 static_assert(sizeof(msiren_solve_r_opts) == 56, "msiren_solve_r_opts is 56 bytes");
 static_assert(msiren::kSolveRSums == 4, "irls_stats_kernel parks four sums per column");
+static_assert(sizeof(msiren::LooOffsets) == 4 * msiren::kLooOffsets && msiren::kLooOffsets % 256 == 0, "loo_upload_kernel's argument and grid");
 
 namespace {
 
@@ -233,9 +237,92 @@ int solve_r_on_stream(msiren_ctx* h, const Call& c, const msiren::SolveRArgs& a)
     return go.rc ? go.rc : profile_end(h, c.stream, e1, (int64_t)voxels, "solve_volume_r_kernels");
 }
 
+// the whole leave-out call on the call's stream, one profile entry; every pointer but opts and group_start is the device's, `a` has passed
+// leave_out_check and has something to write.  The sequence of launches depends on m > 0, the number of groups and which outputs are given alone
+// (leave_out_plan.h: leave_out_launches counts them): nothing is read back
+int leave_out_on_stream(msiren_ctx* h, const Call& c, const msiren::LeaveOutArgs& a) {
+    using namespace msiren;
+    int rc;
+    auto& sc = h->sc[c.stream];
+    const int G = a.m > 0 ? (int)a.n_groups : 0;
+    const LeaveOutLayout lay = leave_out_layout(a.m, a.tw, a.n_groups, a.n, a.H, a.W, a.stats != nullptr);
+    if ((rc = ensure(h, sc.ragged, lay.total))) return rc;
+    char* const base = (char*)sc.ragged.p;
+    double* const rec = a.m > 0 ? (double*)(base + lay.records) : nullptr;
+    int* const gs = G > 0 ? (int*)(base + lay.group_start) : nullptr;
+    double2* const sums = (double2*)(base + lay.sums);
+    double* const columns = a.stats && a.m > 0 ? (double*)(base + lay.columns) : nullptr;
+    const double spacing = a.opts ? a.opts->spacing : 1.0, thickness = a.opts ? a.opts->thickness : 1.0, min_coverage = a.opts ? a.opts->min_coverage : 0.0;
+    hipEvent_t e1 = nullptr;
+    if ((rc = profile_begin(h, c.stream, &e1))) return rc;
+    Launcher go{sc.s};
+    launch_setup(go, a.maps, a.intensity, spacing, thickness, a.m, rec, a.flags);
+    // group_start: up to 512 offsets per launch, by value in the kernel's arguments (no copy from a host buffer that the caller may reuse, no sync)
+    for (int64_t at = 0; at < (G > 0 ? (int64_t)G + 1 : 0); at += kLooOffsets) {
+        LooOffsets off{};
+        const int count = (int)std::min<int64_t>(kLooOffsets, (int64_t)G + 1 - at);
+        for (int i = 0; i < count; ++i) off.v[i] = a.group_start[at + i];
+        go(loo_upload_kernel, dim3(kLooOffsets / 256), off, gs, (int)at, count);
+    }
+    go(loo_sums_kernel, dim3((unsigned)fuse_tiles(a.n, a.H, a.W)), (const float*)a.targets, (const float*)a.weights, (const double*)rec, (int)a.m, a.th, a.tw, a.H, a.W,
+       (int)fuse_tiles_x(a.W), (int)fuse_tiles_y(a.H), spacing, min_coverage, sums, (float*)a.volume, (float*)a.volume_coverage);
+    if (a.m > 0) {
+        go(loo_gather_kernel, dim3((unsigned)project_tiles(a.m, a.th, a.tw)), (const float*)a.targets, (const float*)a.weights, (const double*)rec, (const double2*)sums,
+           (const int*)gs, G, a.th, a.tw, (int)a.n, a.H, a.W, (int)project_tiles_x(a.tw), (int)project_tiles_y(a.th), spacing, thickness, min_coverage, (float*)a.simulated,
+           (float*)a.coverage);
+        if (a.residual || a.stats)
+            go(project_stats_kernel, dim3((unsigned)a.m), (const float*)a.targets, (const float*)a.weights, (const float*)a.simulated, a.th, a.tw, columns, (float*)a.residual,
+               (double*)a.stats);
+    }
+    return go.rc ? go.rc : profile_end(h, c.stream, e1, a.m * a.th * a.tw, "leave_out_kernels");
+}
+
+// (m = 0 without the plain fusion: nothing to write)
+bool leave_out_has_work(const msiren::LeaveOutArgs& a) { return a.m > 0 || a.volume || a.volume_coverage; }
+
 }  // namespace
 
 extern "C" {
+
+int msiren_leave_out_targets_dev(msiren_handle h, const float* targets_dev, int64_t m, int32_t th, int32_t tw, const float* maps_dev, const float* weights_dev,
+                                 const float* intensity_dev, const msiren_fuse_opts* opts, const int32_t* group_start, int64_t n_groups, int64_t n, int32_t height,
+                                 int32_t width, float* simulated_dev, float* coverage_dev, float* residual_dev, double* stats_dev, int32_t* flags_dev, float* volume_dev,
+                                 float* volume_coverage_dev) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    const msiren::LeaveOutArgs a{targets_dev, m, th, tw, maps_dev, weights_dev, intensity_dev, opts, group_start, n_groups, n, height, width, simulated_dev, coverage_dev,
+                                 residual_dev, stats_dev, flags_dev, volume_dev, volume_coverage_dev, true};
+    if ((rc = refusal(msiren::leave_out_check, a))) return rc;  // (before the stream rotates)
+    if (!leave_out_has_work(a)) return 0;
+    return leave_out_on_stream(h, dev_call(h), a);
+}
+
+int msiren_leave_out_targets(msiren_handle h, const float* targets_host, int64_t m, int32_t th, int32_t tw, const float* maps_host, const float* weights_host,
+                             const float* intensity_host, const msiren_fuse_opts* opts, const int32_t* group_start, int64_t n_groups, int64_t n, int32_t height, int32_t width,
+                             float* simulated_host, float* coverage_host, float* residual_host, double* stats_host, int32_t* flags_host, float* volume_host,
+                             float* volume_coverage_host) {
+    int rc = check(h, false);
+    if (rc) return rc;
+    const msiren::LeaveOutArgs host{targets_host, m, th, tw, maps_host, weights_host, intensity_host, opts, group_start, n_groups, n, height, width, simulated_host,
+                                    coverage_host, residual_host, stats_host, flags_host, volume_host, volume_coverage_host, false};
+    if ((rc = refusal(msiren::leave_out_check, host))) return rc;
+    if (!leave_out_has_work(host)) return 0;
+    const Call c = make_call(h, true);
+    const size_t nt = (size_t)(m > 0 ? m * th * tw : 0) * sizeof(float), nv = (size_t)n * height * width * sizeof(float);
+    SyncHostCall io(h, c.stream);
+    const int i_t = io.in(targets_host, nt, HOST_COPY), i_m = io.in(maps_host, (size_t)m * 9 * sizeof(float), HOST_COPY), i_w = io.in(weights_host, nt, HOST_COPY);
+    const int i_gb = io.in(intensity_host, (size_t)m * 2 * sizeof(float), HOST_COPY);
+    // simulated is copied: project_stats_kernel reads it back
+    const int o_s = io.out(simulated_host, nt, HOST_COPY), o_c = io.out(coverage_host, nt, HOST_IN_PLACE), o_r = io.out(residual_host, nt, HOST_IN_PLACE);
+    const int o_st = io.out(stats_host, (size_t)m * 4 * sizeof(double), HOST_COPY), o_f = io.out(flags_host, (size_t)m * sizeof(int32_t), HOST_COPY);
+    const int o_v = io.out(volume_host, nv, HOST_IN_PLACE), o_vc = io.out(volume_coverage_host, nv, HOST_IN_PLACE);
+    if ((rc = io.begin())) return rc;
+    const msiren::LeaveOutArgs dev{io.src<float>(i_t), m, th, tw, io.src<float>(i_m), io.src<float>(i_w), io.src<float>(i_gb), opts, group_start, n_groups, n, height, width,
+                                   io.dst<float>(o_s), io.dst<float>(o_c), io.dst<float>(o_r), io.dst<double>(o_st), io.dst<int32_t>(o_f), io.dst<float>(o_v),
+                                   io.dst<float>(o_vc), true};
+    if ((rc = leave_out_on_stream(h, c, dev))) return rc;
+    return io.finish();
+}
 
 int msiren_solve_volume_r_dev(msiren_handle h, const float* targets_dev, int64_t m, int32_t th, int32_t tw, const float* maps_dev, const float* weights_dev,
                               const float* intensity_dev, const double* scale_dev, const msiren_solve_r_opts* opts, int64_t n, int32_t height, int32_t width,

@@ -1,13 +1,13 @@
 """The slice-to-volume registration calls of ``ModulatedSiren``, from ``resample`` to ``solve_volume_robust``, ``align_stack_solve`` and
-``residual_scale``: the ctypes binding of the ``msiren_resample_*``, ``msiren_align_*``, ``msiren_fuse_targets``, ``msiren_project_volume``,
-``msiren_solve_volume*`` and ``msiren_residual_scale`` entry points (DESIGN.md sections 5.8 to 5.20, 5.22 and 5.23), as the mixin ``_Registration`` the
-model inherits.
+``residual_scale`` and ``leave_out_targets``: the ctypes binding of the ``msiren_resample_*``, ``msiren_align_*``, ``msiren_fuse_targets``,
+``msiren_project_volume``, ``msiren_solve_volume*``, ``msiren_residual_scale`` and ``msiren_leave_out_targets`` entry points (DESIGN.md sections 5.8 to
+5.20 and 5.22 to 5.24), as the mixin ``_Registration`` the model inherits.
 
 Every public method reads the same way: check the inputs, build the options, allocate the outputs, one call into the library, wrap the
 result.  The rules all of them keep:
 
 * ``_ensure_committed()`` in front of everything that evaluates the model; ``fuse_targets``, ``project_volume``, the two volume solves and the
-  two ``align_stack_*`` methods and ``residual_scale`` involve no weights of the model and only need the handle (``_ensure_handle()``).
+  two ``align_stack_*`` methods, ``residual_scale`` and ``leave_out_targets`` involve no weights of the model and only need the handle (``_ensure_handle()``).
 * Outputs are filled before the call -- NaN for sampled images and volumes, 0 for sums, reports and coverage, -1 for ``stopped_at``, (1, 0)
   rows for an absent intensity, +inf for an estimated scale -- because the library may return without writing them (no targets, an empty grid, no rounds).
 * An absent optional array is a null pointer (``_addr``).  For m = 0 targets the fuse, project, solve-volume and residual-scale calls take null for every
@@ -709,3 +709,36 @@ class _Registration:
         _lib.check(self._lib.msiren_residual_scale(self._h, _ptr(t, m), _ptr(sim, m), _ptr(w, m), _ptr(gb, m), m, th, tw, C.byref(o), _addr(gs), G, _ptr(scale, m),
                                                    _ptr(st, m)))
         return rs.ResidualScaleResult(scale, st)
+
+    # ---- every target predicted from the others ----
+    def leave_out_targets(self, targets, maps, shape, spacing, *, groups=None, thickness=None, weights=None, intensity=None, min_coverage=0.0, coverage=False,
+                          residual=False, stats=False, volume=False):
+        """Every target as the OTHER targets predict it -> ``leave_out.LeaveOutResult``: ``simulated`` (m, th, tw) is what ``project_volume`` would read
+        from the ``fuse_targets`` stack of all targets outside the target's own group, in one device call instead of one fusion and one projection per
+        group.  targets, maps, shape = (n, H, W), spacing, thickness, weights, intensity and min_coverage as in ``fuse_targets``; ``groups``: offsets or
+        sizes of groups of consecutive targets as in ``residual_scale`` (None: every target on its own) -- a whole group is left out at a time, as the
+        slices of one acquisition are.  A voxel takes part where the coverage that is left without the group is above ``min_coverage`` and above
+        ``leave_out.LEAVE_OUT_FLOOR`` of the voxel's whole coverage; ``simulated`` is NaN where no such voxel reaches the pixel.  ``coverage``: the
+        pixels' coverage too; ``residual`` = targets - simulated and ``stats`` (m, 4) = (count, sum w, sum w r, sum (w r) r) as in ``project_volume``;
+        ``volume``: the plain fusion of all targets and its coverage too, ``fuse_targets``' bits.  The residual is not biased towards zero as the
+        residual against a stack that the target helped to build: the input for ``residual_scale``, and the score for choosing ``thickness`` and
+        ``min_coverage``.  Build-defined (msiren_leave_out_targets); bit for bit what ``leave_out.leave_out_on_host`` gives.
+        No images and no weights of the model are involved."""
+        from . import align_group as ag, leave_out as lo
+
+        self._ensure_handle()
+        t, mp, w, gb = _fuse_inputs(targets, maps, weights, intensity)
+        m, th, tw = t.shape
+        (n, Hh, Ww), _, vol, vcov, flags = _grid(shape, m, None, volume)
+        if not volume:
+            vol = None
+        gs = None if groups is None else np.ascontiguousarray(ag.group_offsets(groups, m), dtype=np.int32)
+        G = 0 if gs is None else len(gs) - 1
+        o = _lib.FuseOpts(C.sizeof(_lib.FuseOpts), 0, float(spacing), _thickness(thickness, spacing), float(min_coverage))
+        sim = np.full(t.shape, np.nan, np.float32)
+        cov = _optional(coverage, t.shape, 0)
+        res = _optional(residual, t.shape, np.nan)
+        st = _optional(stats, (m, 4), 0, np.float64)
+        _lib.check(self._lib.msiren_leave_out_targets(self._h, _ptr(t, m), m, th, tw, _ptr(mp, m), _ptr(w, m), _ptr(gb, m), C.byref(o), _addr(gs), G, n, Hh, Ww,
+                                                      _ptr(sim, m), _ptr(cov, m), _ptr(res, m), _ptr(st, m), _ptr(flags, m), _addr(vol), _addr(vcov)))
+        return lo.LeaveOutResult(sim, cov, res, st, flags, vol, vcov)
